@@ -2,6 +2,7 @@
 """bench.py -- self-play planning throughput on MI355X (BASELINE.json metric: self-play env-steps/sec & MCTS sims/sec).
 
     python bench.py --gpus 1 --steps 30 --warmup 5
+    python bench.py --gpus 1 --steps 30 --warmup 5 --dump-outputs DIR   # also DIR/*.npy: the last timed move's results (dump_outputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], "C2"): CartPole-v1, 50 simulations per move, 4096 parallel environments per GPU,
@@ -42,6 +43,24 @@ FLOP_PER_SIM = 2 * (MAC_TRANSITION + MAC_REWARD + MAC_VALUE)          # 327 680
 # evaluate that head (mz_search_fast.h: mlp_initial_tile(..., want_value = false)), so it is not counted
 FLOP_PER_ROOT = 2 * (MAC_REPRESENT + MAC_POLICY)                      # 153 600
 PEAK_FP32_MFMA_TFLOPS = 157.3                                         # MI355X_MICROARCH.md, v_mfma_f32_*_f32 dense peak
+DUMP_BYTES = 64_000_000                                               # --dump-outputs: at most this much in all
+
+
+def dump_outputs(p, out_dir):
+    """--dump-outputs: what the last timed move handed a caller of the self-play path -- Planner.selfplay_read(1): every env's
+    observation, action, reward, policy, root value, player and done flag -- as DIR/<field>.npy, float64 where the planner
+    returns float64, float32 otherwise (the integer fields are small: exact).  Above DUMP_BYTES (the C4 frames) a fixed seeded
+    sample of the environments is written, their indices as env_index.npy."""
+    rec = {k: v[0].astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in p.selfplay_read(1).items()}
+    per_env = sum(v.nbytes for v in rec.values()) // p.B + 8  # (+ its env_index entry)
+    budget = DUMP_BYTES - 4096  # (the .npy headers)
+    if per_env * p.B > budget:
+        idx = np.sort(np.random.RandomState(0).choice(p.B, budget // per_env, replace=False))
+        rec = {k: v[idx] for k, v in rec.items()}
+        rec['env_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in rec.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
 
 
 def cpu_baseline(num_sims, sample_envs, budget_s=20.0):
@@ -145,10 +164,11 @@ def conv_cpu_baseline(name, case, net, kw, full_sims):
 DOMINANT = {'c3': 'k_search_fast<256', 'c4': 'k_res_tower<', 'c5': 'k_conv3x3<15, 1, true, 15, false>'}  # dominant kernel of each workload (substring of its rocprof name)
 
 
-def measure_workload(args, name, rank, local_rank, world, torch, dist, red_dev, steps, warmup, preheat, with_cpu, with_sustained):
+def measure_workload(args, name, rank, local_rank, world, torch, dist, red_dev, steps, warmup, preheat, with_cpu, with_sustained, dump=None):
     """One of the other BASELINE.json configs (c3 / c4 / c5) measured exactly like the headline: `warmup` untimed lock-step
     moves, then `steps` timed ones between barriers, MAX over ranks; HIP-event pairs on the planner stream around each move's
-    kernel sequence give the roofline figure.  Returns the record (rank 0; None elsewhere)."""
+    kernel sequence give the roofline figure.  `dump`: directory for rank 0's dump_outputs.  Returns the record (rank 0; None
+    elsewhere)."""
     from helpers import build_conv, build_mlp, mlp_case
     from muzero_amd import planner as pl
 
@@ -185,6 +205,8 @@ def measure_workload(args, name, rank, local_rank, world, torch, dist, red_dev, 
     sync()
     elapsed = time.perf_counter() - t0
     prof = p.profile_end()
+    if dump and rank == 0:
+        dump_outputs(p, dump)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -228,7 +250,7 @@ def measure_workload(args, name, rank, local_rank, world, torch, dist, red_dev, 
 
 def run_conv_workload(args, name, rank, local_rank, world, torch, dist, red_dev='cuda', backend='nccl'):
     rec = measure_workload(args, name, rank, local_rank, world, torch, dist, red_dev, args.steps, args.warmup, args.preheat,
-                           not args.no_cpu_baseline, not args.no_sustained)
+                           not args.no_cpu_baseline, not args.no_sustained, args.dump_outputs)
     if rank == 0:
         rec['distributed'] = dist_record(dist, world, backend)
         print(json.dumps(rec), flush=True)
@@ -274,7 +296,7 @@ def configs_leg(args, rank, local_rank, world, torch, dist, red_dev):
 PROFILE_ROUND = 'round6'
 
 
-def lunar_leg(rank, local_rank, world, torch, dist, red_dev, steps=100, warm=20, preheat=100):
+def lunar_leg(rank, local_rank, world, torch, dist, red_dev, steps=100, warm=20, preheat=100, dump=None):
     """The north-star's "4 actions" wording: a LunarLander-v2-SHAPED search workload (MuZeroMLPNet 512 / 64 / 31 on (4, 9) observations,
     A = 4, config.py:170-201; the reference's shipped LunarLander checkpoint has these shapes), 4096 envs x 50 simulations.  Box2D is an
     absent dependency, so the env is the synthetic stand-in (fresh U[0,1) observations, reward 0, 1000-step episodes: MZ_ENV_SYNTHETIC);
@@ -295,7 +317,8 @@ def lunar_leg(rank, local_rank, world, torch, dist, red_dev, steps=100, warm=20,
         if world > 1:
             dist.barrier()
 
-    p.selfplay_step(1.0, preheat + warm)
+    if preheat + warm:
+        p.selfplay_step(1.0, preheat + warm)
     sync()
     p.profile_begin()
     t0 = time.perf_counter()
@@ -303,6 +326,8 @@ def lunar_leg(rank, local_rank, world, torch, dist, red_dev, steps=100, warm=20,
     sync()
     elapsed = time.perf_counter() - t0
     prof = p.profile_end()
+    if dump and rank == 0:
+        dump_outputs(p, dump)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -674,7 +699,11 @@ def main():
     ap.add_argument('--no-e2e', action='store_true', help='skip the env-steps-into-replay leg')
     ap.add_argument('--no-configs', action='store_true', help='skip the C3 / C4 / C5 / LunarLander-shaped legs of the default run')
     ap.add_argument('--no-learner', action='store_true', help='skip the learner-step leg (and, with N > 1 ranks, the gradient all-reduce leg)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what their last move computed (rank 0) as DIR/<name>.npy; see dump_outputs()')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.preheat < 0:
+        ap.error('--steps must be at least 1, --warmup and --preheat at least 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])
@@ -712,7 +741,7 @@ def main():
         dist.barrier()
 
     if args.workload == 'lunar':  # the LunarLander-shaped leg alone (diagnostics; part of `configs` in the default run)
-        rec = lunar_leg(rank, local_rank, world, torch, dist, red_dev, steps=args.steps, warm=args.warmup, preheat=args.preheat)
+        rec = lunar_leg(rank, local_rank, world, torch, dist, red_dev, steps=args.steps, warm=args.warmup, preheat=args.preheat, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(rec), flush=True)
         if world > 1:
@@ -745,7 +774,8 @@ def main():
     # phase), and W = 5 warm-up moves are 4 ms.  Untimed, disclosed as config.preheat_moves.
     if args.preheat:
         p.selfplay_step(1.0, args.preheat)
-    p.selfplay_step(1.0, args.warmup)
+    if args.warmup:
+        p.selfplay_step(1.0, args.warmup)
     sync()
     p.profile_begin()
     t0 = time.perf_counter()
@@ -753,6 +783,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     prof = p.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(p, args.dump_outputs)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -99,7 +99,8 @@ def test_calc_loss_and_updates_match_reference(name, kind, cname):
         loss, prio = learner.calc_loss(net, torch.device('cpu'), tr, weights)
         loss.backward()
         if step == 0:
-            np.testing.assert_allclose(prio, G[f'{pre}_prio'], **TOL)
+            # (Atari: the priorities come from the same value outputs as the loss, so they carry its blocked-sum rounding, host to host)
+            np.testing.assert_allclose(prio, G[f'{pre}_prio'], **(TOL if big == 0 else dict(rtol=5e-4, atol=2e-7)))
             for pn, pp in net.named_parameters():
                 ref = G[f'{pre}_grad_{pn}']
                 # (the Atari net sums 2304-position planes: float32 rounding of differently blocked sums, relative to the tensor's size)

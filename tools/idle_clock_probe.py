@@ -3,7 +3,8 @@
 moves after start-up, after 3 s of idleness and after an env reset on a busy GPU (answer on MI355X: the clocks).
     python tools/idle_clock_probe.py"""
 import sys, time, os
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo')); sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'tests'))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, 'tests'))
 from helpers import build_mlp, mlp_case
 from muzero_amd import planner as pl
 net = build_mlp(mlp_case('cartpole'))
