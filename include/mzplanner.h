@@ -34,6 +34,7 @@ extern "C" {
 #define MZ_ENV_TICTACTOE 2 /* TicTacToeEnv, games/tictactoe.py + games/env.py */
 #define MZ_ENV_GOMOKU 3    /* GomokuEnv (board = obs_h, stack 4, five in a row), games/gomoku.py + games/env.py */
 #define MZ_ENV_SYNTHETIC 4 /* stand-in for the Atari emulator (absent dependency): fresh U[0,1) frames, reward 0, 1000-step episodes */
+#define MZ_ENV_EXTERNAL 5  /* any environment the caller steps on the host (mz_selfplay_reset_external) */
 
 /* Everything uct_search reads from MuZeroConfig (config.py:51-103) and from the network constructors
  * (network.py:239-247, 504-512, 543-549), plus planner-only sizing knobs. */
@@ -189,6 +190,41 @@ typedef struct {
     int32_t acc_seq_length, unroll_steps, td_steps;  /* MuZeroConfig fields (config.py:58-94) */
 } mz_replay_ring;
 int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ring);
+
+/* Self-play on host-stepped environments: the reference's actor loop body (pipeline.py:91-113) over whatever env object the
+ * launcher built (env.reset / env.step / env.actions_mask / env.current_player, pipeline.py:83-104; e.g. the Atari envs of
+ * atari/run_training.py:86, the classic gym envs of classic/run_training.py:71), split in two at env.step:
+ *   mz_selfplay_external_act    -- obs, player, temperature, uct_search (pipeline.py:91-104): uploads the num_envs frames, builds the
+ *                                  observations on the device (StackFrameAndAction gym_env.py:271-353 and ScaledFloatFrame
+ *                                  gym_env.py:214-224 when asked), records (obs, player), searches with the Philox draws keyed like
+ *                                  mz_selfplay_step's, records (action, pi, root value) and returns the sampled actions;
+ *   mz_selfplay_external_commit -- the outcome of env.step (pipeline.py:106-113): records reward and done, advances step counts and
+ *                                  counters, and runs the device epilogue when a replay is attached (mz_selfplay_attach_replay).
+ * The host resets an env whose done it committed and hands its reset frame to the next act (as pipeline.py:83 does).
+ * mz_selfplay_read, mz_selfplay_counters and mz_selfplay_attach_replay work on this kind as on the device envs; mz_selfplay_step does not
+ * (MZ_E_STATE), nor do two acts without a commit between them or a commit without an act.
+ * A commit whose env has an open trajectory longer than the record ring while a replay is attached returns MZ_E_INVALID naming the env
+ * and runs no epilogue (the replay keeps its last good count); mz_selfplay_reset_external must follow. */
+typedef struct {
+    int32_t stack_history;     /* 0: h_frames are whole observations (obs_c*obs_h*obs_w float32 each), the env stacks itself.
+                                  S > 0: h_frames are the NEWEST unstacked frame; the device applies StackFrameAndAction(S) */
+    int32_t is_obs_image;      /* as gym_env.py:276: frame [C,H,W] -> obs [S*(C+1),H,W]; vector frame [D] -> obs [S, D+1] */
+    int32_t frame_c, frame_h, frame_w;   /* unstacked frame shape (vector frames: frame_c = D, h = w = 1) */
+    int32_t frame_u8;          /* 1: frames are uint8 and are scaled x / 255.0f on the device (ScaledFloatFrame, gym_env.py:214-224) */
+    int32_t max_episode_steps; /* sizes the record ring when a replay is attached (0: acc + unroll + td window) */
+    int32_t temp_switch_steps; /* temperature < 0: 1.0 for the first temp_switch_steps moves of an episode, then 0.1 (config.py:236-249:
+                                  6 TicTacToe, 30 Gomoku); 0: 6 when num_actions <= 10, else 30 */
+} mz_external_env;
+
+int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* env);
+/* Search the current observations of all num_envs envs and return the sampled actions.
+ *   h_frames [B, frame] uint8 or float32 as mz_external_env says (whole observations when stack_history == 0); h_mask uint8 [B, A];
+ *   h_cur / h_opp int32 [B] (env.current_player / env.opponent_player); temperature as mz_selfplay_step; h_action int32 [B] out. */
+int mz_selfplay_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur,
+                             const int32_t* h_opp, double temperature, int32_t* h_action);
+/* Report the outcome of the actions returned by the last act call: h_reward float32 [B], h_done uint8 [B].  done[e] = 1 means the host
+ * will hand env e's reset frame to the next act call. */
+int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done);
 
 /* Measurement hooks (bench.py): HIP-event timing on the planner's own stream.
  * mz_profile_begin/end bracket a region; mz_profile_end returns elapsed milliseconds and the number of

@@ -14,6 +14,7 @@
 
 #include "../../include/mzplanner.h"
 #include "mz_env.h"
+#include "mz_extenv.h"
 #include "mz_search.h"
 #include "mz_search_fast.h"
 #include "mz_convnet.h"
@@ -129,6 +130,15 @@ struct mz_planner {
     int* d_epi_off = nullptr;        // per-env slot offsets of the move being written (k_epi_scan)
     long long* d_epi_ctr = nullptr;  // reserved write cursor of the attached replay ring (k_epilogue reserves, k_epi_publish commits)
     long long selfplay_moves = 0;  // moves since mz_selfplay_reset
+    // host-stepped envs (MZ_ENV_EXTERNAL): device side of the frames / history, pinned staging of every upload and download
+    ExtEnv ext{};
+    int ext_od = 0;
+    bool ext_pending = false;  // an act is waiting for its commit
+    bool ext_broken = false;   // a commit found an open trajectory longer than the record ring: reset before anything else
+    void* h_ext_frames = nullptr;
+    unsigned char *h_ext_mask = nullptr, *h_ext_done = nullptr;
+    int *h_ext_cur = nullptr, *h_ext_opp = nullptr, *h_ext_action = nullptr, *h_ext_err = nullptr;
+    float* h_ext_reward = nullptr;
 
     // profiling
     bool profiling = false;
@@ -465,6 +475,8 @@ static int planner_init(mz_planner* p, bool conv) {
     return MZ_OK;
 }
 
+static void ext_free(mz_planner* p);
+
 extern "C" int mz_planner_destroy(mz_planner* p) {
     if (!p) return MZ_OK;
     (void)hipSetDevice(p->device);
@@ -488,6 +500,7 @@ extern "C" int mz_planner_destroy(mz_planner* p) {
         if (b) (void)hipFree(b);
     convnet_free(p->cnet);
     env_free(p->env);
+    ext_free(p);
     for (auto& pr : p->kev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (p->ev_begin) (void)hipEventDestroy(p->ev_begin);
     if (p->ev_end) (void)hipEventDestroy(p->ev_end);
@@ -1030,6 +1043,7 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
 extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_moves) {
     if (!p || n_moves < 1) return fail(MZ_E_INVALID, "bad argument to mz_selfplay_step");
     if (p->env_kind == MZ_ENV_NONE) return fail(MZ_E_STATE, "call mz_selfplay_reset first");
+    if (p->env_kind == MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "mz_selfplay_step on host-stepped envs: use mz_selfplay_external_act / _commit");
     if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
     const mz_config& c = p->cfg;
@@ -1071,6 +1085,176 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
         p->ring_pos = (p->ring_pos + 1) % p->ring_len;
         if (p->ring_count < p->ring_len) p->ring_count++;
     }
+    return MZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// self-play on host-stepped environments (mz_extenv.h)
+// ---------------------------------------------------------------------------------------------------------
+static void ext_free(mz_planner* p) {
+    void* dbufs[] = {p->ext.frames, p->ext.hist, p->ext.hist_act, p->ext.head, p->ext.reward, p->ext.done, p->ext.err};
+    for (void* b : dbufs)
+        if (b) (void)hipFree(b);
+    void* hbufs[] = {p->h_ext_frames, p->h_ext_mask, p->h_ext_done, p->h_ext_cur, p->h_ext_opp, p->h_ext_action, p->h_ext_err, p->h_ext_reward};
+    for (void* b : hbufs)
+        if (b) (void)hipHostFree(b);
+    p->ext = ExtEnv{};
+    p->h_ext_frames = nullptr; p->h_ext_mask = p->h_ext_done = nullptr;
+    p->h_ext_cur = p->h_ext_opp = p->h_ext_action = p->h_ext_err = nullptr;
+    p->h_ext_reward = nullptr;
+}
+
+static ExtLaunch ext_launch(mz_planner* p, double temperature) {
+    const mz_config& c = p->cfg;
+    ExtLaunch L{};
+    L.env = p->env; L.x = p->ext; L.B = c.num_envs; L.A = c.num_actions; L.OD = p->ext_od;
+    L.slot = p->ring_pos; L.prev_slot = (p->ring_pos + p->ring_len - 1) % p->ring_len; L.first = p->selfplay_moves == 0;
+    L.parity = (int)(p->selfplay_moves & 1); L.sims = c.num_simulations; L.check = p->has_replay ? 1 : 0; L.move_abs = p->selfplay_moves;
+    L.temperature = temperature; L.obs = p->d_obs; L.cur = p->d_cur; L.temp_out = p->d_temp;
+    L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root;
+    return L;
+}
+
+extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* x) {
+    if (!p || !x) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_external");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    const int S = x->stack_history;
+    if (S < 0 || x->frame_c < 1 || x->frame_h < 1 || x->frame_w < 1 || x->max_episode_steps < 0 || x->temp_switch_steps < 0)
+        return fail(MZ_E_INVALID, "mz_external_env: stack_history >= 0, frame dimensions >= 1, max_episode_steps >= 0, temp_switch_steps >= 0");
+    if (!x->is_obs_image && (x->frame_h != 1 || x->frame_w != 1))
+        return fail(MZ_E_INVALID, "mz_external_env: vector frames are frame_c = D, frame_h = frame_w = 1");
+    const long long FE = (long long)x->frame_c * x->frame_h * x->frame_w;
+    const long long stacked = S == 0 ? FE : (x->is_obs_image ? (long long)S * (x->frame_c + 1) * x->frame_h * x->frame_w : (long long)S * (x->frame_c + 1));
+    if (stacked != obs_dim(c))
+        return fail(MZ_E_INVALID, "mz_external_env: the stacked observation has " + std::to_string(stacked) + " values, the network's (obs_c*obs_h*obs_w) " +
+                                      std::to_string(obs_dim(c)));
+    if (S == 0 && x->frame_u8) return fail(MZ_E_INVALID, "mz_external_env: frame_u8 needs stack_history > 0 (whole observations are float32)");
+    ext_free(p);
+    p->env_kind = MZ_ENV_EXTERNAL;
+    p->ext_pending = p->ext_broken = false;
+    p->ring_len = (size_t)c.num_envs * obs_dim(c) * sizeof(float) * 64 > ((size_t)4 << 30) ? 16 : 64;  // as mz_selfplay_reset
+    if (p->has_replay) {  // the record ring holds every env's open trajectory (mz_selfplay_reset), bounded by the episode length when known
+        const int window = p->replay.acc + p->replay.K + p->replay.td;
+        int need = c.is_board_game ? c.num_actions + 1 : window;
+        if (x->max_episode_steps > 0) {
+            const int capped = x->max_episode_steps + (c.is_board_game ? 1 : p->replay.K + p->replay.td);
+            need = c.is_board_game ? capped : (window < capped ? window : capped);
+        }
+        if (need > p->ring_len) p->ring_len = (need + 7) & ~7;
+    }
+    p->selfplay_moves = 0;
+    p->ring_pos = 0;
+    p->ring_count = 0;
+    hipError_t e = env_alloc(p->env, ENV_EXTERNAL, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, 3, 3);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    ExtEnv& X = p->ext;
+    X.S = S; X.image = x->is_obs_image ? 1 : 0; X.C = x->frame_c; X.HW = x->frame_h * x->frame_w; X.FE = (int)FE; X.u8 = x->frame_u8 ? 1 : 0;
+    X.temp_steps = x->temp_switch_steps > 0 ? x->temp_switch_steps : (c.num_actions <= 10 ? 6 : 30);
+    p->ext_od = obs_dim(c);
+    const size_t B = (size_t)c.num_envs, fbytes = (size_t)FE * (X.u8 ? 1 : 4);
+    HIPCHK(hipMalloc(&X.frames, B * fbytes));
+    if (S > 0) {
+        HIPCHK(hipMalloc(&X.hist, B * S * fbytes));
+        HIPCHK(hipMalloc(&X.hist_act, B * S * sizeof(int)));
+        HIPCHK(hipMalloc(&X.head, 2 * B * sizeof(int)));
+        HIPCHK(hipMemsetAsync(X.head, 0, 2 * B * sizeof(int), p->stream));
+    }
+    HIPCHK(hipMalloc(&X.reward, B * sizeof(float)));
+    HIPCHK(hipMalloc(&X.done, B));
+    HIPCHK(hipMalloc(&X.err, sizeof(int)));
+    HIPCHK(hipHostMalloc(&p->h_ext_frames, B * fbytes, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_mask), B * c.num_actions, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_cur), B * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_opp), B * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_action), B * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_reward), B * sizeof(float), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_done), B, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_err), sizeof(int), hipHostMallocDefault));
+    const int none = INT_MAX;
+    HIPCHK(hipMemcpyAsync(X.err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur, const int32_t* h_opp,
+                                        double temperature, int32_t* h_action) {
+    if (!p || !h_frames || !h_mask || !h_cur || !h_opp || !h_action) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_act");
+    if (p->env_kind != MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "call mz_selfplay_reset_external first");
+    if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory: call mz_selfplay_reset_external");
+    if (p->ext_pending) return fail(MZ_E_STATE, "mz_selfplay_external_act twice: commit the last act's outcome first");
+    if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    const size_t B = (size_t)c.num_envs, fbytes = B * p->ext.FE * (p->ext.u8 ? 1 : 4);
+    // pinned staging: the copies below are true asynchronous DMA on the planner's stream
+    std::memcpy(p->h_ext_frames, h_frames, fbytes);
+    std::memcpy(p->h_ext_mask, h_mask, B * c.num_actions);
+    std::memcpy(p->h_ext_cur, h_cur, B * sizeof(int));
+    std::memcpy(p->h_ext_opp, h_opp, B * sizeof(int));
+    HIPCHK(hipMemcpyAsync(p->ext.frames, p->h_ext_frames, fbytes, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->d_mask, p->h_ext_mask, B * c.num_actions, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->d_cur, p->h_ext_cur, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->d_opp, p->h_ext_opp, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    const ExtLaunch L = ext_launch(p, temperature);
+    const int OD = p->ext_od;
+    if ((p->ext.S > 0 && p->ext.image && p->ext.HW % 4 == 0) || (p->ext.S == 0 && OD % 4 == 0))  // (four floats of one plane / run per group)
+        hipLaunchKernelGGL(k_ext_ingest<4>, dim3((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), c.num_envs), dim3(256), 0, p->stream, L);
+    else
+        hipLaunchKernelGGL(k_ext_ingest<1>, dim3((OD + 63) / 64, c.num_envs), dim3(64), 0, p->stream, L);
+    HIPCHK(hipGetLastError());
+    int rc = launch_search(p, c.num_envs, 0, true, false, false);  // (move_counter keys the Philox draws as in mz_selfplay_step)
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ext_record, dim3((c.num_envs * c.num_actions + 255) / 256), dim3(256), 0, p->stream, L);
+    HIPCHK(hipGetLastError());
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(p->h_ext_action, p->d_action, B * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(&err, p->d_err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (err) {
+        HIPCHK(hipMemsetAsync(p->d_err, 0, sizeof(int), p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        return fail(MZ_E_INVALID, "search kernel reported error " + std::to_string(err));
+    }
+    std::memcpy(h_action, p->h_ext_action, B * sizeof(int));
+    p->ext_pending = true;
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done) {
+    if (!p || !h_reward || !h_done) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_commit");
+    if (p->env_kind != MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "call mz_selfplay_reset_external first");
+    if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory: call mz_selfplay_reset_external");
+    if (!p->ext_pending) return fail(MZ_E_STATE, "mz_selfplay_external_commit without an mz_selfplay_external_act");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    const size_t B = (size_t)c.num_envs;
+    std::memcpy(p->h_ext_reward, h_reward, B * sizeof(float));
+    std::memcpy(p->h_ext_done, h_done, B);
+    HIPCHK(hipMemcpyAsync(p->ext.reward, p->h_ext_reward, B * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->ext.done, p->h_ext_done, B, hipMemcpyHostToDevice, p->stream));
+    const ExtLaunch L = ext_launch(p, 0.0);
+    hipLaunchKernelGGL(k_ext_commit, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, L);
+    HIPCHK(hipGetLastError());
+    p->ext_pending = false;
+    if (p->has_replay) {  // the length check must pass before the epilogue may read the trajectories
+        HIPCHK(hipMemcpyAsync(p->h_ext_err, p->ext.err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        if (*p->h_ext_err != INT_MAX) {
+            p->ext_broken = true;
+            return fail(MZ_E_INVALID, "env " + std::to_string(*p->h_ext_err) + ": open trajectory of more than " + std::to_string(p->ring_len) +
+                                          " moves outgrew the record ring (raise mz_external_env.max_episode_steps); no items written, reset next");
+        }
+        EpiLaunch E{};
+        E.env = p->env; E.ring = p->replay; E.B = c.num_envs; E.move_abs = p->selfplay_moves;
+        hipLaunchKernelGGL(k_epi_scan, dim3(1), dim3(1024), 0, p->stream, E);
+        hipLaunchKernelGGL(k_epilogue, dim3(c.num_envs), dim3(64), (size_t)p->ring_len * sizeof(double), p->stream, E);
+        hipLaunchKernelGGL(k_epi_publish, dim3(1), dim3(1), 0, p->stream, p->replay);
+        HIPCHK(hipGetLastError());
+    }
+    p->selfplay_moves++;
+    p->ring_pos = (p->ring_pos + 1) % p->ring_len;
+    if (p->ring_count < p->ring_len) p->ring_count++;
     return MZ_OK;
 }
 

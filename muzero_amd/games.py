@@ -1,6 +1,7 @@
-"""Host-side board games for evaluators and tools: `BoardGameEnv` semantics of the reference (`games/env.py:40-365`)
-with the win test of `games/tictactoe.py:33-77` / `games/gomoku.py:72-116` (n in a row through the last move only).
-Self-play does not use this class -- its environments live on the device (`csrc/mz_env.h`, same rules)."""
+"""Host-side environments: `BoardGameEnv` semantics of the reference (`games/env.py:40-365`) with the win test of
+`games/tictactoe.py:33-77` / `games/gomoku.py:72-116` (n in a row through the last move only), and the observation wrappers of
+`gym_env.py`.  The device-resident self-play has its own copies of the board games and CartPole (`csrc/mz_env.h`, same rules);
+these classes serve evaluators, tools and host-stepped self-play (`pipeline.run_self_play` with env objects)."""
 from typing import Optional, Tuple
 
 import numpy as np
@@ -139,6 +140,28 @@ class GomokuEnv(BoardGameEnv):
 
     def __init__(self, board_size: int = 15, stack_history: int = 4, num_to_win: int = 5) -> None:
         super().__init__(board_size=board_size, stack_history=stack_history, num_to_win=num_to_win, name='Gomoku')
+
+
+class ScaledFloatFrame:
+    """`gym_env.py:214-224`: frames as float32 scaled to [0, 1] (x / 255).  Host-stepped self-play with device frame stacking
+    recognises it inside `StackFrameAndAction` and uploads the raw uint8 frames instead, scaled on the device to the same values."""
+
+    def __init__(self, env) -> None:
+        self.env = env
+
+    def __getattr__(self, name):
+        return getattr(self.env, name)
+
+    @staticmethod
+    def observation(observation) -> np.ndarray:
+        return np.array(observation).astype(np.float32) / 255.0
+
+    def reset(self, **kwargs) -> np.ndarray:
+        return self.observation(self.env.reset(**kwargs))
+
+    def step(self, action):
+        obs, reward, done, info = self.env.step(action)
+        return self.observation(obs), reward, done, info
 
 
 class StackFrameAndAction:

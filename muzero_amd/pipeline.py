@@ -214,21 +214,99 @@ class EpisodeAssembler:
         del self.open[b][:n]
 
 
+DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari')
+MAX_ENV_THREADS = 16
+
+
+def _device_env_name(env) -> Optional[str]:
+    """The device environment `env` names (a string, or an object whose `name` / `spec.id` is one), else None."""
+    if isinstance(env, str):
+        return env
+    name = getattr(env, 'name', None) or getattr(getattr(env, 'spec', None), 'id', None)
+    return name if name in DEVICE_ENVS else None
+
+
+def resolve_self_play_envs(env, num_envs: int):
+    """How run_self_play plays `env`: ('device', name) for a device environment (a name, or one object whose name is one);
+    ('host', [env objects]) for a list / tuple of env objects, a factory `i -> env` (called `num_envs` times), or one env object
+    without a device implementation (then B = 1)."""
+    if isinstance(env, str):
+        if env not in DEVICE_ENVS:
+            raise ValueError(f'no device environment for {env!r}; available: {sorted(DEVICE_ENVS)}')
+        return 'device', env
+    if isinstance(env, (list, tuple)):
+        envs = list(env)
+    elif _device_env_name(env) is not None:
+        return 'device', _device_env_name(env)
+    elif hasattr(env, 'reset') and hasattr(env, 'step'):
+        envs = [env]
+    elif callable(env):
+        envs = [env(i) for i in range(int(num_envs))]
+    else:
+        raise ValueError(f'env must name a device environment ({sorted(DEVICE_ENVS)}), or be an env object, a list of them or a factory '
+                         f'i -> env; got {env!r}')
+    if not envs:
+        raise ValueError('no environments to play')
+    for e in envs:
+        if not (hasattr(e, 'reset') and hasattr(e, 'step')):
+            raise ValueError(f'an environment needs reset() and step(action); got {e!r}')
+    return 'host', envs
+
+
+def device_stack_parts(env):
+    """When `env` is a `games.StackFrameAndAction` -- directly or inside `games.PlayerIdAndActionMaskWrapper` (as `games.CartPoleEnv`
+    is) -- the device can do its stacking: returns (env to step, stack_history, is_obs_image, frames_u8).  The env to step is the
+    stacker's inner env; when that is a `games.ScaledFloatFrame`, it is the env inside it and its uint8 frames are scaled on the
+    device.  None otherwise."""
+    from muzero_amd.games import PlayerIdAndActionMaskWrapper, ScaledFloatFrame, StackFrameAndAction
+
+    inner = env.env if isinstance(env, PlayerIdAndActionMaskWrapper) else env
+    if not isinstance(inner, StackFrameAndAction):
+        return None
+    base, u8 = inner.env, False
+    if isinstance(base, ScaledFloatFrame):
+        base, u8 = base.env, True
+    return base, int(inner.stack_history), bool(inner.is_obs_image), u8
+
+
+def board_temperature_switch(config, train_steps: int = 0) -> int:
+    """The board schedule's switch from temperature 1.0 to 0.1 (config.py:236-249: 6 TicTacToe, 30 Gomoku), read off
+    `config.visit_softmax_temperature_fn`."""
+    fn = config.visit_softmax_temperature_fn
+    for s in range(100000):
+        if fn(s, train_steps) != 1.0:
+            if fn(s, train_steps) != 0.1 or fn(s + 1000, train_steps) != 0.1 or s == 0:
+                break
+            return s
+    raise ValueError('host-stepped board games support the temperature schedule "1.0 for the first n moves, then 0.1" (config.py:236-249)')
+
+
 def run_self_play(config, rank, network, device, env, data_queue, train_steps_counter, stop_event, tag: str = None,
-                  moves_per_drain: int = 16, max_moves: Optional[int] = None) -> int:
+                  moves_per_drain: int = 16, max_moves: Optional[int] = None, device_stack: bool = True, env_threads: int = 1) -> int:
     """Self-play until `stop_event` is set (pipeline.py:41-167).  `env` names a device environment ('CartPole-v1',
     'TicTacToe', 'Gomoku', or 'Synthetic-Atari': random frames standing in for the absent emulator); `config.num_envs` of
     them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
     `(Transition, priority)` tuples, assembled on the host from the device records -- or a
     `muzero_amd.replay.PrioritizedReplay(device='cuda')`: then the planner's DEVICE EPILOGUE builds the items on the GPU and
     writes them straight into that replay (no host assembly, no queue, no data collector thread); only rewards and done
-    flags are read back for the episode statistics.  Returns the number of env steps played."""
+    flags are read back for the episode statistics.  Returns the number of env steps played.
+
+    Host-stepped environments: `env` may also be a list / tuple of env objects, a factory `i -> env` (called `config.num_envs`
+    times), or one env object with no device implementation (B = 1) -- anything with the reference's interface (reset, step,
+    actions_mask, current_player, opponent_player; the last three default to an all-legal mask and players 1 / 1).  Each move
+    is one batched search on the GPU (`Planner.external_act`), env.step on the host, one `external_commit`; an env that is done
+    is reset on the host.  Envs that are `games.StackFrameAndAction` (directly or inside `games.PlayerIdAndActionMaskWrapper`)
+    have their stacking done on the device from the newest frame (`device_stack=False`: on the host).  The actor owns the env
+    objects while it runs: it may step an inner env of a wrapper, leaving the wrapper's own state stale.  `env_threads` (1 to 16)
+    host threads step the envs."""
+    kind, target = resolve_self_play_envs(env, int(getattr(config, 'num_envs', 1)))
+    if kind == 'host':
+        return _run_self_play_host(config, rank, network, device, target, data_queue, train_steps_counter, stop_event, tag, moves_per_drain,
+                                   max_moves, device_stack, env_threads)
     from muzero_amd import planner as pl
 
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU, 'Synthetic-Atari': pl.ENV_SYNTHETIC}
-    name = env if isinstance(env, str) else getattr(env, 'name', None) or getattr(getattr(env, 'spec', None), 'id', None)
-    if name not in kinds:
-        raise ValueError(f'no device environment for {name!r}; available: {sorted(kinds)}')
+    name = target
     num_envs = int(getattr(config, 'num_envs', 1))
     idx = device.index if getattr(device, 'index', None) is not None else 0
     p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx)
@@ -267,6 +345,97 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     tracker.close()
     p.close()  # (detaches the device epilogue: the replay's write cursor and priorities go back to its host side)
     return played * num_envs
+
+
+def _run_self_play_host(config, rank, network, device, envs, data_queue, train_steps_counter, stop_event, tag, moves_per_drain, max_moves,
+                        device_stack, env_threads) -> int:
+    """run_self_play over host-stepped env objects (see there): the reference's loop body (pipeline.py:83-113) for all envs at once."""
+    from muzero_amd import metrics as mzm
+    from muzero_amd import planner as pl
+    from muzero_amd.replay import PrioritizedReplay
+
+    env_threads = int(env_threads)
+    if not 1 <= env_threads <= MAX_ENV_THREADS:
+        raise ValueError(f'env_threads must be 1 to {MAX_ENV_THREADS}, got {env_threads}')
+    B = len(envs)
+    parts = [device_stack_parts(e) for e in envs] if device_stack else [None] * B
+    stacked = all(pt is not None for pt in parts)
+    if stacked and len({pt[1:] for pt in parts}) != 1:
+        raise ValueError('all envs must stack the same way (stack_history, is_obs_image, ScaledFloatFrame)')
+    step_envs = [pt[0] for pt in parts] if stacked else list(envs)
+    S, image, u8 = parts[0][1:] if stacked else (0, False, False)
+    frames = [np.asarray(e.reset()) for e in step_envs]
+    frame_shape = frames[0].shape
+    frame_dtype = np.uint8 if u8 else np.float32
+
+    idx = device.index if getattr(device, 'index', None) is not None else 0
+    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=B, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx)
+    p.load_state_dict(network.state_dict())
+    on_device = isinstance(data_queue, PrioritizedReplay)
+    obs_shape = getattr(network, 'input_shape', None)
+    if on_device:
+        p.attach_replay(data_queue, config, obs_shape=obs_shape)
+    spec = getattr(envs[0], 'spec', None)
+    max_steps = int(getattr(spec, 'max_episode_steps', None) or getattr(envs[0], 'max_episode_steps', None) or 0)
+    board = bool(config.is_board_game)
+    p.selfplay_reset_external(stack_history=S, is_obs_image=image, frame_shape=frame_shape, frame_u8=u8, max_episode_steps=max_steps,
+                              temp_switch_steps=board_temperature_switch(config, train_steps_counter.value) if board else 0)
+    asm = EpisodeAssembler(config, B, obs_shape)
+    tracker = mzm.ActorMetrics(mzm.run_file(config, f'actor{rank}', tag), B)
+    ones = np.ones((B, p.A), np.uint8)
+    rewards = np.zeros(B, np.float32)
+    dones = np.zeros(B, np.uint8)
+
+    def step_range(lo, hi, actions):
+        for i in range(lo, hi):
+            obs, r, d, _ = step_envs[i].step(int(actions[i]))
+            if d:
+                obs = step_envs[i].reset()  # (pipeline.py:83: the next game starts from a fresh reset)
+            frames[i], rewards[i], dones[i] = np.asarray(obs), r, 1 if d else 0
+
+    pool = None
+    if env_threads > 1:
+        from concurrent.futures import ThreadPoolExecutor
+
+        pool = ThreadPoolExecutor(env_threads)
+    cuts = [B * t // env_threads for t in range(env_threads + 1)]
+
+    version = weights_key(network)
+    played = pending = 0
+    try:
+        while not stop_event.is_set() and (max_moves is None or played < max_moves):
+            key = weights_key(network)
+            if key != version:  # learner pushed new weights (pipeline.py:266)
+                p.load_state_dict(network.state_dict())
+                version = key
+            T = -1.0 if board else float(config.visit_softmax_temperature_fn(0, train_steps_counter.value))
+            mask = np.stack([np.asarray(m, np.uint8).reshape(-1) for m in (getattr(e, 'actions_mask', None) for e in envs)]) \
+                if all(getattr(e, 'actions_mask', None) is not None for e in envs) else ones
+            cur = np.array([getattr(e, 'current_player', 1) for e in envs], np.int32)
+            opp = np.array([getattr(e, 'opponent_player', 1) for e in envs], np.int32)
+            actions = p.external_act(np.stack(frames).astype(frame_dtype, copy=False), mask, cur, opp, T)
+            if pool is None:
+                step_range(0, B, actions)
+            else:
+                for f in [pool.submit(step_range, cuts[t], cuts[t + 1], actions) for t in range(env_threads)]:
+                    f.result()
+            p.external_commit(rewards, dones)
+            tracker.moves(rewards[None].copy(), dones[None].copy())
+            played += 1
+            pending += 1
+            if not on_device and pending == moves_per_drain:
+                for item in asm.feed(p.selfplay_read(pending)):
+                    data_queue.put(item)
+                pending = 0
+        if not on_device and pending:
+            for item in asm.feed(p.selfplay_read(pending)):
+                data_queue.put(item)
+    finally:
+        if pool is not None:
+            pool.shutdown()
+        tracker.close()
+        p.close()
+    return played * B
 
 
 def run_board_game_evaluator(config, old_checkpoint_network, new_ckpt_network, device, env, temperature, checkpoint_files, stop_event,

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libmzplanner_hip.so')
 
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
-ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC = 0, 1, 2, 3, 4
+ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL = 0, 1, 2, 3, 4, 5
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
 
 # every symbol include/mzplanner.h declares (tests/test_abi.py checks the library exports all of them)
@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     'mz_last_error', 'mz_version', 'mz_planner_describe', 'mz_planner_create', 'mz_planner_destroy', 'mz_planner_set_param', 'mz_planner_commit_params',
     'mz_planner_initial_inference', 'mz_planner_recurrent_inference', 'mz_planner_hidden_size', 'mz_planner_search',
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
-    'mz_selfplay_attach_replay',
+    'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
 ]
 
@@ -48,6 +48,11 @@ class MzReplayRing(C.Structure):
     _fields_ = [('capacity', C.c_int64), ('state', C.c_void_p), ('action', C.c_void_p), ('pi_prob', C.c_void_p), ('value', C.c_void_p),
                 ('reward', C.c_void_p), ('priority', C.c_void_p), ('num_added', C.c_void_p), ('origin', C.c_void_p),
                 ('acc_seq_length', C.c_int32), ('unroll_steps', C.c_int32), ('td_steps', C.c_int32)]
+
+
+class MzExternalEnv(C.Structure):
+    _fields_ = [('stack_history', C.c_int32), ('is_obs_image', C.c_int32), ('frame_c', C.c_int32), ('frame_h', C.c_int32), ('frame_w', C.c_int32),
+                ('frame_u8', C.c_int32), ('max_episode_steps', C.c_int32), ('temp_switch_steps', C.c_int32)]
 
 
 _lib = None
@@ -84,6 +89,9 @@ def load_library():
     L.mz_selfplay_read.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mz_selfplay_counters.argtypes = [vp, i64p]
     L.mz_selfplay_attach_replay.argtypes = [vp, C.POINTER(MzReplayRing)]
+    L.mz_selfplay_reset_external.argtypes = [vp, C.POINTER(MzExternalEnv)]
+    L.mz_selfplay_external_act.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp]
+    L.mz_selfplay_external_commit.argtypes = [vp, vp, vp]
     L.mz_profile_begin.argtypes = [vp]
     L.mz_profile_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mz_planner_synchronize.argtypes = [vp]
@@ -252,6 +260,49 @@ class Planner:
 
     def selfplay_step(self, temperature=1.0, n_moves=1):
         _chk(self.lib.mz_selfplay_step(self.h, float(temperature), int(n_moves)))
+
+    # ---- self-play on host-stepped environments (mz_selfplay_reset_external / _act / _commit) ----
+    def selfplay_reset_external(self, stack_history=0, is_obs_image=False, frame_shape=None, frame_u8=False, max_episode_steps=0,
+                                temp_switch_steps=0):
+        """Start self-play on `num_envs` envs stepped by the caller.  `stack_history` 0: `external_act` gets whole observations (float32);
+        S > 0: it gets the newest unstacked frame of shape `frame_shape` ([C, H, W] images, [D] vectors) and the device applies
+        StackFrameAndAction(S, is_obs_image) (gym_env.py:271-353); `frame_u8`: uint8 frames scaled by 1 / 255 on the device
+        (ScaledFloatFrame, gym_env.py:214-224).  `max_episode_steps` bounds the record ring when a replay is attached; `temp_switch_steps`
+        is the board schedule's switch from temperature 1.0 to 0.1 (used when `external_act` gets temperature < 0)."""
+        if frame_shape is None:
+            frame_shape = (self.obs_dim,)
+        fs = tuple(int(d) for d in frame_shape)
+        if is_obs_image:
+            if len(fs) != 3:
+                raise ValueError(f'image frames are [C, H, W], got {fs}')
+            c, h, w = fs
+        else:
+            c, h, w = int(np.prod(fs)), 1, 1
+        self._ext_frame = (fs, np.uint8 if frame_u8 else np.float32)
+        x = MzExternalEnv(int(stack_history), int(bool(is_obs_image)), c, h, w, int(bool(frame_u8)), int(max_episode_steps), int(temp_switch_steps))
+        _chk(self.lib.mz_selfplay_reset_external(self.h, C.byref(x)))
+
+    def external_act(self, frames, mask, cur, opp, temperature):
+        """One search over every env's current frame (see selfplay_reset_external): frames [B, ...], mask [B, A] (bool), cur / opp [B]
+        player ids.  Returns the sampled actions, int32 [B]."""
+        shape, dt = self._ext_frame
+        B = self.B
+        f = np.ascontiguousarray(frames, dt)
+        if f.size != B * int(np.prod(shape)):
+            raise ValueError(f'frames: expected {B} frames of shape {shape}, got an array of shape {f.shape}')
+        m = np.ascontiguousarray(mask, np.uint8).reshape(B, self.A)
+        c = np.ascontiguousarray(np.broadcast_to(cur, (B,)), np.int32)
+        o = np.ascontiguousarray(np.broadcast_to(opp, (B,)), np.int32)
+        action = np.empty(B, np.int32)
+        _chk(self.lib.mz_selfplay_external_act(self.h, _p(f), _p(m), _p(c), _p(o), float(temperature), _p(action)))
+        return action
+
+    def external_commit(self, reward, done):
+        """The outcome of the last `external_act`'s actions: reward [B] (float32), done [B].  An env reported done hands its reset frame
+        to the next external_act."""
+        r = np.ascontiguousarray(np.broadcast_to(reward, (self.B,)), np.float32)
+        d = np.ascontiguousarray(np.broadcast_to(done, (self.B,)), np.uint8)
+        _chk(self.lib.mz_selfplay_external_commit(self.h, _p(r), _p(d)))
 
     def selfplay_read(self, n_moves, fields=None):
         """Records of the last `n_moves` moves, arrays [n_moves, B, ...].  `fields`: subset of ('obs', 'action', 'reward', 'pi',
