@@ -12,7 +12,9 @@ train-mode BatchNorm towers, heads, losses, backward, Adam -- no ATen kernel on 
 (learner.train_step), --graphed replays it as ONE HIP graph (learner.GraphedTrainStep, captured before the loop).  --host-assembly keeps the
 reference's host-side assembler (pipeline.py:118-165).
 
-    python examples/train_gomoku.py --train-steps 2000 --envs 128 [--autograd | --graphed] [--board 9]"""
+    python examples/train_gomoku.py --train-steps 2000 --envs 128 [--autograd | --graphed] [--board 9]
+
+Boards up to 19 x 19 plan on the GPU; above 15 x 15 the update is the PyTorch-ROCm one (--graphed or --autograd)."""
 import argparse
 import json
 import os
@@ -74,6 +76,9 @@ def main():
     cfg.num_envs, cfg.num_simulations, cfg.num_planes, cfg.num_res_blocks = args.envs, 32, 32, 2
     N = args.board
     A, obs_shape = N * N + 1, (9, N, N)
+    if N * N > 240 and not (args.graphed or args.autograd or args.host_assembly):
+        sys.exit(f'--board {N}: the hand-written conv learner takes boards up to 15 x 15 (240 points); boards above 15 x 15 train through the '
+                 'PyTorch-ROCm update: add --graphed (or --autograd)')
     net = MuZeroBoardGameNet(obs_shape, A, cfg.num_res_blocks, cfg.num_planes).to(dev)
     graphed = hip = None
     use_hip = not (args.graphed or args.autograd or args.host_assembly)

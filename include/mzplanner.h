@@ -42,7 +42,7 @@ typedef struct {
     /* network */
     int32_t net_kind;            /* MZ_NET_* */
     int32_t obs_c, obs_h, obs_w; /* observation shape; MLP nets flatten it (network.py:153-154) */
-    int32_t num_actions;
+    int32_t num_actions;         /* board nets (MZ_NET_BOARD): <= 384, boards of at most 361 points (19 x 19); MLP / Atari nets: <= 256 */
     int32_t num_planes;
     int32_t hidden_dim;          /* MLP only */
     int32_t num_res_blocks;      /* conv nets only */
@@ -103,7 +103,7 @@ const char* mz_version(void);
  *   per process, at first use (conv nets):
  *     MZ_ACTION_SPARSE=0    evaluate the dynamics net's action planes densely
  *     MZ_ACTION_FUSE=0      add the sparse action terms in their own kernel instead of the first conv's epilogue
- *     MZ_CONV_SPEC=0        no shape-specialised conv / tower builds
+ *     MZ_CONV_SPEC=0        no shape-specialised conv / tower builds (15 x 15 and 19 x 19 Gomoku towers, the Atari net's tiled stages)
  *     MZ_TOWER=0            one launch per conv instead of the persistent residual tower
  *     MZ_CONV_TILE=th*100+tw, MZ_CONV_G=n, MZ_CONV_NCT=n   force the tiled conv kernel's output tile / images per workgroup / channel tiles per wave */
 const char* mz_planner_describe(mz_planner* p);

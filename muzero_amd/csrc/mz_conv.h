@@ -79,9 +79,12 @@ __device__ __forceinline__ int conv_idiv(int p, float rcp_d) { return (int)(((fl
 // per-lane byte offset (ONE VGPR, loop-invariant) + uniform byte offset (SGPR: channel or weight step).  With plain
 // pointers hipcc keeps one 64-bit VGPR address per unrolled load alive across the loop (or emits flat loads that also
 // tick lgkmcnt and serialise against the LDS reads).
+// SIDE == 19 (NPT 23): two workgroups per CU -- 57 KB of LDS each, and a C5-19 layer (256 images x 2 channel slices) is then one wave
+// of workgroups on 256 CUs
 template <int NPT, int NCT, bool WHOLE, int SIDE = 0, bool SP = false>
-__global__ __launch_bounds__(256, (NCT * NPT > 15) ? 1 : 2) void k_conv3x3(const ConvLaunch L_) {
+__global__ __launch_bounds__(256, (NCT * NPT > 15 && SIDE != 19) ? 1 : 2) void k_conv3x3(const ConvLaunch L_) {
     static_assert(!SP || WHOLE, "the sparse action terms are fused into whole-image builds only");
+    static_assert(SIDE != 19 || (WHOLE && NPT == 23 && NCT == 1 && !SP), "the 19 x 19 build: whole image, 23 pixel tiles, one channel slice");
     // SIDE > 0: the launch geometry of a whole SIDE x SIDE image per workgroup, 128 output channels, as compile-time constants (the
     // launcher checks every one).  The kernel's index arithmetic is hoisted out of its loops, but with the geometry in kernel
     // arguments it is still ~4 % of a 140 us launch (prologue divisions, per-tap offsets, predicates): C5 0.757 -> 0.785 of the peak.
@@ -116,29 +119,34 @@ __global__ __launch_bounds__(256, (NCT * NPT > 15) ? 1 : 2) void k_conv3x3(const
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ibase), 0, -1, 0x00020000);
     auto pure_real = [&](int cb) { return cb * 16 + 16 <= L.cin_real; };
     // ---- staging plan, tile == whole image (stride 1): a channel of an image is hw contiguous floats.  Lane t of every wave
-    // owns pixel quad t of the group (4 consecutive pixels, one 16-byte load per channel); wave w owns the channels
-    // {w, 4+w, 8+w, 12+w} of each 16-channel block, i.e. exactly the float4 at slot 4w of each slab position: per block and
-    // thread 4 loads and 4 16-byte LDS writes.  The halo is zeroed once; it is never written again. ----
-    const int QP = (ihw + 3) >> 2;  // quads per image; the host guarantees G * QP <= 64
-    unsigned w_voff = 0;
-    int w_spos[4], w_pm[4], w_act = -1;
-    bool w_ok = false;
-    f32x4 w_sv[4];  // [i]: channel 4i + wave of the block, pixels p0 .. p0+3
+    // owns pixel quad t of the group (4 consecutive pixels, one 16-byte load per channel) -- and quad t + 64 in the 19 x 19
+    // build (QW = 2: 91 quads); wave w owns the channels {w, 4+w, 8+w, 12+w} of each 16-channel block, i.e. exactly the float4
+    // at slot 4w of each slab position: per block, thread and quad 4 loads and 4 16-byte LDS writes.  The halo is zeroed once;
+    // it is never written again. ----
+    constexpr int QW = SIDE == 19 ? 2 : 1;  // pixel quads per lane
+    const int QP = (ihw + 3) >> 2;  // quads per image; the host guarantees G * QP <= 64 * QW
+    unsigned w_voff[QW];
+    int w_spos[QW][4], w_pm[QW][4], w_act[QW];
+    f32x4 w_sv[QW][4];  // [u][i]: quad lane + 64u, channel 4i + wave of the block, pixels p0 .. p0+3
     if constexpr (WHOLE) {
         const float r_qp = 1.0f / (float)QP, r_iw = 1.0f / (float)L.iw;
-        const int g = conv_idiv(lane, r_qp), qd = lane - g * QP, p0 = qd * 4, bimg = img0 + g;
-        w_ok = lane < L.G * QP && bimg < L.B;
-        const int cimg = bimg < L.B ? bimg : L.B - 1;
-        size_t o = (size_t)(w_ok ? p0 : 0);
-        if (!L.in_ptrs) o += (size_t)cimg * L.cin_real * ihw;
-        else if (L.G != 1) o += (size_t)(L.in_ptrs[cimg] - L.in_base);
-        w_voff = (unsigned)(o * sizeof(float));
-        w_act = (w_ok && L.action) ? L.action[cimg] : -1;
 #pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int pp = p0 + e, py = conv_idiv(pp, r_iw), px = pp - py * L.iw;
-            w_spos[e] = (w_ok && pp < ihw) ? ((g < L.G ? g : 0) * plane + (py + 1) * siw + px + 1) * 4 + wave * L.qstride : -1;
-            w_pm[e] = L.cin > L.cin_real ? pp % L.num_actions : 0;
+        for (int u = 0; u < QW; u++) {
+            const int l = lane + 64 * u;
+            const int g = conv_idiv(l, r_qp), qd = l - g * QP, p0 = qd * 4, bimg = img0 + g;
+            const bool w_ok = l < L.G * QP && bimg < L.B;
+            const int cimg = bimg < L.B ? bimg : L.B - 1;
+            size_t o = (size_t)(w_ok ? p0 : 0);
+            if (!L.in_ptrs) o += (size_t)cimg * L.cin_real * ihw;
+            else if (L.G != 1) o += (size_t)(L.in_ptrs[cimg] - L.in_base);
+            w_voff[u] = (unsigned)(o * sizeof(float));
+            w_act[u] = (w_ok && L.action) ? L.action[cimg] : -1;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int pp = p0 + e, py = conv_idiv(pp, r_iw), px = pp - py * L.iw;
+                w_spos[u][e] = (w_ok && pp < ihw) ? ((g < L.G ? g : 0) * plane + (py + 1) * siw + px + 1) * 4 + wave * L.qstride : -1;
+                w_pm[u][e] = L.cin > L.cin_real ? pp % L.num_actions : 0;
+            }
         }
         for (int i = tid; i < bufsz / 2; i += 256) reinterpret_cast<float4*>(slab)[i] = make_float4(0.f, 0.f, 0.f, 0.f);  // both buffers
         if constexpr (SP) {
@@ -154,13 +162,16 @@ __global__ __launch_bounds__(256, (NCT * NPT > 15) ? 1 : 2) void k_conv3x3(const
         __syncthreads();
     }
     auto wfetch_real = [&](int cb, int i) {  // channel 4i + wave of block cb, clamped to a valid channel (branch-free)
+#pragma unroll
+        for (int u = 0; u < QW; u++) {
 #ifndef MZC_NO_FETCH
-        const int ch = cb * 16 + 4 * i + wave, chc = ch < L.cin_real ? ch : 0;
-        const conv_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs_in, w_voff, chc * ihw * (int)sizeof(float), 0);
-        w_sv[i] = f32x4{__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w)};
+            const int ch = cb * 16 + 4 * i + wave, chc = ch < L.cin_real ? ch : 0;
+            const conv_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs_in, w_voff[u], chc * ihw * (int)sizeof(float), 0);
+            w_sv[u][i] = f32x4{__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w)};
 #else
-        w_sv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            w_sv[u][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #endif
+        }
     };
     auto wfix_generic = [&](int cb) {  // overwrite the lanes of action-plane (network.py:440-444) and padding channels of block cb
 #pragma unroll
@@ -169,10 +180,13 @@ __global__ __launch_bounds__(256, (NCT * NPT > 15) ? 1 : 2) void k_conv3x3(const
             if (ch >= L.cin_real) {
                 const int t = ch < L.cin ? (int)(((long long)(ch - L.cin_real) * ihw) % L.num_actions) : 0;
 #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    int m = w_pm[e] + t;
-                    m = m >= L.num_actions ? m - L.num_actions : m;
-                    w_sv[i][e] = (ch < L.cin && m == w_act) ? 1.0f : 0.0f;
+                for (int u = 0; u < QW; u++) {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        int m = w_pm[u][e] + t;
+                        m = m >= L.num_actions ? m - L.num_actions : m;
+                        w_sv[u][i][e] = (ch < L.cin && m == w_act[u]) ? 1.0f : 0.0f;
+                    }
                 }
             }
         }
@@ -180,8 +194,12 @@ __global__ __launch_bounds__(256, (NCT * NPT > 15) ? 1 : 2) void k_conv3x3(const
     auto wstore = [&](int buf) {
         float* d = slab + buf * bufsz;
 #pragma unroll
-        for (int e = 0; e < 4; e++)
-            if (w_spos[e] >= 0) *reinterpret_cast<float4*>(d + w_spos[e]) = make_float4(w_sv[0][e], w_sv[1][e], w_sv[2][e], w_sv[3][e]);
+        for (int u = 0; u < QW; u++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (w_spos[u][e] >= 0)
+                    *reinterpret_cast<float4*>(d + w_spos[u][e]) = make_float4(w_sv[u][0][e], w_sv[u][1][e], w_sv[u][2][e], w_sv[u][3][e]);
+        }
     };
     // ---- staging plan, tiled images (any stride): positions r = tid, tid + 256; out-of-image positions read a clamped address and are zeroed ----
     unsigned voff[CONV_RK];
@@ -307,7 +325,7 @@ __global__ __launch_bounds__(256, (NCT * NPT > 15) ? 1 : 2) void k_conv3x3(const
     MZC_T(0);
     // B operands run two pixel tiles ahead of the MFMAs in a 3-slot ring; step n = tap * NPT + pt lives in xr[n % 3]
     float4 xr[3];
-    constexpr int FL = WHOLE ? 1 : 2 * CONV_RK;     // staging loads per tap: whole images 1 (taps 0..3), tiled 2 channels (taps 0..7)
+    constexpr int FL = WHOLE ? QW : 2 * CONV_RK;    // staging loads per tap: whole images QW (taps 0..3), tiled 2 channels (taps 0..7)
     constexpr int FT = WHOLE ? 4 : 8;               // taps that carry staging loads
     constexpr int FS = FL < NPT ? FL : NPT;         // of which this many go one per pixel tile, the rest in front
     for (int cb = 0; cb < n_cb; cb++) {
@@ -691,6 +709,8 @@ struct HeadLaunch {
     int B;
 };
 
+// FPT: 1x1-conv features per thread, oc * hw <= 256 * FPT (2: boards up to 240 points; 3: the policy head's 2 x 361 at 19 x 19)
+template <int FPT>
 __global__ __launch_bounds__(256) void k_head(const HeadLaunch L) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* feat = reinterpret_cast<float*>(smem);     // [oc*hw]
@@ -699,10 +719,10 @@ __global__ __launch_bounds__(256) void k_head(const HeadLaunch L) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* src = L.in_ptrs ? L.in_ptrs[b] : L.in + (size_t)b * L.C * L.hw;
     const int nf = L.oc * L.hw;
-    // 1x1 conv: feature i = (plane o, pixel p); threads stride over features (at most 2 * 240 of them)
-    float acc[2];
+    // 1x1 conv: feature i = (plane o, pixel p); threads stride over features (at most 256 * FPT of them)
+    float acc[FPT];
 #pragma unroll
-    for (int u = 0; u < 2; u++) {
+    for (int u = 0; u < FPT; u++) {
         const int i = tid + 256 * u;
         acc[u] = i < nf ? L.cb[i / L.hw] : 0.0f;
     }
@@ -712,7 +732,7 @@ __global__ __launch_bounds__(256) void k_head(const HeadLaunch L) {
         for (int i = tid; i < nc * L.hw; i += 256) stage[i] = src[(size_t)c0 * L.hw + i];
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < 2; u++) {
+        for (int u = 0; u < FPT; u++) {
             const int i = tid + 256 * u;
             if (i < nf) {
                 const int o = i / L.hw, p = i - o * L.hw;
@@ -722,7 +742,7 @@ __global__ __launch_bounds__(256) void k_head(const HeadLaunch L) {
         }
     }
 #pragma unroll
-    for (int u = 0; u < 2; u++) {
+    for (int u = 0; u < FPT; u++) {
         const int i = tid + 256 * u;
         if (i < nf) feat[i] = acc[u] > 0.0f ? acc[u] : 0.0f;
     }

@@ -329,8 +329,23 @@ struct ConvGeom {
 };
 
 
+// The shape-specialised 19 x 19 build (k_conv3x3<23, 1, true, 19>, MZ_CONV_SPEC): one whole image and one 64-channel slice of 128 per
+// workgroup -- 23 pixel tiles (368 slots for 361 outputs, 98 % fill), a 21 x 21 slab per 16-channel block (441 positions, 28 KB per
+// buffer), two pixel quads per lane.  The generic geometry cuts a 19 x 19 image into nine ragged 8 x 8 tiles (361 of 576 slots, a
+// 10 x 10 slab each).
+inline bool conv_whole19(int oh, int ow, int stride, int cout) {
+    return stride == 1 && oh == 19 && ow == 19 && cout == 128 && conv_switches().conv_spec != 0;
+}
+
 inline ConvGeom conv_geometry(int B, int oh, int ow, int stride, int cout, bool allow_group = true) {
     static const int kNpt[9] = {1, 2, 3, 4, 5, 6, 9, 12, 15};
+    if (conv_whole19(oh, ow, stride, cout)) {
+        ConvGeom g{};
+        g.th = 19; g.tw = 19; g.G = 1; g.npt = 23; g.nct = 1; g.whole = true;
+        g.qstride = (21 * 21 * 4 + 63) & ~63;
+        g.cstride = 4 * g.qstride;
+        return g;
+    }
     auto round_npt = [&](int tiles) {
         for (int c : kNpt)
             if (tiles <= c) return c;
@@ -442,6 +457,10 @@ inline bool conv_run(hipStream_t st, const ConvLayerDev& Lr, int B, const float*
     } else if (sp) {
         L.relu = 0;  // k_action_sparse reads the pre-activation and applies the ReLU after its additions
     }
+    if (g.npt == 23) {  // conv_whole19 (no fused action terms: 57 KB of slabs + 17 KB of term rows exceed 64 KB; k_action_sparse adds them)
+        hipLaunchKernelGGL((k_conv3x3<23, 1, true, 19>), grid, dim3(256), lds, st, L);
+        return false;
+    }
     // shape-specialised builds (mz_conv.h, SIDE): a whole 15x15 image per workgroup, 128 output channels (Gomoku's towers)
     const bool spec_ok = conv_switches().conv_spec != 0;
     if (spec_ok && g.whole && g.nct == 1 && g.npt == 15 && g.G == 1 && L.stride == 1 && L.ih == 15 && L.iw == 15 && L.oh == 15 && L.ow == 15 &&
@@ -548,7 +567,8 @@ inline void head_run(hipStream_t st, const HeadDev& H, int B, const float* in, c
     L.in = in; L.in_ptrs = in_ptrs; L.C = H.C; L.hw = hw; L.oc = H.oc; L.n_out = H.n_out; L.cw = H.cw; L.cb = H.cb; L.lw = H.lw; L.lb = H.lb;
     L.mode = mode; L.out_scalar = out_scalar; L.out_probs = out_probs; L.B = B;
     const size_t lds = ((((size_t)H.oc * hw + 3) & ~(size_t)3) + (((size_t)H.n_out + 3) & ~(size_t)3) + (size_t)HEAD_CK * hw) * sizeof(float);
-    hipLaunchKernelGGL(k_head, dim3(B), dim3(256), lds, st, L);
+    if (H.oc * hw <= 2 * 256) hipLaunchKernelGGL(k_head<2>, dim3(B), dim3(256), lds, st, L);
+    else hipLaunchKernelGGL(k_head<3>, dim3(B), dim3(256), lds, st, L);
 }
 
 // the two of {a, b, c} that are not x
@@ -651,6 +671,8 @@ struct GTreeLaunch {
     int sim;
 };
 
+// ANY_N (more than 248 actions): numpy's sums at any n (np_sum_any_*)
+template <bool ANY_N>
 __global__ __launch_bounds__(256) void k_gtree_init(const GTreeLaunch G) {
     const SearchParams& P = G.P;
     unsigned char* smem = G.regions + (size_t)blockIdx.x * P.lds_bytes;
@@ -678,9 +700,11 @@ __global__ __launch_bounds__(256) void k_gtree_init(const GTreeLaunch G) {
     }
     root_noise_lanes(smem, P, e, a0, env_g, env_ok);
     __syncthreads();
-    if (a0 == 0 && env_ok) root_prior(smem, P, e, env_g);
+    if (a0 == 0 && env_ok) root_prior<ANY_N>(smem, P, e, env_g);
 }
 
+// MAXCH: action chunks of 16 lanes (16: A <= 256; 24: A <= 384, boards up to 19 x 19)
+template <int MAXCH>
 __global__ __launch_bounds__(256) void k_gtree_select(const GTreeLaunch G) {
     const SearchParams& P = G.P;
     unsigned char* smem = G.regions + (size_t)blockIdx.x * P.lds_bytes;
@@ -688,7 +712,7 @@ __global__ __launch_bounds__(256) void k_gtree_select(const GTreeLaunch G) {
     const int env_g = blockIdx.x * TILE_E + e;
     const bool env_ok = env_g < P.B;
     int lp, la;
-    tree_select<16>(smem, P, tid, env_ok, env_g, lp, la);
+    tree_select<MAXCH>(smem, P, tid, env_ok, env_g, lp, la);
     if (a0 == 0 && env_ok) {
         float* base = P.hidden + (size_t)env_g * P.NN * G.hidden_size;
         G.src_ptrs[env_g] = base + (size_t)lp * G.hidden_size;
@@ -718,8 +742,10 @@ __device__ __forceinline__ int nth_set_bit64(unsigned long long m, int idx) {
     for (int i = 0; i < idx; i++) m &= m - 1;
     return __ffsll((long long)m) - 1;
 }
-constexpr int MAX_CH64 = 4;  // action chunks of 64 lanes: A <= 256
+constexpr int MAX_CH64 = 4;       // action chunks of 64 lanes: A <= 256 (every config up to 15 x 15 Gomoku)
+constexpr int MAX_CH64_WIDE = 6;  // A <= 384: board nets up to 19 x 19 (362 actions)
 
+template <int MAX_CH64>
 __global__ __launch_bounds__(256) void k_gtree_select_wave(const GTreeLaunch G) {
     const SearchParams& P = G.P;
     const int lane = threadIdx.x & 63, env_g = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -827,12 +853,13 @@ __global__ __launch_bounds__(256) void k_gtree_backup(const GTreeLaunch G) {
     if (a0 == 0 && env_g < P.B) tree_expand_backup(smem, P, e, G.sim, G.reward[(size_t)env_g * G.rv_stride], G.value[(size_t)env_g * G.rv_stride]);
 }
 
+template <bool ANY_N>
 __global__ __launch_bounds__(256) void k_gtree_finish(const GTreeLaunch G) {
     const SearchParams& P = G.P;
     unsigned char* smem = G.regions + (size_t)blockIdx.x * P.lds_bytes;
     const int tid = threadIdx.x, e = tid >> 4, a0 = tid & 15;
     const int env_g = blockIdx.x * TILE_E + e;
-    if (a0 == 0 && env_g < P.B) tree_finish(smem, P, e, env_g);
+    if (a0 == 0 && env_g < P.B) tree_finish<ANY_N>(smem, P, e, env_g);
 }
 
 }  // namespace mz

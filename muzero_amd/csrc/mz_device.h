@@ -211,7 +211,9 @@ __device__ __forceinline__ void row_softmax(const float* lg, float* out, int n, 
 }
 
 // numpy's np.sum on a contiguous 1-D array (pairwise_sum, numpy/core/src/umath/loops_utils.h.src):
-// the reference normalises the masked prior with it (mcts.py:296) and the play policy (mcts.py:279).
+// the reference normalises the masked prior with it (mcts.py:296) and the play policy (mcts.py:279).  One level of recursion, inline:
+// numpy's result while both halves hold at most 128 elements (n <= 248, and n = 256) -- the LDS-resident search kernels and the HBM
+// trees of up to 248 actions; np_sum_any_* below for any n.
 __device__ inline double np_sum_f64(const double* a, int n) {
     if (n < 8) {
         double r = 0.0;
@@ -290,6 +292,51 @@ __device__ inline float np_sum_f32(const float* a, int n) {
     }
     return parts == 1 ? part[0] : part[0] + part[1];
 }
+
+// The same reduction at any n, numpy's recursion exactly: blocks of at most 128 elements with eight interleaved partial sums, longer
+// arrays split at n / 2 rounded down to a multiple of 8 (np_sum_deep: a recursion bounded by template depth, 26 levels cover any int
+// n).  Its calls make a kernel set up a call stack, so only the HBM-tree kernels of more than 256 actions (19 x 19 Gomoku: 362) use it.
+template <typename T>
+__device__ __forceinline__ T np_sum_block(const T* a, int n) {  // n <= 128
+    if (n < 8) {
+        T r = T(0);
+        for (int i = 0; i < n; i++) r = r + a[i];
+        return r;
+    }
+    T r[8];
+    for (int j = 0; j < 8; j++) r[j] = a[j];
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; j++) r[j] = r[j] + a[i + j];
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res = res + a[i];
+    return res;
+}
+
+template <typename T, int D>
+__device__ __noinline__ T np_sum_deep(const T* a, int n) {
+    if constexpr (D == 0) {
+        return np_sum_block(a, n);
+    } else {
+        if (n <= 128) return np_sum_block(a, n);
+        int n2 = n / 2;
+        n2 -= n2 % 8;
+        return np_sum_deep<T, D - 1>(a, n2) + np_sum_deep<T, D - 1>(a + n2, n - n2);
+    }
+}
+
+template <typename T>
+__device__ inline T np_sum_pairwise(const T* a, int n) {
+    if (n <= 128) return np_sum_block(a, n);
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    const T lo = n2 <= 128 ? np_sum_block(a, n2) : np_sum_deep<T, 26>(a, n2);
+    const T hi = n - n2 <= 128 ? np_sum_block(a + n2, n - n2) : np_sum_deep<T, 26>(a + n2, n - n2);
+    return lo + hi;
+}
+
+__device__ inline double np_sum_any_f64(const double* a, int n) { return np_sum_pairwise(a, n); }
+__device__ inline float np_sum_any_f32(const float* a, int n) { return np_sum_pairwise(a, n); }
 
 // ---- Philox4x32-10 counter-based RNG (production-mode randomness; parity mode injects recorded draws) ----
 struct Philox {

@@ -322,7 +322,9 @@ __device__ __forceinline__ void root_noise_lanes(unsigned char* smem, const Sear
     }
 }
 
-// root prior: Dirichlet mix + illegal-action mask + renormalisation (mcts.py:357-365, 244-247, 293-299); one lane per env
+// root prior: Dirichlet mix + illegal-action mask + renormalisation (mcts.py:357-365, 244-247, 293-299); one lane per env.
+// ANY_N: numpy's sum at any action count (np_sum_any_*: HBM trees of more than 248 actions)
+template <bool ANY_N = false>
 __device__ __forceinline__ void root_prior(unsigned char* smem, const SearchParams& P, int e, int env_g) {
     double* prior = reinterpret_cast<double*>(smem + P.t_prior) + e * P.A;
     float* pi0 = reinterpret_cast<float*>(smem + P.t_pi0) + e * P.A;
@@ -348,7 +350,7 @@ __device__ __forceinline__ void root_prior(unsigned char* smem, const SearchPara
         if (mk) {
             for (int a = 0; a < A; a++)
                 if (!mk[a]) prior[a] = 0.0;
-            const double s = np_sum_f64(prior, A);
+            const double s = ANY_N ? np_sum_any_f64(prior, A) : np_sum_f64(prior, A);
             if (s > 0)
                 for (int a = 0; a < A; a++) prior[a] = prior[a] / s;
         }
@@ -356,7 +358,7 @@ __device__ __forceinline__ void root_prior(unsigned char* smem, const SearchPara
         if (mk) {
             for (int a = 0; a < A; a++)
                 if (!mk[a]) pi0[a] = 0.0f;
-            const float s = np_sum_f32(pi0, A);
+            const float s = ANY_N ? np_sum_any_f32(pi0, A) : np_sum_f32(pi0, A);
             if (s > 0)
                 for (int a = 0; a < A; a++) pi0[a] = pi0[a] / s;
         }
@@ -366,6 +368,7 @@ __device__ __forceinline__ void root_prior(unsigned char* smem, const SearchPara
 
 // play: visit counts -> policy -> action (mcts.py:391-407); one lane per env
 // play: visit counts -> policy -> action (mcts.py:391-407); one lane per env.  raw_visits: the root children's N in LDS.
+template <bool ANY_N = false>
 __device__ __forceinline__ void play_from_visits(unsigned char* smem, const SearchParams& P, int e, int env_g, const int* raw_visits, double rootW,
                                                  int rootN) {
     double* tmp = reinterpret_cast<double*>(smem + P.t_tmp) + e * P.A;
@@ -386,7 +389,7 @@ __device__ __forceinline__ void play_from_visits(unsigned char* smem, const Sear
         if (v > bestv) { bestv = v; best = a; }
         tmp[a] = (T > 0.0) ? pow_policy((double)v, ex) : (double)v;
     }
-    double s = np_sum_f64(tmp, A);
+    double s = ANY_N ? np_sum_any_f64(tmp, A) : np_sum_f64(tmp, A);
     if (!(s > 0.0)) {
         // Every visit went to an illegal root child: the first simulation of a search ties ALL actions (U == 0 while the
         // root has N == 0, mcts.py:193-195) and may pick an illegal one, which then keeps winning on Q alone when simulations
@@ -429,6 +432,7 @@ __device__ __forceinline__ void play_from_visits(unsigned char* smem, const Sear
     P.out_root[env_g] = rootN > 0 ? rootW / (double)rootN : 0.0;
 }
 
+template <bool ANY_N = false>
 __device__ __forceinline__ void tree_finish(unsigned char* smem, const SearchParams& P, int e, int env_g) {
     int* rv = reinterpret_cast<int*>(smem + P.t_pi0) + e * P.A;  // the float32 root policy is no longer needed: reuse as int scratch
     const short* crow = child_row(smem, P, e, 0);
@@ -437,7 +441,7 @@ __device__ __forceinline__ void tree_finish(unsigned char* smem, const SearchPar
         rv[a] = c >= 0 ? node_at(smem, P, e, c)->N : 0;
     }
     const TreeNode* root = node_at(smem, P, e, 0);
-    play_from_visits(smem, P, e, env_g, rv, root->W, root->N);
+    play_from_visits<ANY_N>(smem, P, e, env_g, rv, root->W, root->N);
 }
 
 #include "mz_tree2.h"

@@ -310,13 +310,16 @@ extern "C" int mz_planner_create(const mz_config* cfg, int device_id, mz_planner
     if (!cfg || !out) return fail(MZ_E_INVALID, "null argument");
     const bool conv = cfg->net_kind == MZ_NET_BOARD || cfg->net_kind == MZ_NET_ATARI;
     if (cfg->net_kind != MZ_NET_MLP && !conv) return fail(MZ_E_INVALID, "unknown net_kind");
-    if (cfg->num_actions < 1 || cfg->num_actions > 256) return fail(MZ_E_INVALID, "num_actions must be in [1, 256]");
+    if (cfg->net_kind == MZ_NET_BOARD && (long long)cfg->obs_h * cfg->obs_w > 361) return fail(MZ_E_INVALID, "board larger than 361 points (19 x 19)");
+    // board nets reach 19 x 19 (362 actions: the HBM tree's select covers 384); MLP and Atari nets keep 256
+    const int max_actions = cfg->net_kind == MZ_NET_BOARD ? 384 : 256;
+    if (cfg->num_actions < 1 || cfg->num_actions > max_actions)
+        return fail(MZ_E_INVALID, max_actions == 384 ? "num_actions must be in [1, 384] for board nets" : "num_actions must be in [1, 256]");
     if (cfg->num_simulations < 1 || cfg->num_simulations > 4000) return fail(MZ_E_INVALID, "num_simulations out of range");
     if (conv) {
         if (cfg->obs_c < 1 || cfg->obs_h < 1 || cfg->obs_w < 1 || cfg->num_res_blocks < 0) return fail(MZ_E_INVALID, "bad conv network dimensions");
         if (cfg->net_kind == MZ_NET_ATARI && (cfg->obs_h != 96 || cfg->obs_w != 96))
             return fail(MZ_E_INVALID, "MuZeroAtariNet takes 96x96 frames (its hidden state is fixed at 6x6, network.py:515)");
-        if (cfg->net_kind == MZ_NET_BOARD && cfg->obs_h * cfg->obs_w > 240) return fail(MZ_E_INVALID, "board larger than 240 points");
         if (cfg->num_planes > 512) return fail(MZ_E_INVALID, "conv nets: num_planes must be <= 512");
     }
     if ((!conv && cfg->hidden_dim < 1) || cfg->num_planes < 1 || cfg->num_envs < 1) return fail(MZ_E_INVALID, "bad network/env dimensions");
@@ -352,7 +355,7 @@ static int planner_init(mz_planner* p, bool conv) {
         // is 727.7 us against 734.6 us (same box, same build)
         p->fuse_env = fe ? fe[0] != '0' : true;
         const char* gw = getenv("MZ_GTREE_WAVE");
-        p->gtree_wave = gw ? gw[0] != '0' : cfg->num_actions <= 64 * MAX_CH64;  // (C5: +4.3 %; C4, six actions: +0.5 %)
+        p->gtree_wave = gw ? gw[0] != '0' : cfg->num_actions <= 64 * MAX_CH64_WIDE;  // (C5: +4.3 %; C4, six actions: +0.5 %)
         const char* hx = getenv("MZ_HWX");
         if (hx) p->hwx = atoi(hx);
         const char* to = getenv("MZ_TREE_OLD");
@@ -836,12 +839,21 @@ static int launch_search(mz_planner* p, int batch, int deterministic, bool has_m
             convnet_initial(p->stream, p->cnet, batch, p->d_obs, p->d_rootptrs, nullptr, p->d_pi0, p->d_sim_value);  // root value discarded
             G.pi0 = p->d_pi0;
         }
-        hipLaunchKernelGGL(k_gtree_init, grid, block, 0, p->stream, G);
+        const bool any_n = c.num_actions > 248;  // (np_sum_f64 / _f32 are numpy's sums up to 248 actions: mz_device.h)
+        if (any_n) hipLaunchKernelGGL(k_gtree_init<true>, grid, block, 0, p->stream, G);
+        else hipLaunchKernelGGL(k_gtree_init<false>, grid, block, 0, p->stream, G);
         for (int sim = 0; sim < c.num_simulations; sim++) {
             G.sim = sim;
             // one wave per env (see k_gtree_select_wave); MZ_GTREE_WAVE=0/1 overrides (A/B measurements, tests)
-            if (p->gtree_wave) hipLaunchKernelGGL(k_gtree_select_wave, dim3((batch + 3) / 4), block, 0, p->stream, G);
-            else hipLaunchKernelGGL(k_gtree_select, grid, block, 0, p->stream, G);
+            // (more than 256 actions: the wider builds, 6 chunks of 64 lanes / 24 chunks of 16 lanes; the same arithmetic and tie order)
+            const bool wide = c.num_actions > 64 * MAX_CH64;
+            if (p->gtree_wave) {
+                if (wide) hipLaunchKernelGGL(k_gtree_select_wave<MAX_CH64_WIDE>, dim3((batch + 3) / 4), block, 0, p->stream, G);
+                else hipLaunchKernelGGL(k_gtree_select_wave<MAX_CH64>, dim3((batch + 3) / 4), block, 0, p->stream, G);
+            } else {
+                if (wide) hipLaunchKernelGGL(k_gtree_select<24>, grid, block, 0, p->stream, G);
+                else hipLaunchKernelGGL(k_gtree_select<16>, grid, block, 0, p->stream, G);
+            }
             if (scripted) {
                 G.reward = p->d_srewards + sim; G.value = p->d_svalues + sim; G.rv_stride = c.num_simulations;
             } else if (mlp) {
@@ -856,7 +868,8 @@ static int launch_search(mz_planner* p, int batch, int deterministic, bool has_m
             }
             hipLaunchKernelGGL(k_gtree_backup, grid, block, 0, p->stream, G);
         }
-        hipLaunchKernelGGL(k_gtree_finish, grid, block, 0, p->stream, G);
+        if (any_n) hipLaunchKernelGGL(k_gtree_finish<true>, grid, block, 0, p->stream, G);
+        else hipLaunchKernelGGL(k_gtree_finish<false>, grid, block, 0, p->stream, G);
     } else
     if (scripted) {
         p->last_dispatch = "k_search<SCRIPTED=true> (scripted-network test hook)";
