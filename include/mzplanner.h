@@ -93,13 +93,9 @@ const char* mz_version(void);
  * different kernel from one call to the next.
  *   per handle, at mz_planner_create:
  *     MZ_FORCE_GENERIC=1    the shape-generic k_search instead of the tuned k_search_fast builds
- *     MZ_FUSE_ENV=0|1       device self-play as three launches per move (0) or one (1, default for LDS-resident MLP searches)
- *     MZ_GTREE_WAVE=0|1     HBM trees: select with 16 lanes per env (0) or one wave per env (1, default up to 256 actions)
  *     MZ_HWX=0..3           work split of k_search_fast's helper waves (default by head kinds)
  *     MZ_TREE_OLD=1         evaluate every level of every descent (no selection cache; the anchor of the tree parity tests)
  *     MZ_HBM_TREE=1         MLP nets: trees in HBM around batched k_infer launches even where they fit LDS
- *     MZ_NO_FAST_LAYOUT=1   never give k_search_fast its own LDS carve-out (the LunarLander-shaped search then runs the generic kernel)
- *     MZ_FAST_AC4=0         the general-action-count build instead of the four-action one
  *   per process, at first use (conv nets):
  *     MZ_ACTION_SPARSE=0    evaluate the dynamics net's action planes densely
  *     MZ_ACTION_FUSE=0      add the sparse action terms in their own kernel instead of the first conv's epilogue

@@ -703,34 +703,12 @@ __global__ __launch_bounds__(256) void k_gtree_init(const GTreeLaunch G) {
     if (a0 == 0 && env_ok) root_prior<ANY_N>(smem, P, e, env_g);
 }
 
-// MAXCH: action chunks of 16 lanes (16: A <= 256; 24: A <= 384, boards up to 19 x 19)
-template <int MAXCH>
-__global__ __launch_bounds__(256) void k_gtree_select(const GTreeLaunch G) {
-    const SearchParams& P = G.P;
-    unsigned char* smem = G.regions + (size_t)blockIdx.x * P.lds_bytes;
-    const int tid = threadIdx.x, e = tid >> 4, a0 = tid & 15;
-    const int env_g = blockIdx.x * TILE_E + e;
-    const bool env_ok = env_g < P.B;
-    int lp, la;
-    tree_select<MAXCH>(smem, P, tid, env_ok, env_g, lp, la);
-    if (a0 == 0 && env_ok) {
-        float* base = P.hidden + (size_t)env_g * P.NN * G.hidden_size;
-        G.src_ptrs[env_g] = base + (size_t)lp * G.hidden_size;
-        G.dst_ptrs[env_g] = base + (size_t)(G.sim + 1) * G.hidden_size;
-        G.actions[env_g] = la;
-        if (P.trace_parent) {
-            P.trace_parent[(size_t)env_g * P.S + G.sim] = lp;
-            P.trace_action[(size_t)env_g * P.S + G.sim] = la;
-        }
-    }
-}
-
 // ---- select with ONE WAVE PER ENV (HBM trees, many actions) ----
-// k_gtree_select gives an env 16 lanes and a workgroup 16 envs: at C5 (256 envs, 226 actions) that is 16 workgroups on 256 CUs, each
-// lane walking 15 action chunks per level through dependent global loads -- 98 us per simulation, 2 % of a move.  Here a wave owns
-// an env (64 lanes -> 4 chunks per level at 226 actions) and a 256-thread workgroup four envs: 4x fewer dependent chunks per level,
-// 4x as many workgroups.  Same per-action arithmetic as select_level (child_Q + child_U, mcts.py:159-200), same tie set in
-// ascending action order, same draw protocol: identical results.
+// The LDS kernels' tree_select gives an env 16 lanes and a workgroup 16 envs: over HBM trees at C5 (256 envs, 226 actions) that was 16
+// workgroups on 256 CUs, each lane walking 15 action chunks per level through dependent global loads -- 98 us per simulation, 2 % of a
+// move.  Here a wave owns an env (64 lanes -> 4 chunks per level at 226 actions) and a 256-thread workgroup four envs: 4x fewer
+// dependent chunks per level, 4x as many workgroups.  Same per-action arithmetic as select_level (child_Q + child_U, mcts.py:159-200),
+// same tie set in ascending action order, same draw protocol: identical results.
 __device__ __forceinline__ float wave_max_f32(float v) {
     v = butterfly16_max(v);
     const float a = __shfl_xor(v, 16, 64);

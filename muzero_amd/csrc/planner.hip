@@ -47,6 +47,46 @@ static const char* kMlpNames[L_COUNT] = {
     "prediction_net.value_net.0",   "prediction_net.value_net.2",
 };
 
+// The compiled builds of the tuned kernel k_search_fast<planes, TR = TV = tiles, FUSE, AC, kFastHW, SPB> (mz_search_fast.h), one entry
+// each.  A handle's family (planes, tiles, ac) is fixed at create; a launch adds FUSE (env step in the kernel) and SPB.
+struct FastKey {
+    int planes, tiles, ac;  // ac: the action count as a constant (10, 4, 2) or 0
+    bool fuse, spb;
+};
+struct FastBuild {
+    FastKey key;
+    const void* fn;
+};
+#define MZ_FB(PL, T, F, AC, SPB) {{PL, T, AC, F, SPB}, reinterpret_cast<const void*>(&k_search_fast<PL, T, T, F, AC, kFastHW, SPB>)}
+#define MZ_FB4(PL, T) MZ_FB(PL, T, false, 0, false), MZ_FB(PL, T, false, 2, false), MZ_FB(PL, T, true, 0, false), MZ_FB(PL, T, true, 2, false)
+static const FastBuild kFastBuilds[] = {
+    // ten actions and MSE heads (TicTacToe's MLP net, config.py:106-136); SPB: the board games' self-play settings as constants
+    MZ_FB(256, 1, false, 10, false), MZ_FB(256, 1, true, 10, false), MZ_FB(256, 1, false, 10, true), MZ_FB(256, 1, true, 10, true),
+    // four actions, categorical heads, the 512-plane net (LunarLander's shape)
+    MZ_FB(512, 2, false, 4, false), MZ_FB(512, 2, true, 4, false),
+    // categorical heads by (planes, head tiles); AC = 2: two actions, single player (classic control)
+    MZ_FB4(256, 1), MZ_FB4(512, 2),
+#ifndef MZ_DEV_SHAPES  // development builds: only the C2 / C3 shapes (a third of the compile time); the others run the generic kernel
+    MZ_FB4(256, 2), MZ_FB4(512, 1),
+#endif
+};
+#undef MZ_FB4
+#undef MZ_FB
+
+static const FastBuild* fast_find(const FastKey& k) {
+    for (const FastBuild& b : kFastBuilds)
+        if (b.key.planes == k.planes && b.key.tiles == k.tiles && b.key.ac == k.ac && b.key.fuse == k.fuse && b.key.spb == k.spb) return &b;
+    return nullptr;
+}
+
+// the name mz_planner_describe reports for a k_search_fast launch
+static std::string fast_name(const FastKey& k, bool own_layout) {
+    char b[160];
+    snprintf(b, sizeof b, "k_search_fast<planes=%d, TR=%d, TV=%d, FUSE=%s, AC=%d, HW=%s%s> (LDS trees%s, one launch per move)", k.planes, k.tiles, k.tiles,
+             k.fuse ? "true" : "false", k.ac, kFastHW ? "true" : "false", k.spb ? ", SPB=true" : "", own_layout ? ", own carve-out" : "");
+    return b;
+}
+
 struct mz_planner {
     mz_config cfg;
     int device = 0;
@@ -71,14 +111,12 @@ struct mz_planner {
     double* d_ftab_tri = nullptr;
     InferParams ip{};
     // tuned kernel for the benchmark shapes (mz_search_fast.h): per-wave weight streams of the wide layers
-    int fast_planes = 0;  // 0: generic kernel only; 256 / 512: k_search_fast<P>
+    FastKey fast{};            // its build family (planner_init); planes 0: the shape-generic kernel only
+    bool fast_mse = false;     // the tuned kernel's shape, but an MSE head outside the ten-action build: the shape-generic kernel
+    bool fast_layout = false;  // k_search_fast runs in its own LDS carve-out (sp2f) unless a search is scripted
     bool tree_old = false;       // MZ_TREE_OLD=1: evaluate every level on every descent (A/B measurements, tests)
     bool force_generic = false;  // MZ_FORCE_GENERIC=1: run the shape-generic kernel (A/B measurements, tests)
-    bool fuse_env = false;       // device self-play as one kernel per move instead of three (MZ_FUSE_ENV=0/1 overrides the default)
     int hwx = -1;  // k_search_fast helper-wave work split (MZ_HWX=0..3 overrides the default: A/B measurements)
-    bool gtree_wave = true;   // HBM trees: select with one wave per env
-    bool no_fast_layout = false;  // MZ_NO_FAST_LAYOUT=1: never give k_search_fast its own LDS carve-out (diagnostic)
-    bool fast_ac4 = true;         // MZ_FAST_AC4=0: the general build instead of the four-action one (diagnostic)
     std::string last_dispatch = "none yet";  // what the last search launch ran (mz_planner_describe)
     float* d_stream[1] = {};
     float* d_bias_all = nullptr;
@@ -160,10 +198,9 @@ extern "C" const char* mz_planner_describe(mz_planner* p) {
     char b[512];
     const ConvSwitches& cs = conv_switches();
     snprintf(b, sizeof b,
-             "; switches: MZ_FORCE_GENERIC=%d MZ_FUSE_ENV=%d MZ_GTREE_WAVE=%d MZ_HWX=%d MZ_TREE_OLD=%d MZ_HBM_TREE=%d MZ_NO_FAST_LAYOUT=%d MZ_FAST_AC4=%d"
+             "; switches: MZ_FORCE_GENERIC=%d MZ_HWX=%d MZ_TREE_OLD=%d MZ_HBM_TREE=%d"
              " | per process: MZ_ACTION_SPARSE=%d MZ_ACTION_FUSE=%d MZ_CONV_SPEC=%d MZ_TOWER=%d MZ_CONV_TILE=%d MZ_CONV_G=%d MZ_CONV_NCT=%d",
-             (int)p->force_generic, (int)p->fuse_env, (int)p->gtree_wave, p->hwx, (int)p->tree_old, (int)p->hbm_tree, (int)p->no_fast_layout, (int)p->fast_ac4,
-             cs.action_sparse, cs.action_fuse, cs.conv_spec, cs.tower, cs.conv_tile, cs.conv_g, cs.conv_nct);
+             (int)p->force_generic, p->hwx, (int)p->tree_old, (int)p->hbm_tree, cs.action_sparse, cs.action_fuse, cs.conv_spec, cs.tower, cs.conv_tile, cs.conv_g, cs.conv_nct);
     g_describe = "search: " + p->last_dispatch + b;
     return g_describe.c_str();
 }
@@ -333,6 +370,16 @@ extern "C" int mz_planner_create(const mz_config* cfg, int device_id, mz_planner
     mz_planner* p = new mz_planner();
     p->cfg = *cfg;
     p->device = device_id;
+    {   // the per-handle diagnostic switches (mzplanner.h), read here once
+        const char* fg = getenv("MZ_FORCE_GENERIC");
+        const char* hx = getenv("MZ_HWX");
+        const char* to = getenv("MZ_TREE_OLD");
+        const char* ht = getenv("MZ_HBM_TREE");
+        p->force_generic = fg && fg[0] == '1';
+        if (hx) p->hwx = atoi(hx);
+        p->tree_old = to && to[0] == '1';
+        p->hbm_tree = !conv && ht && ht[0] == '1';  // (MLP nets; planner_init adds the trees that do not fit LDS)
+    }
     const int rc = planner_init(p, conv);  // every failure past this point releases what was allocated so far
     if (rc) {
         (void)mz_planner_destroy(p);
@@ -345,26 +392,6 @@ extern "C" int mz_planner_create(const mz_config* cfg, int device_id, mz_planner
 static int planner_init(mz_planner* p, bool conv) {
     const mz_config* cfg = &p->cfg;
     const int device_id = p->device;
-    {
-        const char* fg = getenv("MZ_FORCE_GENERIC");
-        p->force_generic = fg && fg[0] == '1';
-        const char* fe = getenv("MZ_FUSE_ENV");
-        // default: fused -- one launch per lock-step move instead of four (temperature kernel, record copy, search, env step).  Round 1
-        // kept the kernels separate for long moves because the env step ran single-lane behind four dependent global round trips at the
-        // search kernel's tail; with its inputs requested before the play-policy phase (mz_env.h, cartpole_prefetch) the fused C2 move
-        // is 727.7 us against 734.6 us (same box, same build)
-        p->fuse_env = fe ? fe[0] != '0' : true;
-        const char* gw = getenv("MZ_GTREE_WAVE");
-        p->gtree_wave = gw ? gw[0] != '0' : cfg->num_actions <= 64 * MAX_CH64_WIDE;  // (C5: +4.3 %; C4, six actions: +0.5 %)
-        const char* hx = getenv("MZ_HWX");
-        if (hx) p->hwx = atoi(hx);
-        const char* to = getenv("MZ_TREE_OLD");
-        p->tree_old = to && to[0] == '1';
-        const char* nf = getenv("MZ_NO_FAST_LAYOUT");
-        p->no_fast_layout = nf && nf[0] == '1';
-        const char* a4 = getenv("MZ_FAST_AC4");
-        p->fast_ac4 = !(a4 && a4[0] == '0');
-    }
     p->conv = conv;
     if (conv) {
         ConvNetDev& n = p->cnet;
@@ -378,8 +405,7 @@ static int planner_init(mz_planner* p, bool conv) {
         compute_layout(p);
     }
     if (!conv) {
-        const char* ht = getenv("MZ_HBM_TREE");
-        p->hbm_tree = (ht && ht[0] == '1') || cfg->num_actions > 16 * MAX_CH || (p->sp.lds_bytes > 160 * 1024 && !p->tree2_ok);
+        p->hbm_tree = p->hbm_tree || cfg->num_actions > 16 * MAX_CH || (p->sp.lds_bytes > 160 * 1024 && !p->tree2_ok);
         if (p->hbm_tree) {
             if (p->ip.lds_bytes > 160 * 1024) {
                 const int need = p->ip.lds_bytes;
@@ -460,20 +486,24 @@ static int planner_init(mz_planner* p, bool conv) {
     if (c.hidden_dim == 64 && (c.num_planes == 256 || c.num_planes == 512) && c.num_actions <= 16 && c.value_support_size <= 32 &&
         c.reward_support_size <= 32 && (c.value_support_size + 15) / 16 == (c.reward_support_size + 15) / 16 &&
         (size_t)c.num_envs * (c.num_simulations + 1) * 256 < ((size_t)1 << 32)) {  // (the tuned kernel addresses the node store with 32-bit byte offsets)
-        p->fast_planes = c.num_planes;
-#define MZ_FAST_LDS(PL, T, F, W) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_search_fast<PL, T, T, F, W, kFastHW>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds))
-#define MZ_FAST_LDS4(PL, T) MZ_FAST_LDS(PL, T, false, 0); MZ_FAST_LDS(PL, T, false, 2); MZ_FAST_LDS(PL, T, true, 0); MZ_FAST_LDS(PL, T, true, 2)
-        MZ_FAST_LDS(256, 1, false, 10); MZ_FAST_LDS(256, 1, true, 10);  // ten actions (TicTacToe)
-        MZ_FAST_LDS(512, 2, false, 4); MZ_FAST_LDS(512, 2, true, 4);    // four actions, the classic-control net (LunarLander's shape)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_search_fast<256, 1, 1, false, 10, kFastHW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_search_fast<256, 1, 1, true, 10, kFastHW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-#ifdef MZ_DEV_SHAPES  // development builds: only the C2 / C3 shapes of the tuned kernel (a third of the compile time)
-        MZ_FAST_LDS4(256, 1); MZ_FAST_LDS4(512, 2);
-#else
-        MZ_FAST_LDS4(256, 1); MZ_FAST_LDS4(256, 2); MZ_FAST_LDS4(512, 1); MZ_FAST_LDS4(512, 2);
-#endif
-#undef MZ_FAST_LDS4
-#undef MZ_FAST_LDS
+        // the build family (kFastBuilds).  An MSE head's one-neuron layer runs on the vector ALUs in its own summation order (mz_mlp.h,
+        // scalar_head_tile): of the tuned builds only the ten-action one has that form
+        const int tiles = p->net.L[L_VAL1].n_tiles;
+        const bool categorical = c.value_support_size > 1 && c.reward_support_size > 1;
+        if (c.num_planes == 256 && c.num_actions == 10 && c.value_support_size == 1 && c.reward_support_size == 1)
+            p->fast = FastKey{256, 1, 10, false, false};
+        else if (!categorical)
+            p->fast_mse = true;
+        else if (c.num_actions == 4 && c.num_planes == 512 && tiles == 2)
+            p->fast = FastKey{512, 2, 4, false, false};
+        else  // (AC = 2: compile-time specialisation for two actions, single player, mz_tree2.h)
+            p->fast = FastKey{c.num_planes, tiles, c.num_actions == 2 && !c.is_board_game ? 2 : 0, false, false};
+        if (p->fast.planes && !fast_find(p->fast)) p->fast = FastKey{};  // (-DMZ_DEV_SHAPES)
+        // the tuned kernel's own carve-out (sp2f): only where the generic one does not fit (the ten-action build is 256 planes wide and
+        // always fits the generic one)
+        p->fast_layout = !p->tree2_ok && p->tree2f_ok && p->fast.planes && p->fast.ac != 10 && !p->force_generic && !p->tree_old;
+        if (p->fast.planes)
+            for (const FastBuild& b : kFastBuilds) HIPCHK(hipFuncSetAttribute(b.fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     }
     return MZ_OK;
 }
@@ -542,17 +572,6 @@ static int packed_k(const MlpNet& n, int l, int g, int q, int s) {
     return k < L.k ? k : -1;
 }
 
-// the ten-action instantiation of the tuned kernel: ten actions AND MSE heads (TicTacToe's MLP net, config.py:106-136)
-static bool fast_ac10(const mz_planner* p) {
-    const mz_config& c = p->cfg;
-    return p->fast_planes == 256 && c.num_actions == 10 && c.value_support_size == 1 && c.reward_support_size == 1;
-}
-
-// the two-action instantiations: two actions, single player, categorical reward and value heads (classic control)
-static bool fast_two_act(const mz_config& c) {
-    return c.num_actions == 2 && !c.is_board_game && c.reward_support_size > 1 && c.value_support_size > 1;
-}
-
 extern "C" int mz_planner_commit_params(mz_planner* p) {
     if (!p) return fail(MZ_E_INVALID, "null planner");
     HIPCHK(hipSetDevice(p->device));
@@ -614,15 +633,15 @@ extern "C" int mz_planner_commit_params(mz_planner* p) {
     }
     p->sp.net = p->net;
     p->ip.net = p->net;
-    if (p->fast_planes) {
-        // ONE per-wave weight stream in consumption order (layout: mz_search_fast.h header)
-        const bool sc = kFastSC && fast_ac10(p), ax = kFastAX && fast_ac10(p);  // (mz_search_fast.h: scalar heads / action column outside the stream)
-        const int NT = p->fast_planes / 64, TR = sc ? 0 : p->net.L[L_REW1].n_tiles, TV = sc ? 0 : p->net.L[L_VAL1].n_tiles, RD = fast_rd(p->fast_planes, fast_two_act(p->cfg) ? 2 : 0);
+    if (p->fast.planes) {
+        // ONE per-wave weight stream in consumption order (layout: mz_search_fast.h header), for the family's weight ring depth
+        const bool sc = kFastSC && p->fast.ac == 10, ax = kFastAX && p->fast.ac == 10;  // (mz_search_fast.h: scalar heads / action column outside the stream)
+        const int NT = p->fast.planes / 64, TR = sc ? 0 : p->fast.tiles, TV = TR, RD = fast_rd(p->fast.planes, p->fast.ac);
         const int XG = ax ? 4 : 5;
         const int I_D1 = 0, I_D2 = I_D1 + XG, I_R1 = I_D2 + 4, I_R2 = I_R1 + 4, I_V1 = I_R2 + TR, I_V2 = I_V1 + 4, I_END = I_V2 + TV;
         const int SL = (I_END + RD - 1) / RD * RD;
         const size_t stream_floats = (size_t)WG_WAVES * SL * NT * 256;
-        std::vector<float> st(stream_floats + (ax ? (size_t)p->cfg.num_actions * p->fast_planes : 0), 0.0f);
+        std::vector<float> st(stream_floats + (ax ? (size_t)p->cfg.num_actions * p->fast.planes : 0), 0.0f);
         auto put = [&](int w, int slot, int j, int l, int row_tile, int g) {
             const MlpLayer& L = p->net.L[l];
             const HostTensor& W = p->params.find(std::string(kMlpNames[l]) + ".weight")->second;
@@ -648,7 +667,7 @@ extern "C" int mz_planner_commit_params(mz_planner* p) {
             const HostTensor& W = p->params.find(std::string(kMlpNames[L_DYN0]) + ".weight")->second;
             const MlpLayer& L = p->net.L[L_DYN0];
             for (int a = 0; a < p->cfg.num_actions; a++)
-                for (int r = 0; r < L.n; r++) st[stream_floats + (size_t)a * p->fast_planes + r] = W.data[(size_t)r * L.k + p->net.H + a];
+                for (int r = 0; r < L.n; r++) st[stream_floats + (size_t)a * p->fast.planes + r] = W.data[(size_t)r * L.k + p->net.H + a];
         }
         if (!p->d_stream[0]) HIPCHK(hipMalloc(&p->d_stream[0], st.size() * sizeof(float)));
         HIPCHK(hipMemcpy(p->d_stream[0], st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -740,37 +759,11 @@ static int next_kernel_events(mz_planner* p, hipEvent_t* a, hipEvent_t* b) {
     return MZ_OK;
 }
 
-// Whether the dispatch of launch_search has a k_search_fast build for this net's categorical-head shape.  Always true in the product build;
-// -DMZ_DEV_SHAPES compiles only two of the four (planes, head tiles) builds and falls back to the shape-generic kernel for the others, which
-// must then keep the generic LDS carve-out (the fast carve-out under the generic kernel overruns LDS).
-static bool fast_build_exists(const mz_planner* p) {
-#ifdef MZ_DEV_SHAPES
-    const int two = p->net.L[L_VAL1].n_tiles == 2;
+// the SearchParams fields the LDS-tree kernels and the HBM-tree sequence share, over a tree layout: the search configuration, this
+// call's modes and the planner's buffers.  The one place a search advances move_counter (the key of its Philox draws).
+static SearchParams search_params(mz_planner* p, const SearchParams& layout, int batch, int deterministic, bool has_mask, bool injected_rng) {
     const mz_config& c = p->cfg;
-    const bool four_act = p->fast_ac4 && c.num_actions == 4 && c.reward_support_size > 1 && c.value_support_size > 1 && p->fast_planes == 512 && two;
-    return four_act || (p->fast_planes == 512 && two) || (p->fast_planes == 256 && !two);
-#else
-    (void)p;
-    return true;
-#endif
-}
-
-// launches the fused search kernel over inputs that are already resident in the planner's device buffers
-static int launch_search(mz_planner* p, int batch, int deterministic, bool has_mask, bool injected_rng, bool scripted, const EnvLaunch* fenv = nullptr) {
-    const mz_config& c = p->cfg;
-    // the tuned kernel with its own LDS carve-out (sp2f): only where the generic carve-out does not fit AND k_search_fast is the kernel
-    // the dispatch below picks (categorical heads; the ten-action MSE build is 256 planes wide and always fits the generic one)
-    const bool fastlayout = !p->tree2_ok && p->tree2f_ok && p->fast_planes && !p->force_generic && !p->tree_old && !scripted &&
-                            c.value_support_size > 1 && c.reward_support_size > 1 && !p->no_fast_layout && fast_build_exists(p);
-    const bool mode2 = (p->tree2_ok && !p->tree_old) || fastlayout;
-    SearchParams s = fastlayout ? p->sp2f : (mode2 ? p->sp2 : p->sp);
-    s.tree_mode = mode2 ? 2 : 0;
-    s.net = p->net;
-    if (fastlayout) {  // the bias block sits `fast_delta` floats lower in this carve-out
-        s.net.b_base -= p->fast_delta;
-        for (int l = 0; l < L_COUNT; l++) s.net.L[l].b_lds -= p->fast_delta;
-    }
-    s.ftab_tri = p->d_ftab_tri;
+    SearchParams s = layout;
     s.discount = c.discount; s.board = c.is_board_game; s.has_bounds = c.has_known_bounds;
     s.kb_min = c.known_bounds_min; s.kb_max = c.known_bounds_max; s.alpha = c.root_dirichlet_alpha; s.eps = c.root_exploration_eps;
     s.deterministic = deterministic; s.has_mask = has_mask ? 1 : 0;
@@ -782,139 +775,119 @@ static int launch_search(mz_planner* p, int batch, int deterministic, bool has_m
     s.obs = p->d_obs; s.mask = p->d_mask; s.cur = p->d_cur; s.opp = p->d_opp; s.temperature = p->d_temp;
     s.noise = p->d_noise; s.u_tie = p->d_utie; s.u_final = p->d_ufinal; s.hidden = p->d_hidden; s.ftab = p->d_ftab;
     s.out_action = p->d_action; s.out_pi = p->d_pi; s.out_root = p->d_root; s.out_visits = p->d_visits; s.err = p->d_err;
-    s.s_pi0 = p->d_spi0; s.s_values = p->d_svalues; s.s_rewards = p->d_srewards; s.trace_parent = p->d_tparent; s.trace_action = p->d_taction;
-    s.seed = c.seed; s.move_counter = p->move_counter++; s.env_offset = 0; s.stamps = p->d_stamps;
+    s.seed = c.seed; s.move_counter = p->move_counter++; s.env_offset = 0;
     s.dbg_noise = p->d_dbg_noise; s.dbg_utie = p->d_dbg_utie; s.dbg_ufinal = p->d_dbg_ufinal;
+    return s;
+}
+
+// MLP nets whose trees fit LDS: one fused kernel per search (with fenv: per self-play move)
+static int launch_lds_search(mz_planner* p, int batch, int deterministic, bool has_mask, bool injected_rng, bool scripted, const EnvLaunch* fenv) {
+    const mz_config& c = p->cfg;
+    const bool fastlayout = p->fast_layout && !scripted;
+    const bool mode2 = (p->tree2_ok && !p->tree_old) || fastlayout;
+    SearchParams s = search_params(p, fastlayout ? p->sp2f : (mode2 ? p->sp2 : p->sp), batch, deterministic, has_mask, injected_rng);
+    s.tree_mode = mode2 ? 2 : 0;
+    s.net = p->net;
+    if (fastlayout) {  // the bias block sits `fast_delta` floats lower in this carve-out
+        s.net.b_base -= p->fast_delta;
+        for (int l = 0; l < L_COUNT; l++) s.net.L[l].b_lds -= p->fast_delta;
+    }
+    s.ftab_tri = p->d_ftab_tri;
+    s.s_pi0 = p->d_spi0; s.s_values = p->d_svalues; s.s_rewards = p->d_srewards; s.trace_parent = p->d_tparent; s.trace_action = p->d_taction;
+    s.stamps = p->d_stamps;
     s.fuse_env = fenv ? 1 : 0;
     // both jobs where both heads are categorical (classic control: -3.8 % on C2, same box); the normalisation alone for the MSE heads of
     // the board games, which have no softmax row (C3: -1.2 %)
     s.hwx = p->hwx >= 0 ? p->hwx : ((c.reward_support_size > 1 && c.value_support_size > 1) ? 3 : 1);
     if (fenv) s.fenv = *fenv;
     const dim3 grid((batch + TILE_E - 1) / TILE_E), block(WG_THREADS);
+    if (scripted) {
+        p->last_dispatch = "k_search<SCRIPTED=true> (scripted-network test hook)";
+        hipLaunchKernelGGL(k_search<true>, grid, block, s.lds_bytes, p->stream, s);
+    } else if (p->fast.planes && !p->force_generic && s.tree_mode == 2) {  // (k_search_fast is written for the tree_mode 2 layout)
+        FastKey k = p->fast;
+        k.fuse = fenv != nullptr;
+        // SPB: the build with the board games' self-play settings as compile-time constants (mz_search_fast.h)
+        k.spb = k.ac == 10 && s.board && s.has_bounds && s.discount == 1.0 && s.noise_mode == 2 && s.rng_mode == 1 && !s.deterministic && s.has_mask;
+        const FastBuild* b = fast_find(k);
+        p->last_dispatch = fast_name(k, fastlayout);
+        if (!b) return fail(MZ_E_STATE, "not compiled: " + p->last_dispatch);
+        void* args[] = {&s, &p->fw};
+        HIPCHK(hipLaunchKernel(b->fn, grid, dim3(kFastHW ? 2 * WG_THREADS : WG_THREADS), args, s.lds_bytes, p->stream));
+    } else {
+        p->last_dispatch = p->force_generic ? "k_search<false> (shape-generic, forced by MZ_FORCE_GENERIC=1)"
+                           : p->fast_mse && s.tree_mode == 2 ? "k_search<false> (shape-generic; MSE head outside the ten-action build)"
+                                                              : "k_search<false> (shape-generic: no tuned build for this shape)";
+        hipLaunchKernelGGL(k_search<false>, grid, block, s.lds_bytes, p->stream, s);
+    }
+    return MZ_OK;
+}
+
+// conv nets, and MLP nets whose trees do not fit LDS: HBM-resident trees, root inference -> init -> S x {select, network evaluation,
+// expand + backup} -> play
+static int launch_hbm_search(mz_planner* p, int batch, int deterministic, bool has_mask, bool injected_rng, bool scripted) {
+    const mz_config& c = p->cfg;
+    const bool mlp = !p->conv;
+    p->last_dispatch = std::string(mlp ? "k_infer" : "conv towers (mz_convnet.h: k_conv3x3 / k_res_tower / k_head)") +
+                       " around HBM trees: k_gtree_select_wave + k_gtree_backup per simulation";
+    SearchParams s = search_params(p, mlp ? p->spg : p->sp, batch, deterministic, has_mask, injected_rng);
+    s.trace_parent = scripted ? p->d_tparent : nullptr; s.trace_action = scripted ? p->d_taction : nullptr;
+    const dim3 grid((batch + TILE_E - 1) / TILE_E), block(WG_THREADS);
+    InferParams ip = p->ip;
+    ip.net = p->net; ip.B = batch; ip.in = nullptr; ip.in_ptrs = nullptr; ip.action = p->d_sim_action; ip.hidden_out = nullptr;
+    ip.out_ptrs = nullptr; ip.reward = p->d_sim_reward; ip.value = p->d_sim_value; ip.pi = p->d_pi_scratch;
+    GTreeLaunch G{};
+    G.P = s; G.regions = p->d_regions; G.hidden_size = c.hidden_dim; G.src_ptrs = p->d_srcptrs; G.dst_ptrs = p->d_dstptrs;
+    G.actions = p->d_sim_action;
+    if (scripted) {
+        G.pi0 = p->d_spi0;
+    } else if (mlp) {
+        InferParams r = ip;
+        r.in = p->d_obs; r.out_ptrs = p->d_rootptrs; r.pi = p->d_pi0;
+        hipLaunchKernelGGL(k_infer<true>, grid, block, r.lds_bytes, p->stream, r);  // root value discarded (mcts.py:356-367)
+        G.pi0 = p->d_pi0;
+    } else {
+        convnet_initial(p->stream, p->cnet, batch, p->d_obs, p->d_rootptrs, nullptr, p->d_pi0, p->d_sim_value);  // root value discarded
+        G.pi0 = p->d_pi0;
+    }
+    const bool any_n = c.num_actions > 248;  // (np_sum_f64 / _f32 are numpy's sums up to 248 actions: mz_device.h)
+    if (any_n) hipLaunchKernelGGL(k_gtree_init<true>, grid, block, 0, p->stream, G);
+    else hipLaunchKernelGGL(k_gtree_init<false>, grid, block, 0, p->stream, G);
+    for (int sim = 0; sim < c.num_simulations; sim++) {
+        G.sim = sim;
+        // one wave per env (k_gtree_select_wave); more than 256 actions: the wider build, 6 chunks of 64 lanes (the same arithmetic and tie order)
+        if (c.num_actions > 64 * MAX_CH64) hipLaunchKernelGGL(k_gtree_select_wave<MAX_CH64_WIDE>, dim3((batch + 3) / 4), block, 0, p->stream, G);
+        else hipLaunchKernelGGL(k_gtree_select_wave<MAX_CH64>, dim3((batch + 3) / 4), block, 0, p->stream, G);
+        if (scripted) {
+            G.reward = p->d_srewards + sim; G.value = p->d_svalues + sim; G.rv_stride = c.num_simulations;
+        } else if (mlp) {
+            InferParams r = ip;
+            r.in_ptrs = p->d_srcptrs; r.out_ptrs = p->d_dstptrs;
+            hipLaunchKernelGGL(k_infer<false>, grid, block, r.lds_bytes, p->stream, r);
+            G.reward = p->d_sim_reward; G.value = p->d_sim_value; G.rv_stride = 1;
+        } else {
+            convnet_recurrent(p->stream, p->cnet, batch, p->d_srcptrs, nullptr, p->d_sim_action, p->d_dstptrs, nullptr, p->d_sim_reward,
+                              p->d_sim_value, nullptr, p->d_hidden, (size_t)c.num_envs * (c.num_simulations + 1) * (size_t)c.hidden_dim);
+            G.reward = p->d_sim_reward; G.value = p->d_sim_value; G.rv_stride = 1;
+        }
+        hipLaunchKernelGGL(k_gtree_backup, grid, block, 0, p->stream, G);
+    }
+    if (any_n) hipLaunchKernelGGL(k_gtree_finish<true>, grid, block, 0, p->stream, G);
+    else hipLaunchKernelGGL(k_gtree_finish<false>, grid, block, 0, p->stream, G);
+    return MZ_OK;
+}
+
+// launches one search over inputs that are already resident in the planner's device buffers
+static int launch_search(mz_planner* p, int batch, int deterministic, bool has_mask, bool injected_rng, bool scripted, const EnvLaunch* fenv = nullptr) {
     hipEvent_t ea = nullptr, eb = nullptr;
     if (p->profiling) {
         int rc = next_kernel_events(p, &ea, &eb);
         if (rc) return rc;
         HIPCHK(hipEventRecord(ea, p->stream));
     }
-    auto fast_name = [&](int planes, int tiles, bool fuse, int ac, bool spb) {
-        char b[160];
-        snprintf(b, sizeof b, "k_search_fast<planes=%d, TR=%d, TV=%d, FUSE=%s, AC=%d, HW=%s%s> (LDS trees%s, one launch per move)", planes, tiles, tiles,
-                 fuse ? "true" : "false", ac, kFastHW ? "true" : "false", spb ? ", SPB=true" : "", fastlayout ? ", own carve-out" : "");
-        p->last_dispatch = b;
-    };
-    if (p->conv || p->hbm_tree) {
-        // HBM-resident trees: root inference -> init -> S x {select, network evaluation, expand + backup} -> play
-        const bool mlp = !p->conv;
-        p->last_dispatch = std::string(mlp ? "k_infer" : "conv towers (mz_convnet.h: k_conv3x3 / k_res_tower / k_head)") + " around HBM trees: " +
-                           (p->gtree_wave ? "k_gtree_select_wave" : "k_gtree_select") + " + k_gtree_backup per simulation";
-        InferParams ip = p->ip;
-        ip.net = p->net; ip.B = batch; ip.in = nullptr; ip.in_ptrs = nullptr; ip.action = p->d_sim_action; ip.hidden_out = nullptr;
-        ip.out_ptrs = nullptr; ip.reward = p->d_sim_reward; ip.value = p->d_sim_value; ip.pi = p->d_pi_scratch;
-        s = mlp ? p->spg : p->sp;
-        s.tree_mode = 0;
-        s.discount = c.discount; s.board = c.is_board_game; s.has_bounds = c.has_known_bounds;
-        s.kb_min = c.known_bounds_min; s.kb_max = c.known_bounds_max; s.alpha = c.root_dirichlet_alpha; s.eps = c.root_exploration_eps;
-        s.deterministic = deterministic; s.has_mask = has_mask ? 1 : 0;
-        s.noise_mode = want_noise ? (injected_rng ? 1 : 2) : 0; s.legacy_promo = c.legacy_scalar_promotion ? 1 : 0;
-        s.rng_mode = injected_rng ? 0 : 1;
-        s.max_ties = c.max_ties; s.B = batch;
-        s.obs = p->d_obs; s.mask = p->d_mask; s.cur = p->d_cur; s.opp = p->d_opp; s.temperature = p->d_temp;
-        s.noise = p->d_noise; s.u_tie = p->d_utie; s.u_final = p->d_ufinal; s.hidden = p->d_hidden; s.ftab = p->d_ftab;
-        s.out_action = p->d_action; s.out_pi = p->d_pi; s.out_root = p->d_root; s.out_visits = p->d_visits; s.err = p->d_err;
-        s.trace_parent = scripted ? p->d_tparent : nullptr; s.trace_action = scripted ? p->d_taction : nullptr;
-        s.seed = c.seed; s.move_counter = p->move_counter - 1; s.env_offset = 0; s.stamps = nullptr;
-        s.dbg_noise = p->d_dbg_noise; s.dbg_utie = p->d_dbg_utie; s.dbg_ufinal = p->d_dbg_ufinal;
-        GTreeLaunch G{};
-        G.P = s; G.regions = p->d_regions; G.hidden_size = c.hidden_dim; G.src_ptrs = p->d_srcptrs; G.dst_ptrs = p->d_dstptrs;
-        G.actions = p->d_sim_action;
-        if (scripted) {
-            G.pi0 = p->d_spi0;
-        } else if (mlp) {
-            InferParams r = ip;
-            r.in = p->d_obs; r.out_ptrs = p->d_rootptrs; r.pi = p->d_pi0;
-            hipLaunchKernelGGL(k_infer<true>, grid, block, r.lds_bytes, p->stream, r);  // root value discarded (mcts.py:356-367)
-            G.pi0 = p->d_pi0;
-        } else {
-            convnet_initial(p->stream, p->cnet, batch, p->d_obs, p->d_rootptrs, nullptr, p->d_pi0, p->d_sim_value);  // root value discarded
-            G.pi0 = p->d_pi0;
-        }
-        const bool any_n = c.num_actions > 248;  // (np_sum_f64 / _f32 are numpy's sums up to 248 actions: mz_device.h)
-        if (any_n) hipLaunchKernelGGL(k_gtree_init<true>, grid, block, 0, p->stream, G);
-        else hipLaunchKernelGGL(k_gtree_init<false>, grid, block, 0, p->stream, G);
-        for (int sim = 0; sim < c.num_simulations; sim++) {
-            G.sim = sim;
-            // one wave per env (see k_gtree_select_wave); MZ_GTREE_WAVE=0/1 overrides (A/B measurements, tests)
-            // (more than 256 actions: the wider builds, 6 chunks of 64 lanes / 24 chunks of 16 lanes; the same arithmetic and tie order)
-            const bool wide = c.num_actions > 64 * MAX_CH64;
-            if (p->gtree_wave) {
-                if (wide) hipLaunchKernelGGL(k_gtree_select_wave<MAX_CH64_WIDE>, dim3((batch + 3) / 4), block, 0, p->stream, G);
-                else hipLaunchKernelGGL(k_gtree_select_wave<MAX_CH64>, dim3((batch + 3) / 4), block, 0, p->stream, G);
-            } else {
-                if (wide) hipLaunchKernelGGL(k_gtree_select<24>, grid, block, 0, p->stream, G);
-                else hipLaunchKernelGGL(k_gtree_select<16>, grid, block, 0, p->stream, G);
-            }
-            if (scripted) {
-                G.reward = p->d_srewards + sim; G.value = p->d_svalues + sim; G.rv_stride = c.num_simulations;
-            } else if (mlp) {
-                InferParams r = ip;
-                r.in_ptrs = p->d_srcptrs; r.out_ptrs = p->d_dstptrs;
-                hipLaunchKernelGGL(k_infer<false>, grid, block, r.lds_bytes, p->stream, r);
-                G.reward = p->d_sim_reward; G.value = p->d_sim_value; G.rv_stride = 1;
-            } else {
-                convnet_recurrent(p->stream, p->cnet, batch, p->d_srcptrs, nullptr, p->d_sim_action, p->d_dstptrs, nullptr, p->d_sim_reward,
-                                  p->d_sim_value, nullptr, p->d_hidden, (size_t)c.num_envs * (c.num_simulations + 1) * (size_t)c.hidden_dim);
-                G.reward = p->d_sim_reward; G.value = p->d_sim_value; G.rv_stride = 1;
-            }
-            hipLaunchKernelGGL(k_gtree_backup, grid, block, 0, p->stream, G);
-        }
-        if (any_n) hipLaunchKernelGGL(k_gtree_finish<true>, grid, block, 0, p->stream, G);
-        else hipLaunchKernelGGL(k_gtree_finish<false>, grid, block, 0, p->stream, G);
-    } else
-    if (scripted) {
-        p->last_dispatch = "k_search<SCRIPTED=true> (scripted-network test hook)";
-        hipLaunchKernelGGL(k_search<true>, grid, block, s.lds_bytes, p->stream, s);
-    } else if (p->fast_planes && !p->force_generic && s.tree_mode == 2) {  // (k_search_fast is written for the tree_mode 2 layout)
-        const int two = p->net.L[L_VAL1].n_tiles == 2;
-#define MZ_FAST4(PL, T, F, W) fast_name(PL, T, F, W, false); hipLaunchKernelGGL((k_search_fast<PL, T, T, F, W, kFastHW>), grid, dim3(kFastHW ? 2 * WG_THREADS : WG_THREADS), s.lds_bytes, p->stream, s, p->fw)
-#define MZ_FAST(PL, T) do { if (fenv) { if (two_act) { MZ_FAST4(PL, T, true, 2); } else { MZ_FAST4(PL, T, true, 0); } } \
-                            else { if (two_act) { MZ_FAST4(PL, T, false, 2); } else { MZ_FAST4(PL, T, false, 0); } } } while (0)
-        // compile-time specialisation (mz_tree2.h, AM): two actions, single player, categorical reward and value heads
-        const bool two_act = fast_two_act(c);  // (also fixes the depth of the weight ring the stream is packed for: load_weights)
-        // four actions, categorical heads, the 512-plane net (mz_tree2.h, ACT: the backup's refresh unrolled, the action count a constant)
-        const bool four_act = p->fast_ac4 && c.num_actions == 4 && c.reward_support_size > 1 && c.value_support_size > 1 && p->fast_planes == 512 && two;
-        if (fast_ac10(p)) {  // (TicTacToe: ten actions)
-            // SPB: the build with the board games' self-play settings as compile-time constants (mz_search_fast.h)
-            const bool spb = s.board && s.has_bounds && s.discount == 1.0 && s.noise_mode == 2 && s.rng_mode == 1 && !s.deterministic && s.has_mask;
-            const dim3 fblock(kFastHW ? 2 * WG_THREADS : WG_THREADS);
-            if (spb) {
-                fast_name(256, 1, fenv != nullptr, 10, true);
-                if (fenv) hipLaunchKernelGGL((k_search_fast<256, 1, 1, true, 10, kFastHW, true>), grid, fblock, s.lds_bytes, p->stream, s, p->fw);
-                else hipLaunchKernelGGL((k_search_fast<256, 1, 1, false, 10, kFastHW, true>), grid, fblock, s.lds_bytes, p->stream, s, p->fw);
-            } else if (fenv) { MZ_FAST4(256, 1, true, 10); } else { MZ_FAST4(256, 1, false, 10); }
-        } else
-        if (four_act) { if (fenv) { MZ_FAST4(512, 2, true, 4); } else { MZ_FAST4(512, 2, false, 4); } }
-        else if (c.value_support_size == 1 || c.reward_support_size == 1) {
-            // an MSE head's one-neuron layer runs on the vector ALUs in its own summation order (mz_mlp.h, scalar_head_tile): of the
-            // tuned kernel's builds only the ten-action one has that form
-            p->last_dispatch = "k_search<false> (shape-generic; MSE head outside the ten-action build)";
-            hipLaunchKernelGGL(k_search<false>, grid, block, s.lds_bytes, p->stream, s);
-        } else
-#ifdef MZ_DEV_SHAPES
-        if (p->fast_planes == 512 && two) MZ_FAST(512, 2);
-        else if (p->fast_planes == 256 && !two) MZ_FAST(256, 1);
-        else hipLaunchKernelGGL(k_search<false>, grid, block, s.lds_bytes, p->stream, s);
-#else
-        if (p->fast_planes == 512) { if (two) MZ_FAST(512, 2); else MZ_FAST(512, 1); }
-        else { if (two) MZ_FAST(256, 2); else MZ_FAST(256, 1); }
-#endif
-#undef MZ_FAST4
-#undef MZ_FAST
-    }
-    else {
-        p->last_dispatch = p->force_generic ? "k_search<false> (shape-generic, forced by MZ_FORCE_GENERIC=1)" : "k_search<false> (shape-generic: no tuned build for this shape)";
-        hipLaunchKernelGGL(k_search<false>, grid, block, s.lds_bytes, p->stream, s);
-    }
+    const int rc = p->conv || p->hbm_tree ? launch_hbm_search(p, batch, deterministic, has_mask, injected_rng, scripted)
+                                          : launch_lds_search(p, batch, deterministic, has_mask, injected_rng, scripted, fenv);
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     if (p->profiling) HIPCHK(hipEventRecord(eb, p->stream));
     return MZ_OK;
@@ -1006,6 +979,43 @@ extern "C" int mz_planner_search_scripted(mz_planner* p, int32_t batch, const fl
 // ---------------------------------------------------------------------------------------------------------
 // device-resident self-play
 // ---------------------------------------------------------------------------------------------------------
+// Starts an empty record ring.  Its length: 64 moves (16 where that would pass 4 GB of observations) or, with a replay attached, every
+// env's open trajectory -- a whole board game, or the acc + unroll + td window (pipeline.py:118-121), but never longer than an episode can
+// get when its step limit is known (max_steps > 0): the classic configs set acc_seq_length = 9999 ("never flush mid-episode",
+// config.py:198), and 10 014 slots x 4096 envs of CartPole records would be ~5 GB.
+static void ring_start(mz_planner* p, int max_steps) {
+    const mz_config& c = p->cfg;
+    p->ring_len = (size_t)c.num_envs * obs_dim(c) * sizeof(float) * 64 > ((size_t)4 << 30) ? 16 : 64;
+    if (p->has_replay) {
+        const int window = p->replay.acc + p->replay.K + p->replay.td;
+        int need = c.is_board_game ? c.num_actions + 1 : window;
+        if (max_steps > 0) {
+            const int capped = max_steps + (c.is_board_game ? 1 : p->replay.K + p->replay.td);
+            need = c.is_board_game ? capped : (window < capped ? window : capped);
+        }
+        if (need > p->ring_len) p->ring_len = (need + 7) & ~7;
+    }
+    p->selfplay_moves = 0;
+    p->ring_pos = 0;
+    p->ring_count = 0;
+}
+
+// after a move's records are in the ring: the attached replay's items (k_epi_scan -> k_epilogue -> k_epi_publish), then the next slot
+static int ring_finish_move(mz_planner* p) {
+    if (p->has_replay) {
+        EpiLaunch E{};
+        E.env = p->env; E.ring = p->replay; E.B = p->cfg.num_envs; E.move_abs = p->selfplay_moves;
+        hipLaunchKernelGGL(k_epi_scan, dim3(1), dim3(1024), 0, p->stream, E);
+        hipLaunchKernelGGL(k_epilogue, dim3(p->cfg.num_envs), dim3(64), (size_t)p->ring_len * sizeof(double), p->stream, E);
+        hipLaunchKernelGGL(k_epi_publish, dim3(1), dim3(1), 0, p->stream, p->replay);
+    }
+    HIPCHK(hipGetLastError());
+    p->selfplay_moves++;
+    p->ring_pos = (p->ring_pos + 1) % p->ring_len;
+    if (p->ring_count < p->ring_len) p->ring_count++;
+    return MZ_OK;
+}
+
 extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* h_init_state) {
     if (!p) return fail(MZ_E_INVALID, "null planner");
     HIPCHK(hipSetDevice(p->device));
@@ -1026,19 +1036,9 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         return fail(MZ_E_INVALID, "unknown env kind");
     }
     p->env_kind = env_kind;
-    p->ring_len = (size_t)c.num_envs * obs_dim(c) * sizeof(float) * 64 > ((size_t)4 << 30) ? 16 : 64;  // record ring: at most a few GB
-    if (p->has_replay) {
-        // the record ring is every env's open trajectory: a whole board game, or the acc + unroll + td window (pipeline.py:118-121)
-        // -- but never longer than an episode can get: the classic configs set acc_seq_length = 9999 ("never flush mid-episode", config.py:198), and
-        // gym's TimeLimit ends CartPole after 500 steps (the synthetic frames env after 1000): 10 014 slots x 4096 envs of records would be ~5 GB
-        const int limit = env_kind == MZ_ENV_CARTPOLE ? 500 : (env_kind == MZ_ENV_SYNTHETIC ? 1000 : (1 << 30) - 64);
-        const int window = p->replay.acc + p->replay.K + p->replay.td, capped = limit + p->replay.K + p->replay.td;
-        const int need = c.is_board_game ? c.num_actions + 1 : (window < capped ? window : capped);
-        if (need > p->ring_len) p->ring_len = (need + 7) & ~7;
-    }
-    p->selfplay_moves = 0;
-    p->ring_pos = 0;
-    p->ring_count = 0;
+    // gym's TimeLimit ends CartPole after 500 steps, the synthetic frames env after 1000; a board game's ring holds the whole game
+    const int limit = env_kind == MZ_ENV_CARTPOLE ? 500 : (env_kind == MZ_ENV_SYNTHETIC ? 1000 : (1 << 30) - 64);
+    ring_start(p, c.is_board_game ? 0 : limit);
     hipError_t e = env_alloc(p->env, env_kind, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, board_n, num_to_win);
     if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
     if (h_init_state) HIPCHK(hipMemcpyAsync(p->env.init_state, h_init_state, (size_t)c.num_envs * 4 * sizeof(double), hipMemcpyHostToDevice, p->stream));
@@ -1060,43 +1060,29 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
     if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
     const mz_config& c = p->cfg;
-    auto epilogue = [&]() {
-        if (p->has_replay) {
-            EpiLaunch E{};
-            E.env = p->env; E.ring = p->replay; E.B = c.num_envs; E.move_abs = p->selfplay_moves;
-            hipLaunchKernelGGL(k_epi_scan, dim3(1), dim3(1024), 0, p->stream, E);
-            hipLaunchKernelGGL(k_epilogue, dim3(c.num_envs), dim3(64), (size_t)p->ring_len * sizeof(double), p->stream, E);
-            hipLaunchKernelGGL(k_epi_publish, dim3(1), dim3(1), 0, p->stream, p->replay);
-        }
-        p->selfplay_moves++;
-    };
     for (int m = 0; m < n_moves; m++) {
         EnvLaunch L{};
         L.env = p->env; L.B = c.num_envs; L.seed = c.seed; L.temperature = temperature; L.move_counter = p->move_counter;
         L.obs = p->d_obs; L.mask = p->d_mask; L.cur = p->d_cur; L.opp = p->d_opp; L.temp_out = p->d_temp;
         L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root; L.slot = p->ring_pos; L.sims = c.num_simulations;
-        if (!p->conv && !p->hbm_tree && p->fuse_env && p->env_kind != MZ_ENV_SYNTHETIC) {  // (synthetic frames are redrawn by k_env_synth_obs below)
-            // MLP nets: the whole move -- temperature / record, search, env.step, auto-reset -- is ONE kernel launch
+        if (!p->conv && !p->hbm_tree && p->env_kind != MZ_ENV_SYNTHETIC) {  // (synthetic frames are redrawn by k_env_synth_obs below)
+            // MLP nets with LDS trees: the whole move -- temperature / record, search, env.step, auto-reset -- is ONE kernel launch
+            // (C2: 727.7 us per move against 734.6 us for the four launches below, same box, same build)
             int rc = launch_search(p, c.num_envs, 0, true, false, false, &L);
             if (rc) return rc;
-            epilogue();
-            p->ring_pos = (p->ring_pos + 1) % p->ring_len;
-            if (p->ring_count < p->ring_len) p->ring_count++;
-            continue;
+        } else {
+            // temperatures for this move, then the search, then env.step + record + auto-reset
+            hipLaunchKernelGGL(k_env_pre, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, L);
+            HIPCHK(hipMemcpyAsync(p->env.r_obs + (size_t)p->ring_pos * c.num_envs * obs_dim(c), p->d_obs, (size_t)c.num_envs * obs_dim(c) * sizeof(float),
+                                  hipMemcpyDeviceToDevice, p->stream));
+            int rc = launch_search(p, c.num_envs, 0, true, false, false);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_env_step, dim3((c.num_envs + 15) / 16), dim3(256), 0, p->stream, L);
+            if (p->env_kind == MZ_ENV_SYNTHETIC)
+                hipLaunchKernelGGL(k_env_synth_obs, dim3(((size_t)c.num_envs * ((obs_dim(c) + 3) / 4) + 255) / 256), dim3(256), 0, p->stream, L);
         }
-        // temperatures for this move, then the search, then env.step + record + auto-reset
-        hipLaunchKernelGGL(k_env_pre, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, L);
-        HIPCHK(hipMemcpyAsync(p->env.r_obs + (size_t)p->ring_pos * c.num_envs * obs_dim(c), p->d_obs, (size_t)c.num_envs * obs_dim(c) * sizeof(float),
-                              hipMemcpyDeviceToDevice, p->stream));
-        int rc = launch_search(p, c.num_envs, 0, true, false, false);
+        int rc = ring_finish_move(p);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_env_step, dim3((c.num_envs + 15) / 16), dim3(256), 0, p->stream, L);
-        if (p->env_kind == MZ_ENV_SYNTHETIC)
-            hipLaunchKernelGGL(k_env_synth_obs, dim3(((size_t)c.num_envs * ((obs_dim(c) + 3) / 4) + 255) / 256), dim3(256), 0, p->stream, L);
-        epilogue();
-        HIPCHK(hipGetLastError());
-        p->ring_pos = (p->ring_pos + 1) % p->ring_len;
-        if (p->ring_count < p->ring_len) p->ring_count++;
     }
     return MZ_OK;
 }
@@ -1146,19 +1132,7 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
     ext_free(p);
     p->env_kind = MZ_ENV_EXTERNAL;
     p->ext_pending = p->ext_broken = false;
-    p->ring_len = (size_t)c.num_envs * obs_dim(c) * sizeof(float) * 64 > ((size_t)4 << 30) ? 16 : 64;  // as mz_selfplay_reset
-    if (p->has_replay) {  // the record ring holds every env's open trajectory (mz_selfplay_reset), bounded by the episode length when known
-        const int window = p->replay.acc + p->replay.K + p->replay.td;
-        int need = c.is_board_game ? c.num_actions + 1 : window;
-        if (x->max_episode_steps > 0) {
-            const int capped = x->max_episode_steps + (c.is_board_game ? 1 : p->replay.K + p->replay.td);
-            need = c.is_board_game ? capped : (window < capped ? window : capped);
-        }
-        if (need > p->ring_len) p->ring_len = (need + 7) & ~7;
-    }
-    p->selfplay_moves = 0;
-    p->ring_pos = 0;
-    p->ring_count = 0;
+    ring_start(p, x->max_episode_steps);
     hipError_t e = env_alloc(p->env, ENV_EXTERNAL, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, 3, 3);
     if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
     ExtEnv& X = p->ext;
@@ -1258,17 +1232,8 @@ extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward,
             return fail(MZ_E_INVALID, "env " + std::to_string(*p->h_ext_err) + ": open trajectory of more than " + std::to_string(p->ring_len) +
                                           " moves outgrew the record ring (raise mz_external_env.max_episode_steps); no items written, reset next");
         }
-        EpiLaunch E{};
-        E.env = p->env; E.ring = p->replay; E.B = c.num_envs; E.move_abs = p->selfplay_moves;
-        hipLaunchKernelGGL(k_epi_scan, dim3(1), dim3(1024), 0, p->stream, E);
-        hipLaunchKernelGGL(k_epilogue, dim3(c.num_envs), dim3(64), (size_t)p->ring_len * sizeof(double), p->stream, E);
-        hipLaunchKernelGGL(k_epi_publish, dim3(1), dim3(1), 0, p->stream, p->replay);
-        HIPCHK(hipGetLastError());
     }
-    p->selfplay_moves++;
-    p->ring_pos = (p->ring_pos + 1) % p->ring_len;
-    if (p->ring_count < p->ring_len) p->ring_count++;
-    return MZ_OK;
+    return ring_finish_move(p);
 }
 
 extern "C" int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ring) {
