@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from board19_cases import BOARD_CASES, board_case
+from fullsize_cases import BOARD_KW, FULL19  # C5's net (128 planes x 8 blocks) on a 19 x 19 board, and its search keywords
 from helpers import build_conv, load_golden
 from test_oracle_nets import _oracle_net
 
@@ -19,8 +20,6 @@ pytestmark = pytest.mark.gpu
 
 G = load_golden('board19_cases.npz')
 IDS = [c[0] for c in BOARD_CASES]
-FULL19 = ('c5_19', 'board', (9, 19, 19), 362, 8, 128, 1, 1, 41)  # C5's net (128 planes x 8 blocks) on a 19 x 19 board
-BOARD_KW = dict(discount=1.0, is_board_game=True, known_bounds=(-1.0, 1.0), root_dirichlet_alpha=0.03, root_exploration_eps=0.25)
 
 
 def _planner(net, num_envs, **search):

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from fullsize_cases import FULL
 from helpers import CONV_CASES, build_conv, conv_case, load_golden
 from test_oracle_nets import _oracle_net
 
@@ -214,12 +215,7 @@ def test_conv_network_api_runs_on_planner(oracle):
 
 
 # ----------------------------------------------------------------------------------------------- BASELINE sizes
-FULL = {
-    # BASELINE.json configs[3] / configs[4]: network, envs per GPU, sims per move, search kwargs
-    'c4': (('c4', 'atari', (8, 96, 96), 6, 8, 128, 61, 61, 41), 512, 50, dict(discount=0.997, root_dirichlet_alpha=0.25)),
-    'c5': (('c5', 'board', (9, 15, 15), 226, 8, 128, 1, 1, 42), 256, 200,
-           dict(discount=1.0, is_board_game=True, known_bounds=(-1.0, 1.0), root_dirichlet_alpha=0.03)),
-}
+# BASELINE.json configs[3] / configs[4]: network, envs per GPU, sims per move, search kwargs -- tests/fullsize_cases.py
 
 
 @pytest.mark.parametrize('name', ['c4', 'c5'])
