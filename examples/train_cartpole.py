@@ -43,6 +43,8 @@ def main():
                     help='let self-play (planner stream) and updates (learner stream) overlap: faster, but how many items the replay holds when a '
                          'batch is drawn then depends on timing -- without it every draw happens after the moves before it have been committed '
                          '(event order), and a seed gives ONE learning curve')
+    ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
+                    help='also play N evaluation episodes as one lock-step batch on the device env (pipeline.play_match); 0: off')
     args = ap.parse_args()
     args.eager_learner = args.learner == 'eager'
 
@@ -147,6 +149,12 @@ def main():
     lengths = evaluate()
     evals.append(dict(train_steps=steps, eval_episode_lengths=lengths))
     print(json.dumps(dict(eval_episode_lengths=lengths)), flush=True)
+    if args.arena_eval > 0:
+        from muzero_amd.pipeline import play_match
+
+        m = play_match(cfg, net, None, dev, 'CartPole-v1', args.arena_eval)
+        evals[-1]['arena_episode_lengths'] = [int(n) for n in m.length]
+        print(json.dumps(dict(arena_episode_lengths=evals[-1]['arena_episode_lengths'])), flush=True)
     if args.out:
         json.dump(dict(args=vars(args), log=log, eval_episode_lengths=lengths, evals=evals), open(args.out, 'w'), indent=1)
 

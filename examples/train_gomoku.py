@@ -61,6 +61,8 @@ def main():
     ap.add_argument('--graphed', action='store_true', help='the PyTorch-ROCm update as one HIP graph (learner.GraphedTrainStep)')
     ap.add_argument('--autograd', action='store_true', help='the PyTorch-ROCm update, eager (learner.train_step)')
     ap.add_argument('--out', default='')
+    ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
+                    help='also play N games (even) against the random opponent as one lock-step batch on the device (pipeline.play_match); 0: off')
     args = ap.parse_args()
 
     from muzero_amd import learner
@@ -108,7 +110,15 @@ def main():
     def evaluate(player):
         return play_vs_random(net, dev, cfg, player, args.eval_games, rs, N)
 
-    log = [dict(train_steps=0, black=evaluate(1), white=evaluate(2))]
+    def arena():  # {} unless --arena-eval: the records keep their fields
+        if args.arena_eval <= 0:
+            return {}
+        from muzero_amd.pipeline import play_match
+
+        m = play_match(cfg, net, 'random', dev, 'Gomoku', args.arena_eval)
+        return dict(arena=dict(games=m.num_games, win=m.wins, draw=m.draws, loss=m.losses, **m.by_colour()))
+
+    log = [dict(train_steps=0, black=evaluate(1), white=evaluate(2), **arena())]
     print(json.dumps(log[0]), flush=True)
     steps, t0 = 0, time.time()
     while steps < args.train_steps:
@@ -129,7 +139,7 @@ def main():
                 if steps % args.report_every == 0:
                     net.eval()
                     rec = dict(train_steps=steps, loss=float(loss), seconds=round(time.time() - t0, 1), env_steps=p.selfplay_counters()['env_steps'],
-                               black=evaluate(1), white=evaluate(2), learner='hip')
+                               black=evaluate(1), white=evaluate(2), learner='hip', **arena())
                     log.append(rec)
                     print(json.dumps(rec), flush=True)
                 continue
@@ -144,7 +154,7 @@ def main():
             if steps % args.report_every == 0:
                 net.eval()
                 rec = dict(train_steps=steps, loss=float(loss), seconds=round(time.time() - t0, 1), env_steps=p.selfplay_counters()['env_steps'],
-                           black=evaluate(1), white=evaluate(2))
+                           black=evaluate(1), white=evaluate(2), **arena())
                 net.train()
                 log.append(rec)
                 print(json.dumps(rec), flush=True)

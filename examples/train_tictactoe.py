@@ -50,6 +50,8 @@ def main():
     ap.add_argument('--host-assembly', action='store_true',
                     help="round 1's path: (Transition, priority) items assembled on the host and the PyTorch learner step; default: device epilogue "
                          'into the HBM replay + the HIP learner kernels (hip_learner.HipLearner), in event order (a seed gives one run)')
+    ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
+                    help='also play N games (even) against the random opponent as one lock-step batch on the device (pipeline.play_match); 0: off')
     args = ap.parse_args()
 
     from muzero_amd import learner
@@ -80,7 +82,15 @@ def main():
     asm = EpisodeAssembler(cfg, args.envs, (9, 3, 3))
     rs = np.random.RandomState(args.seed + 7)
 
-    log = [dict(train_steps=0, black=play_vs_random(net, dev, cfg, 1, args.eval_games, rs), white=play_vs_random(net, dev, cfg, 2, args.eval_games, rs))]
+    def arena():  # {} unless --arena-eval: the records keep their fields
+        if args.arena_eval <= 0:
+            return {}
+        from muzero_amd.pipeline import play_match
+
+        m = play_match(cfg, net, 'random', dev, 'TicTacToe', args.arena_eval)
+        return dict(arena=dict(games=m.num_games, win=m.wins, draw=m.draws, loss=m.losses, **m.by_colour()))
+
+    log = [dict(train_steps=0, black=play_vs_random(net, dev, cfg, 1, args.eval_games, rs), white=play_vs_random(net, dev, cfg, 2, args.eval_games, rs), **arena())]
     print(json.dumps(log[0]), flush=True)
     steps, t0 = 0, time.time()
     while steps < args.train_steps:
@@ -105,7 +115,7 @@ def main():
             if steps % args.report_every == 0:
                 net.eval()
                 rec = dict(train_steps=steps, loss=float(loss), seconds=round(time.time() - t0, 1), env_steps=p.selfplay_counters()['env_steps'],
-                           black=play_vs_random(net, dev, cfg, 1, args.eval_games, rs), white=play_vs_random(net, dev, cfg, 2, args.eval_games, rs))
+                           black=play_vs_random(net, dev, cfg, 1, args.eval_games, rs), white=play_vs_random(net, dev, cfg, 2, args.eval_games, rs), **arena())
                 net.train()
                 log.append(rec)
                 print(json.dumps(rec), flush=True)

@@ -222,6 +222,55 @@ int mz_selfplay_external_act(mz_planner* p, const void* h_frames, const uint8_t*
  * will hand env e's reset frame to the next act call. */
 int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done);
 
+/* Arena: the evaluators' game loops (pipeline.py:289-397 board games, pipeline.py:400-488 one-player envs) for num_envs games in
+ * lock-step on the device.  Every searched move is uct_search(deterministic = True) on the planner's search kernels: no root noise, the
+ * most-visited child, tie draws consumed as mz_planner_search consumes them (mz_debug_capture_rng reads them back per handle).  The
+ * recorded policy is the visit distribution (temperature 1); the move does not depend on the temperature.  Nothing resets: a finished env
+ * is FROZEN -- board, winner, length and return no longer change, its record of the last ply stays as it was -- and is still searched
+ * (its unchanged observation, an all-legal mask) with the output discarded; frozen envs are not compacted away, so a ply costs the same
+ * until the last game ends.
+ *   Sides: the CHALLENGER `p` owns the env state.  Opponent kinds: MZ_ARENA_NONE (one-player envs: p plays every move), MZ_ARENA_RANDOM
+ *   (uniform over the legal moves), MZ_ARENA_PLANNER (a second planner q on p's device whose mz_config equals p's apart from the seed,
+ *   weights committed; anything else: MZ_E_INVALID / MZ_E_STATE).  q is BORROWED until p's next reset or destroy: the arena launches
+ *   searches on q's stream and buffers; using or destroying q meanwhile is the caller's error.
+ *   Colours: two-player envs need an even num_envs; the challenger plays black in envs [0, B/2) and white in [B/2, B); env i and
+ *   env i + B/2 are a pair.  All live games are at the same ply, so each side searches one contiguous run of B/2 roots per ply.
+ *   Openings: the first opening_plies plies (0 allowed) are uniform-random legal moves drawn once per PAIR (per env for one-player
+ *   envs) from a Philox stream of their own: both games of a pair start from the same position with colours swapped.
+ *   Random moves (openings, MZ_ARENA_RANDOM): legal[floor(u * n_legal)], u one Philox double per (pair or env, ply), recorded.
+ *   Game length is capped by the env: 500 steps (CartPole), the point count (boards).
+ * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC, MZ_ENV_EXTERNAL: MZ_E_INVALID); h_init_state as
+ * mz_selfplay_reset (CartPole only).  Arena and self-play exclude each other on a handle: mz_selfplay_step during an arena is MZ_E_STATE,
+ * mz_arena_step without mz_arena_reset (e.g. during self-play) is MZ_E_STATE; each mode's reset enters it. */
+#define MZ_ARENA_NONE 0
+#define MZ_ARENA_RANDOM 1
+#define MZ_ARENA_PLANNER 2
+#define MZ_ARENA_SIDE_CHALLENGER 0 /* who chose a ply's move (mz_arena_read_ply h_side) */
+#define MZ_ARENA_SIDE_OPPONENT 1
+#define MZ_ARENA_SIDE_RANDOM 2
+#define MZ_ARENA_SIDE_OPENING 3
+#define MZ_ARENA_UNFINISHED 0 /* mz_arena_result h_winner */
+#define MZ_ARENA_WIN_CHALLENGER 1
+#define MZ_ARENA_WIN_OPPONENT 2
+#define MZ_ARENA_DRAW 3 /* also: a finished one-player episode (it has no winner; its score is h_ret) */
+int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_kind, mz_planner* q_or_null, int32_t opening_plies,
+                   const double* h_init_state_or_null);
+/* Issues n_plies plies -- per ply: roots, at most one search per side (B/2 roots each; B with MZ_ARENA_NONE), env.step -- with no host
+ * synchronisation inside; the two planners' streams are ordered with events.  Replaces the `while not done` loops of pipeline.py:289-397
+ * (:370-377) and pipeline.py:400-488 (:463-473). */
+int mz_arena_step(mz_planner* p, int32_t n_plies);
+/* The last ply, per env; any pointer may be NULL.  h_obs float32 [B, obs], h_mask uint8 [B, A], h_player int32 [B] (side to move, 1 / 2):
+ * the root before the move.  h_side int32 [B] (MZ_ARENA_SIDE_*), h_pi float64 [B, A] and h_root float64 [B] (zeros for a random move),
+ * h_action int32 [B], h_u float64 [B] (the uniform of a random move, else 0), h_live uint8 [B]: 1 where the env was live when the ply
+ * began -- elsewhere the other fields are those of the env's last ply.  What the evaluators read per move (pipeline.py:370-377). */
+int mz_arena_read_ply(mz_planner* p, float* h_obs, uint8_t* h_mask, int32_t* h_player, int32_t* h_side, double* h_pi, double* h_root,
+                      int32_t* h_action, double* h_u, uint8_t* h_live);
+/* The tally (pipeline.py:378-383 winner, :474-476 returns and steps); any pointer may be NULL.  h_winner int32 [B] (MZ_ARENA_*), h_length
+ * int32 [B] plies played, h_ret float64 [B]: the undiscounted return (one-player envs), +1 / -1 / 0 from the challenger's side (boards);
+ * totals: [0] challenger wins, [1] opponent wins, [2] draws (finished episodes of one-player envs), [3] sum of finished lengths;
+ * n_live: games still running. */
+int mz_arena_result(mz_planner* p, int32_t* h_winner, int32_t* h_length, double* h_ret, int64_t totals[4], int32_t* n_live);
+
 /* Measurement hooks (bench.py): HIP-event timing on the planner's own stream.
  * mz_profile_begin/end bracket a region; mz_profile_end returns elapsed milliseconds and the number of
  * search-kernel launches inside it (the dominant kernel of the path). */

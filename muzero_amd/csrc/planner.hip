@@ -14,6 +14,7 @@
 
 #include "../../include/mzplanner.h"
 #include "mz_env.h"
+#include "mz_arena.h"
 #include "mz_extenv.h"
 #include "mz_search.h"
 #include "mz_search_fast.h"
@@ -177,6 +178,13 @@ struct mz_planner {
     unsigned char *h_ext_mask = nullptr, *h_ext_done = nullptr;
     int *h_ext_cur = nullptr, *h_ext_opp = nullptr, *h_ext_action = nullptr, *h_ext_err = nullptr;
     float* h_ext_reward = nullptr;
+
+    // arena (mz_arena.h): evaluation games in lock-step on this handle's env state
+    ArenaState arena{};
+    bool arena_open = false;
+    int arena_ply = 0;
+    mz_planner* arena_q = nullptr;  // the borrowed opponent planner (MZ_ARENA_PLANNER)
+    hipEvent_t ev_arena_pre = nullptr, ev_arena_q = nullptr;  // order the two planners' streams within a ply
 
     // profiling
     bool profiling = false;
@@ -533,6 +541,9 @@ extern "C" int mz_planner_destroy(mz_planner* p) {
         if (b) (void)hipFree(b);
     convnet_free(p->cnet);
     env_free(p->env);
+    arena_free(p->arena);
+    if (p->ev_arena_pre) (void)hipEventDestroy(p->ev_arena_pre);
+    if (p->ev_arena_q) (void)hipEventDestroy(p->ev_arena_q);
     ext_free(p);
     for (auto& pr : p->kev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (p->ev_begin) (void)hipEventDestroy(p->ev_begin);
@@ -1036,6 +1047,7 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         return fail(MZ_E_INVALID, "unknown env kind");
     }
     p->env_kind = env_kind;
+    p->arena_open = false;
     // gym's TimeLimit ends CartPole after 500 steps, the synthetic frames env after 1000; a board game's ring holds the whole game
     const int limit = env_kind == MZ_ENV_CARTPOLE ? 500 : (env_kind == MZ_ENV_SYNTHETIC ? 1000 : (1 << 30) - 64);
     ring_start(p, c.is_board_game ? 0 : limit);
@@ -1055,6 +1067,7 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
 
 extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_moves) {
     if (!p || n_moves < 1) return fail(MZ_E_INVALID, "bad argument to mz_selfplay_step");
+    if (p->arena_open) return fail(MZ_E_STATE, "mz_selfplay_step during an arena: call mz_selfplay_reset first");
     if (p->env_kind == MZ_ENV_NONE) return fail(MZ_E_STATE, "call mz_selfplay_reset first");
     if (p->env_kind == MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "mz_selfplay_step on host-stepped envs: use mz_selfplay_external_act / _commit");
     if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
@@ -1130,6 +1143,7 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
                                       std::to_string(obs_dim(c)));
     if (S == 0 && x->frame_u8) return fail(MZ_E_INVALID, "mz_external_env: frame_u8 needs stack_history > 0 (whole observations are float32)");
     ext_free(p);
+    p->arena_open = false;
     p->env_kind = MZ_ENV_EXTERNAL;
     p->ext_pending = p->ext_broken = false;
     ring_start(p, x->max_episode_steps);
@@ -1276,6 +1290,7 @@ extern "C" int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ri
     if (!p->d_epi_off) HIPCHK(hipMalloc(&p->d_epi_off, (size_t)c.num_envs * sizeof(int)));
     R.off = p->d_epi_off;
     p->has_replay = true;
+    p->arena_open = false;
     p->env_kind = MZ_ENV_NONE;  // the record ring must be re-sized: mz_selfplay_reset next
     return MZ_OK;
 }
@@ -1307,12 +1322,213 @@ extern "C" int mz_selfplay_read(mz_planner* p, int32_t n_moves, float* h_obs, in
 
 extern "C" int mz_selfplay_counters(mz_planner* p, int64_t out[4]) {
     if (!p || !out) return fail(MZ_E_INVALID, "null argument");
-    if (p->env_kind == MZ_ENV_NONE) return fail(MZ_E_STATE, "call mz_selfplay_reset first");
+    if (p->env_kind == MZ_ENV_NONE || p->arena_open) return fail(MZ_E_STATE, "call mz_selfplay_reset first");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipStreamSynchronize(p->stream));
     unsigned long long c[4];
     HIPCHK(hipMemcpy(c, p->env.counters, sizeof(c), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) out[i] = (int64_t)c[i];
+    return MZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// arena: evaluation matches in lock-step (mz_arena.h)
+// ---------------------------------------------------------------------------------------------------------
+static bool arena_same_config(const mz_config& a, const mz_config& b) {
+    mz_config x = a, y = b;
+    x.seed = y.seed = 0;
+    return x.net_kind == y.net_kind && x.obs_c == y.obs_c && x.obs_h == y.obs_h && x.obs_w == y.obs_w && x.num_actions == y.num_actions &&
+           x.num_planes == y.num_planes && x.hidden_dim == y.hidden_dim && x.num_res_blocks == y.num_res_blocks &&
+           x.value_support_size == y.value_support_size && x.reward_support_size == y.reward_support_size &&
+           x.num_simulations == y.num_simulations && x.discount == y.discount && x.pb_c_base == y.pb_c_base && x.pb_c_init == y.pb_c_init &&
+           x.is_board_game == y.is_board_game && x.has_known_bounds == y.has_known_bounds && x.known_bounds_min == y.known_bounds_min &&
+           x.known_bounds_max == y.known_bounds_max && x.root_dirichlet_alpha == y.root_dirichlet_alpha &&
+           x.root_exploration_eps == y.root_exploration_eps && x.num_envs == y.num_envs && x.max_ties == y.max_ties &&
+           x.legacy_scalar_promotion == y.legacy_scalar_promotion;
+}
+
+static ArenaLaunch arena_launch(mz_planner* p) {
+    const mz_config& c = p->cfg;
+    ArenaLaunch R{};
+    R.L.env = p->env; R.L.B = c.num_envs; R.L.seed = c.seed; R.L.sims = c.num_simulations;
+    R.L.obs = p->arena.obs; R.L.mask = p->arena.mask; R.L.cur = p->arena.cur; R.L.opp = p->arena.opp;
+    R.a = p->arena;
+    R.ply = p->arena_ply;
+    return R;
+}
+
+// a searched run: staged into, and read back from, the root buffers of the planner `s` that searches it
+static void arena_seg_searched(ArenaSeg& g, mz_planner* s) {
+    g.obs = s->d_obs; g.mask = s->d_mask; g.cur = s->d_cur; g.opp = s->d_opp; g.temp = s->d_temp;
+    g.action = s->d_action; g.pi = s->d_pi; g.root = s->d_root;
+}
+
+extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_kind, mz_planner* q, int32_t opening_plies, const double* h_init_state) {
+    if (!p) return fail(MZ_E_INVALID, "null planner");
+    const mz_config& c = p->cfg;
+    int board_n = 3, num_to_win = 3;
+    if (env_kind == MZ_ENV_CARTPOLE) {
+        if (c.num_actions != 2 || obs_dim(c) != 20) return fail(MZ_E_INVALID, "CartPole env needs num_actions == 2 and a (4,5) observation");
+    } else if (env_kind == MZ_ENV_TICTACTOE) {
+        if (c.num_actions != 10 || obs_dim(c) != 81) return fail(MZ_E_INVALID, "TicTacToe env needs num_actions == 10 and a (9,3,3) observation");
+    } else if (env_kind == MZ_ENV_GOMOKU) {
+        if (c.net_kind != MZ_NET_BOARD || c.obs_c != 9 || c.obs_h != c.obs_w || c.num_actions != c.obs_h * c.obs_w + 1 || c.obs_h < 5)
+            return fail(MZ_E_INVALID, "Gomoku env needs a board net with a (9,N,N) observation, N >= 5, and num_actions == N*N + 1");
+        board_n = c.obs_h;
+        num_to_win = 5;
+    } else {
+        return fail(MZ_E_INVALID, "the arena plays the device envs CartPole, TicTacToe and Gomoku (not the synthetic or host-stepped kinds)");
+    }
+    const bool two = env_kind != MZ_ENV_CARTPOLE;
+    if (opponent_kind != MZ_ARENA_NONE && opponent_kind != MZ_ARENA_RANDOM && opponent_kind != MZ_ARENA_PLANNER) return fail(MZ_E_INVALID, "unknown opponent kind");
+    if (two != (opponent_kind != MZ_ARENA_NONE)) return fail(MZ_E_INVALID, "two-player envs need an opponent (MZ_ARENA_RANDOM / MZ_ARENA_PLANNER), one-player envs MZ_ARENA_NONE");
+    if (two && (c.num_envs & 1)) return fail(MZ_E_INVALID, "two-player arenas need an even num_envs (env i and i + num_envs / 2 are a pair)");
+    if (opening_plies < 0) return fail(MZ_E_INVALID, "opening_plies must be >= 0");
+    if (h_init_state && env_kind != MZ_ENV_CARTPOLE) return fail(MZ_E_INVALID, "only the CartPole env takes an initial state");
+    if (opponent_kind == MZ_ARENA_PLANNER) {
+        if (!q || q == p) return fail(MZ_E_INVALID, "MZ_ARENA_PLANNER needs a second planner");
+        if (q->device != p->device) return fail(MZ_E_INVALID, "the opponent planner must be on the challenger's device");
+        if (!arena_same_config(p->cfg, q->cfg)) return fail(MZ_E_INVALID, "the opponent planner's mz_config must equal the challenger's (apart from the seed)");
+        if (!q->committed) return fail(MZ_E_STATE, "the opponent planner's weights are not committed");
+    } else if (q) {
+        return fail(MZ_E_INVALID, "an opponent planner is given but the opponent kind is not MZ_ARENA_PLANNER");
+    }
+    if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (!p->ev_arena_pre) {
+        HIPCHK(hipEventCreateWithFlags(&p->ev_arena_pre, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&p->ev_arena_q, hipEventDisableTiming));
+    }
+    p->env_kind = env_kind;
+    p->ring_len = 1; p->ring_pos = 0; p->ring_count = 0;  // no self-play records in this mode (mz_selfplay_read: MZ_E_INVALID)
+    p->selfplay_moves = 0;
+    hipError_t e = env_alloc(p->env, env_kind, c.num_envs, c.num_actions, obs_dim(c), 1, board_n, num_to_win);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    e = arena_alloc(p->arena, c.num_envs, c.num_actions, obs_dim(c));
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("arena_alloc: ") + hipGetErrorString(e));
+    p->arena.half = two ? c.num_envs / 2 : 0;
+    p->arena.opponent = opponent_kind;
+    p->arena.opening_plies = opening_plies;
+    p->arena_q = opponent_kind == MZ_ARENA_PLANNER ? q : nullptr;
+    p->arena_ply = 0;
+    if (h_init_state) HIPCHK(hipMemcpyAsync(p->env.init_state, h_init_state, (size_t)c.num_envs * 4 * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    ArenaLaunch R = arena_launch(p);
+    R.L.use_init = h_init_state != nullptr;
+    hipLaunchKernelGGL(k_arena_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, R);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->arena_open = true;
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
+    if (!p || n_plies < 1) return fail(MZ_E_INVALID, "bad argument to mz_arena_step");
+    if (!p->arena_open) return fail(MZ_E_STATE, "call mz_arena_reset first");
+    mz_planner* q = p->arena_q;
+    if (!p->committed || (q && !q->committed)) return fail(MZ_E_STATE, "weights not committed");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    const int B = c.num_envs, half = p->arena.half;
+    const dim3 waves((B + 3) / 4), block(256);
+    for (int m = 0; m < n_plies; m++) {
+        ArenaLaunch R = arena_launch(p);
+        const int t = p->arena_ply;
+        const bool opening = t < p->arena.opening_plies;
+        // black moves at even plies; the challenger is black in the lower half of the envs and white in the upper half
+        const int other = p->arena.opponent == MZ_ARENA_RANDOM ? SIDE_RANDOM : SIDE_OPPONENT;
+        if (half) {
+            R.nseg = 2;
+            R.seg[0].lo = 0; R.seg[0].n = half; R.seg[0].side = opening ? SIDE_OPENING : ((t & 1) ? other : SIDE_CHALLENGER);
+            R.seg[1].lo = half; R.seg[1].n = half; R.seg[1].side = opening ? SIDE_OPENING : ((t & 1) ? SIDE_CHALLENGER : other);
+        } else {
+            R.nseg = 1;
+            R.seg[0].lo = 0; R.seg[0].n = B; R.seg[0].side = opening ? SIDE_OPENING : SIDE_CHALLENGER;
+        }
+        bool picks = false;
+        int n_p = 0, n_q = 0;
+        for (int k = 0; k < R.nseg; k++) {
+            if (R.seg[k].side == SIDE_CHALLENGER) { arena_seg_searched(R.seg[k], p); n_p = R.seg[k].n; }
+            else if (R.seg[k].side == SIDE_OPPONENT) { arena_seg_searched(R.seg[k], q); n_q = R.seg[k].n; }
+            else picks = true;
+        }
+        const size_t work = (size_t)B * obs_dim(c) / 4 + 1;
+        const int pre_blocks = (int)((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024);
+        hipLaunchKernelGGL(k_arena_pre, dim3(pre_blocks), block, 0, p->stream, R);
+        if (picks) hipLaunchKernelGGL(k_arena_pick, waves, block, 0, p->stream, R);
+        HIPCHK(hipGetLastError());
+        if (n_q) {  // the opponent's half on its own stream, beside the challenger's
+            HIPCHK(hipEventRecord(p->ev_arena_pre, p->stream));
+            HIPCHK(hipStreamWaitEvent(q->stream, p->ev_arena_pre, 0));
+            int rc = launch_search(q, n_q, 1, true, false, false);
+            if (rc) return rc;
+            HIPCHK(hipEventRecord(p->ev_arena_q, q->stream));
+        }
+        if (n_p) {
+            int rc = launch_search(p, n_p, 1, true, false, false);
+            if (rc) return rc;
+        }
+        if (n_q) HIPCHK(hipStreamWaitEvent(p->stream, p->ev_arena_q, 0));
+        hipLaunchKernelGGL(k_arena_step, waves, block, 0, p->stream, R);
+        HIPCHK(hipGetLastError());
+        p->arena_ply++;
+    }
+    return MZ_OK;
+}
+
+// drains the arena's work (the opponent's stream is ordered before the challenger's k_arena_step) and reports a search error of either side
+static int arena_drain(mz_planner* p) {
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    mz_planner* both[2] = {p, p->arena_q};
+    for (mz_planner* s : both) {
+        if (!s) continue;
+        int err = 0;
+        HIPCHK(hipMemcpy(&err, s->d_err, sizeof(int), hipMemcpyDeviceToHost));
+        if (err) {
+            HIPCHK(hipMemset(s->d_err, 0, sizeof(int)));
+            return fail(MZ_E_INVALID, "search kernel reported error " + std::to_string(err));
+        }
+    }
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_read_ply(mz_planner* p, float* h_obs, uint8_t* h_mask, int32_t* h_player, int32_t* h_side, double* h_pi, double* h_root,
+                                 int32_t* h_action, double* h_u, uint8_t* h_live) {
+    if (!p) return fail(MZ_E_INVALID, "null planner");
+    if (!p->arena_open || p->arena_ply < 1) return fail(MZ_E_STATE, "no arena ply played yet");
+    int rc = arena_drain(p);
+    if (rc) return rc;
+    const size_t B = (size_t)p->cfg.num_envs, A = (size_t)p->cfg.num_actions, D = (size_t)obs_dim(p->cfg);
+    const ArenaState& a = p->arena;
+    if (h_obs) HIPCHK(hipMemcpy(h_obs, a.r_obs, B * D * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_mask) HIPCHK(hipMemcpy(h_mask, a.r_mask, B * A, hipMemcpyDeviceToHost));
+    if (h_player) HIPCHK(hipMemcpy(h_player, a.r_player, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (h_side) HIPCHK(hipMemcpy(h_side, a.r_side, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (h_pi) HIPCHK(hipMemcpy(h_pi, a.r_pi, B * A * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_root) HIPCHK(hipMemcpy(h_root, a.r_root, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_action) HIPCHK(hipMemcpy(h_action, a.r_action, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (h_u) HIPCHK(hipMemcpy(h_u, a.r_u, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_live) HIPCHK(hipMemcpy(h_live, a.r_live, B, hipMemcpyDeviceToHost));
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_result(mz_planner* p, int32_t* h_winner, int32_t* h_length, double* h_ret, int64_t totals[4], int32_t* n_live) {
+    if (!p) return fail(MZ_E_INVALID, "null planner");
+    if (!p->arena_open) return fail(MZ_E_STATE, "call mz_arena_reset first");
+    int rc = arena_drain(p);
+    if (rc) return rc;
+    const size_t B = (size_t)p->cfg.num_envs;
+    const ArenaState& a = p->arena;
+    if (h_winner) HIPCHK(hipMemcpy(h_winner, a.winner, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (h_length) HIPCHK(hipMemcpy(h_length, a.length, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (h_ret) HIPCHK(hipMemcpy(h_ret, a.ret, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (totals) {
+        unsigned long long t[4];
+        HIPCHK(hipMemcpy(t, a.totals, sizeof(t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 4; i++) totals[i] = (int64_t)t[i];
+    }
+    if (n_live) HIPCHK(hipMemcpy(n_live, a.n_live, sizeof(int), hipMemcpyDeviceToHost));
     return MZ_OK;
 }
 

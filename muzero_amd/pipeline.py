@@ -438,11 +438,157 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
     return played * B
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# evaluation matches on the device arena (Planner.arena_*)
+# ------------------------------------------------------------------------------------------------------------------
+ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku')
+_UNFINISHED, _WIN_CHALLENGER, _WIN_OPPONENT, _DRAW = 0, 1, 2, 3  # planner.ARENA_* (kept here so this module imports without the library)
+
+
+class MatchResult(NamedTuple):
+    """Outcome of `play_match`.  Per game, in env-index order: `winner` (1 challenger, 2 opponent, 3 draw -- or a finished one-player
+    episode), `length` (plies) and `ret` (the undiscounted return of a one-player episode; +1 / -1 / 0 from the challenger's side of a
+    board game).  For two-player envs games [0, n/2) had the challenger as black, games [n/2, n) as white."""
+    winner: np.ndarray
+    length: np.ndarray
+    ret: np.ndarray
+    two_player: bool
+
+    @property
+    def num_games(self) -> int:
+        return int(len(self.winner))
+
+    @property
+    def wins(self) -> int:
+        return int((self.winner == _WIN_CHALLENGER).sum())
+
+    @property
+    def losses(self) -> int:
+        return int((self.winner == _WIN_OPPONENT).sum())
+
+    @property
+    def draws(self) -> int:
+        return int((self.winner == _DRAW).sum())
+
+    @property
+    def score(self) -> float:
+        """(wins + draws / 2) / games."""
+        return (self.wins + 0.5 * self.draws) / max(self.num_games, 1)
+
+    def by_colour(self) -> dict:
+        """{'black': (wins, draws, losses), 'white': (...)}: the challenger's games as each colour (two-player envs)."""
+        if not self.two_player:
+            raise ValueError('by_colour: a one-player match has no colours')
+        h = self.num_games // 2
+        part = lambda w: (int((w == _WIN_CHALLENGER).sum()), int((w == _DRAW).sum()), int((w == _WIN_OPPONENT).sum()))  # noqa: E731
+        return dict(black=part(self.winner[:h]), white=part(self.winner[h:]))
+
+    def elo(self, challenger_elo: float, opponent_elo: float) -> float:
+        """The challenger's rating after folding the decided games, in env-index order, through `rating.compute_elo_rating` with the
+        opponent's rating held fixed.  Draws are skipped, as pipeline.py:378-383 skips them."""
+        from muzero_amd.rating import compute_elo_rating
+
+        if not self.two_player:
+            raise ValueError('elo: a one-player match has no opponent')
+        r = challenger_elo
+        for w in self.winner:
+            if w == _WIN_CHALLENGER:
+                r, _ = compute_elo_rating(0, r, opponent_elo)
+            elif w == _WIN_OPPONENT:
+                r, _ = compute_elo_rating(1, r, opponent_elo)
+        return r
+
+
+def resolve_arena_env(env) -> str:
+    """The device env an arena plays `env` on: a name, or an object with a device twin (resolved as run_self_play resolves it)."""
+    name = _device_env_name(env)
+    if name is None and hasattr(env, 'board_size') and hasattr(env, 'num_to_win'):  # games.BoardGameEnv and its subclasses
+        if env.board_size == 3 and env.num_to_win == 3:
+            name = 'TicTacToe'
+        elif env.num_to_win == 5:
+            name = 'Gomoku'
+    if name is None:
+        from muzero_amd.games import CartPoleEnv
+
+        if isinstance(env, CartPoleEnv):
+            name = 'CartPole-v1'
+    if name not in ARENA_ENVS:
+        raise ValueError(f'no arena for {env!r}: the arena plays the device envs {sorted(ARENA_ENVS)} (a name, or an env object with a device twin)')
+    return name
+
+
+def play_match(config, challenger_network, opponent, device, env, num_games: int, opening_plies: Optional[int] = None, tag: str = None,
+               init_state=None) -> MatchResult:
+    """`num_games` evaluation games in lock-step on the GPU (Planner.arena_*), every searched move a deterministic search
+    (pipeline.py:374, 468).  `opponent`: a network (two-player envs), 'random' (two-player envs), or None (one-player envs).  `env`: a
+    device-env name ('TicTacToe', 'Gomoku', 'CartPole-v1') or an env object with a device twin.  Two-player envs: `num_games` must be
+    even -- the challenger plays black in the first half and white in the second, game i and game i + num_games / 2 share their
+    `opening_plies` random opening plies (default: 2 against a network, 0 otherwise; deterministic play from one opening would repeat one
+    game).  `init_state`: CartPole start states [num_games, 4].  `tag` names the match in error messages."""
+    what = f'play_match({tag})' if tag else 'play_match'
+    name = resolve_arena_env(env)
+    two = name != 'CartPole-v1'
+    num_games = int(num_games)
+    if num_games < 1:
+        raise ValueError(f'{what}: num_games must be >= 1, got {num_games}')
+    if two and num_games % 2:
+        raise ValueError(f'{what}: {name} is a two-player env, num_games must be even (colours are balanced), got {num_games}')
+    is_net = opponent is not None and not isinstance(opponent, str)
+    if isinstance(opponent, str) and opponent != 'random':
+        raise ValueError(f"{what}: opponent must be a network, 'random' or None, got {opponent!r}")
+    if two and opponent is None:
+        raise ValueError(f"{what}: {name} needs an opponent (a network or 'random')")
+    if not two and opponent is not None:
+        raise ValueError(f'{what}: {name} is a one-player env, opponent must be None')
+    if is_net and not (hasattr(opponent, 'planner_spec') and hasattr(opponent, 'state_dict')):
+        raise ValueError(f"{what}: opponent must be a network, 'random' or None, got {opponent!r}")
+    if opening_plies is None:
+        opening_plies = 2 if is_net else 0
+    if int(opening_plies) < 0:
+        raise ValueError(f'{what}: opening_plies must be >= 0, got {opening_plies}')
+    if init_state is not None and name != 'CartPole-v1':
+        raise ValueError(f'{what}: init_state is for CartPole-v1 only')
+    if is_net and opponent.planner_spec() != challenger_network.planner_spec():
+        raise ValueError(f'{what}: challenger and opponent networks differ in shape')
+    from muzero_amd import planner as pl
+
+    kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU}
+    idx = device.index if getattr(device, 'index', None) is not None else 0
+    seed = int(getattr(config, 'planner_seed', 1))
+    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729), idx)
+    q = None
+    try:
+        p.load_state_dict(challenger_network.state_dict())
+        if is_net:
+            q = pl.Planner(pl.make_mz_config(opponent.planner_spec(), config, num_envs=num_games, seed=seed + 130003), idx)
+            q.load_state_dict(opponent.state_dict())
+        p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
+        cap = 500 if not two else p.A - 1  # the env's own cap: CartPole's TimeLimit, a board's point count
+        res = p.arena_result()
+        played = 0
+        while res['live'] > 0 and played < cap:
+            n = min(8, cap - played)
+            p.arena_step(n)
+            played += n
+            res = p.arena_result()
+        if res['live'] > 0:
+            raise RuntimeError(f'{what}: {res["live"]} games still running after the env cap of {cap} plies')
+        return MatchResult(res['winner'].copy(), res['length'].copy(), res['ret'].copy(), two)
+    finally:
+        p.close()  # (the challenger first: it borrows the opponent's planner)
+        if q is not None:
+            q.close()
+
+
 def run_board_game_evaluator(config, old_checkpoint_network, new_ckpt_network, device, env, temperature, checkpoint_files, stop_event,
-                             initial_elo: int = -2000, tag: str = None, on_result=None) -> float:
+                             initial_elo: int = -2000, tag: str = None, on_result=None, match_games: int = 0, opening_plies: int = 2) -> float:
     """pipeline.py:289-397: for every new checkpoint, one deterministic game new (black) vs previous (white) checkpoint on a
     host `games.BoardGameEnv`, searches through the HIP planner; Elo update as the reference does (white inherits black's
-    rating).  `on_result(black_elo, env.steps, train_steps)` stands in for the tensorboard trackers.  Returns the final Elo."""
+    rating).  `on_result(black_elo, env.steps, train_steps)` stands in for the tensorboard trackers.  Returns the final Elo.
+
+    `match_games` > 0: each checkpoint is judged by a device match of that many games instead (`play_match`: new checkpoint against
+    the previous one, colours balanced, `opening_plies` random opening plies per pair); the Elo is the match folded game by game
+    (`MatchResult.elo`) against the previous checkpoint's rating, and the step count handed to the trackers is the mean game length."""
     from muzero_amd import mcts
     from muzero_amd.games import BoardGameEnv
     from muzero_amd.rating import compute_elo_rating
@@ -467,6 +613,16 @@ def run_board_game_evaluator(config, old_checkpoint_network, new_ckpt_network, d
         train_steps = loaded_state['train_steps']
         new_ckpt_network.eval()
         old_checkpoint_network.eval()
+        if match_games > 0:
+            match = play_match(config, new_ckpt_network, old_checkpoint_network, device, env, match_games, opening_plies=opening_plies, tag=tag)
+            black_elo = match.elo(black_elo, white_elo)
+            white_elo = black_elo
+            steps = int(round(float(match.length.mean())))
+            tracker.board_game_step(black_elo, steps, train_steps)
+            if on_result is not None:
+                on_result(black_elo, steps, train_steps)
+            old_checkpoint_network.load_state_dict(new_ckpt_network.state_dict())
+            continue
         obs = env.reset()
         done = False
         while not done:
@@ -489,11 +645,14 @@ def run_board_game_evaluator(config, old_checkpoint_network, new_ckpt_network, d
 
 
 def run_evaluator(config, new_ckpt_network, device, env, temperature, checkpoint_files, stop_event, tag: str = None, num_episodes: int = 1,
-                  on_result=None) -> List:
+                  on_result=None, device_episodes: int = 0) -> List:
     """pipeline.py:400-488: for every new checkpoint, `num_episodes` deterministic episodes on a host environment exposing
     `reset / step / actions_mask / current_player / opponent_player` (e.g. `games.CartPoleEnv`), searches through the HIP
     planner.  `on_result(eval_returns, eval_steps, train_steps)` stands in for the tensorboard trackers; the list of those
-    triples is returned."""
+    triples is returned.
+
+    `device_episodes` > 0: each checkpoint plays that many episodes in lock-step on the device twin of `env` instead (`play_match`
+    with no opponent); the same tracker calls receive their returns and lengths."""
     from muzero_amd import mcts
 
     for p in new_ckpt_network.parameters():
@@ -513,7 +672,10 @@ def run_evaluator(config, new_ckpt_network, device, env, temperature, checkpoint
         train_steps = loaded_state['train_steps']
         new_ckpt_network.eval()
         eval_returns, eval_steps = [], []
-        for _ in range(num_episodes):
+        if device_episodes > 0:
+            match = play_match(config, new_ckpt_network, None, device, env, device_episodes, tag=tag)
+            eval_returns, eval_steps = [float(r) for r in match.ret], [int(n) for n in match.length]
+        for _ in range(num_episodes if device_episodes <= 0 else 0):
             obs = env.reset()
             done, steps, returns = False, 0, 0.0
             while not done:

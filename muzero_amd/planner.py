@@ -14,6 +14,9 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libmzplanner_hip.so')
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
 ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL = 0, 1, 2, 3, 4, 5
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
+ARENA_NONE, ARENA_RANDOM, ARENA_PLANNER = 0, 1, 2  # opponent kinds of mz_arena_reset
+SIDE_CHALLENGER, SIDE_OPPONENT, SIDE_RANDOM, SIDE_OPENING = 0, 1, 2, 3  # who chose a ply's move (arena_read_ply 'side')
+ARENA_UNFINISHED, ARENA_WIN_CHALLENGER, ARENA_WIN_OPPONENT, ARENA_DRAW = 0, 1, 2, 3  # arena_result 'winner'
 
 # every symbol include/mzplanner.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
@@ -21,6 +24,7 @@ ABI_SYMBOLS = [
     'mz_planner_initial_inference', 'mz_planner_recurrent_inference', 'mz_planner_hidden_size', 'mz_planner_search',
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
+    'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
 ]
 
@@ -92,6 +96,10 @@ def load_library():
     L.mz_selfplay_reset_external.argtypes = [vp, C.POINTER(MzExternalEnv)]
     L.mz_selfplay_external_act.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp]
     L.mz_selfplay_external_commit.argtypes = [vp, vp, vp]
+    L.mz_arena_reset.argtypes = [vp, i32, i32, vp, i32, vp]
+    L.mz_arena_step.argtypes = [vp, i32]
+    L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
+    L.mz_arena_result.argtypes = [vp, vp, vp, vp, i64p, vp]
     L.mz_profile_begin.argtypes = [vp]
     L.mz_profile_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mz_planner_synchronize.argtypes = [vp]
@@ -352,6 +360,49 @@ class Planner:
         if self._replay_keepalive is not None:
             self._replay_keepalive[0].detach_device_writer()
         self._replay_keepalive = None
+
+    # ---- arena: evaluation games in lock-step (mz_arena_*; pipeline.py:289-397, 400-488) ----
+    def arena_reset(self, env_kind, opponent=None, opening_plies=0, init_state=None):
+        """Start `num_envs` evaluation games on the device env `env_kind`.  `opponent`: None (one-player envs), 'random', or a second
+        `Planner` on the same GPU with the same configuration (apart from the seed) and loaded weights -- it is borrowed until this
+        planner's next reset or close, and kept alive here.  Two-player envs: the challenger (this planner) is black in envs [0, B/2) and
+        white in [B/2, B); the first `opening_plies` plies are random moves shared by env i and env i + B/2."""
+        if opponent is None:
+            kind, q = ARENA_NONE, None
+        elif isinstance(opponent, str):
+            if opponent != 'random':
+                raise ValueError(f"opponent must be None, 'random' or a Planner, got {opponent!r}")
+            kind, q = ARENA_RANDOM, None
+        elif isinstance(opponent, Planner):
+            kind, q = ARENA_PLANNER, opponent
+        else:
+            raise ValueError(f"opponent must be None, 'random' or a Planner, got {opponent!r}")
+        init = None if init_state is None else np.ascontiguousarray(init_state, np.float64).reshape(self.B, 4)
+        _chk(self.lib.mz_arena_reset(self.h, int(env_kind), kind, q.h if q is not None else None, int(opening_plies), _p(init)))
+        self._arena_opponent = q
+
+    def arena_step(self, n_plies=1):
+        """`n_plies` lock-step plies, enqueued without a host synchronisation."""
+        _chk(self.lib.mz_arena_step(self.h, int(n_plies)))
+
+    def arena_read_ply(self):
+        """The last ply per env: dict(obs, mask, player -- the root before the move; side (SIDE_*), pi, root_value, action, u -- the move;
+        live -- 1 where the env was live when the ply began, elsewhere the other fields are those of its last ply)."""
+        B, A, D = self.B, self.A, self.obs_dim
+        out = dict(obs=np.empty((B, D), np.float32), mask=np.empty((B, A), np.uint8), player=np.empty(B, np.int32), side=np.empty(B, np.int32),
+                   pi=np.empty((B, A), np.float64), root_value=np.empty(B, np.float64), action=np.empty(B, np.int32), u=np.empty(B, np.float64),
+                   live=np.empty(B, np.uint8))
+        _chk(self.lib.mz_arena_read_ply(self.h, *[_p(out[k]) for k in ('obs', 'mask', 'player', 'side', 'pi', 'root_value', 'action', 'u', 'live')]))
+        return out
+
+    def arena_result(self):
+        """The tally: dict(winner [B] (ARENA_*), length [B], ret [B], challenger_wins, opponent_wins, draws, finished_plies, live)."""
+        B = self.B
+        winner, length, ret = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.float64)
+        totals, live = (C.c_int64 * 4)(), C.c_int32()
+        _chk(self.lib.mz_arena_result(self.h, _p(winner), _p(length), _p(ret), totals, C.cast(C.byref(live), C.c_void_p)))
+        return dict(winner=winner, length=length, ret=ret, challenger_wins=int(totals[0]), opponent_wins=int(totals[1]), draws=int(totals[2]),
+                    finished_plies=int(totals[3]), live=int(live.value))
 
     def selfplay_counters(self):
         c = (C.c_int64 * 4)()
