@@ -61,6 +61,8 @@ def main():
     ap.add_argument('--graphed', action='store_true', help='the PyTorch-ROCm update as one HIP graph (learner.GraphedTrainStep)')
     ap.add_argument('--autograd', action='store_true', help='the PyTorch-ROCm update, eager (learner.train_step)')
     ap.add_argument('--out', default='')
+    ap.add_argument('--conv-precision', choices=['f32', 'bf16x3'], default='f32',
+                    help="the planner's conv arithmetic (mz_config.conv_precision): f32 is bit-equal to the oracle, bf16x3 the split-bf16 path; the learner stays float32")
     ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
                     help='also play N games (even) against the random opponent as one lock-step batch on the device (pipeline.play_match); 0: off')
     args = ap.parse_args()
@@ -97,7 +99,7 @@ def main():
         opt = torch.optim.Adam(net.parameters(), lr=cfg.lr_init, weight_decay=cfg.weight_decay)
     sched = None if hip is not None else torch.optim.lr_scheduler.MultiStepLR(opt, milestones=cfg.lr_milestones, gamma=cfg.lr_decay_rate)
     replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda')
-    p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed), 0)
+    p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed, conv_precision=args.conv_precision), 0)
     net.eval()
     p.load_state_dict(net.state_dict())
     if not args.host_assembly:

@@ -67,7 +67,16 @@ typedef struct {
      * reference pins 1.21.6 (requirements.txt:21) -- promotes it to float64 and rounds once.  0 (default): the numpy-2 form, the one every
      * recorded fixture of this repo was produced under; 1: the numpy-1.21 form.  Self-play (float64 prior after the noise) is the same in both. */
     int32_t legacy_scalar_promotion;
+    /* Arithmetic of the board nets' 3x3 convolutions.  MZ_CONV_F32 (0, default): float32 MFMA in the oracle's summation order, bit-equal to the
+     * oracle.  MZ_CONV_BF16X3 (1): every float32 operand as the exact sum of three bf16 values, six bf16 MFMA products per step accumulated in
+     * float32: NOT bit-equal to the oracle, held to the reference within the reference's own tolerance; results still do not depend on
+     * the batch, the row or the kernel build.  MZ_NET_BOARD only: mz_planner_create returns MZ_E_INVALID for MZ_NET_MLP, MZ_NET_ATARI and for any
+     * other value.  Heads, normalisation, residual adds and the dynamics net's action terms stay float32. */
+    int32_t conv_precision;
 } mz_config;
+
+#define MZ_CONV_F32 0
+#define MZ_CONV_BF16X3 1
 
 /* Injected randomness for a batch of searches: replaces the reference's global numpy RNG
  * (np.random.dirichlet mcts.py:245, np.random.choice mcts.py:124 and :404).  All host pointers.

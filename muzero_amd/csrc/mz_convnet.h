@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mz_conv.h"
+#include "mz_conv_split.h"
 #include "mz_search.h"
 #include "mz_tower.h"
 
@@ -28,6 +29,7 @@ struct ConvLayerDev {
     float* w = nullptr;
     float* b = nullptr;
     int cin = 0, cin_real = 0, cout = 0, stride = 1;
+    const conv_u32x4* w3 = nullptr;  // split mode (mz_conv_split.h): the three bf16 fragment streams; non-null selects k_conv3x3_bf16x3 in conv_run
 };
 struct ResBlockDev {
     ConvLayerDev c1, c2;
@@ -39,6 +41,7 @@ struct HeadDev {
 
 struct ConvNetDev {
     int kind = 0;  // MZ_NET_BOARD (1) / MZ_NET_ATARI (2)
+    int split = 0; // mz_config.conv_precision == MZ_CONV_BF16X3: every conv also gets its split-bf16 weight copy, no fused towers
     int in_c = 0, in_h = 0, in_w = 0, A = 0, R = 0, P = 0, Sv = 1, Sr = 1, hh = 0, hw = 0;
     ConvLayerDev rep_conv, rep_conv2;
     std::vector<ResBlockDev> rep_res, dyn_res, pred_res;
@@ -164,6 +167,38 @@ inline int build_conv(ConvNetDev& n, const ParamMap& pm, const std::string& conv
                         }
                     }
     out->cin = pcin; out->cin_real = pack_cin >= 0 ? pcin : cin_real; out->cout = cout; out->stride = stride;
+    out->w3 = nullptr;
+    if (n.split) {
+        // mz_conv_split.h: [co_tile][32-channel block][tap][term h, m, l][lane][8 bf16], B fragment of v_mfma_f32_16x16x32_bf16:
+        // W'[16t + (lane & 15)][cb * 32 + 8 * (lane >> 4) + j][tap]; channels padded to 32 with zeros
+        const int n_cb32 = (pcin + 31) / 32;
+        std::vector<unsigned short> p3((size_t)co_tiles * n_cb32 * taps * 3 * 64 * 8, 0);
+        for (int t = 0; t < co_tiles; t++)
+            for (int cb = 0; cb < n_cb32; cb++)
+                for (int tap = 0; tap < taps; tap++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int j = 0; j < 8; j++) {
+                            const int co = 16 * t + (lane & 15), ci = cb * 32 + 8 * (lane >> 4) + j;
+                            if (co >= cout || ci >= pcin) continue;
+                            float v = W.data[((size_t)co * cin + ci) * taps + tap];
+                            if (!bn.empty()) v = v * alpha[co];
+                            float r = v;
+                            for (int term = 0; term < 3; term++) {  // h = bf16(v), m = bf16(v - h), l = bf16(v - h - m): exact
+                                unsigned u;
+                                memcpy(&u, &r, 4);
+                                const unsigned b16 = conv_bf16_rne(u), back = b16 << 16;
+                                float f;
+                                memcpy(&f, &back, 4);
+                                r = r - f;
+                                p3[(((((size_t)t * n_cb32 + cb) * taps + tap) * 3 + term) * 64 + lane) * 8 + j] = (unsigned short)b16;
+                            }
+                        }
+        void* d = nullptr;
+        if (hipMalloc(&d, p3.size() * 2) != hipSuccess) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
+        n.allocs.push_back(d);
+        if (hipMemcpy(d, p3.data(), p3.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
+        out->w3 = reinterpret_cast<const conv_u32x4*>(d);
+    }
     if (dev_upload(n, pw, &out->w) != hipSuccess || dev_upload(n, bias, &out->b) != hipSuccess) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
     return 0;
 }
@@ -282,7 +317,7 @@ inline int convnet_build(ConvNetDev& n, const ParamMap& pm, std::string* err) {
     if ((rc = build_head(n, pm, "prediction_net.policy_net", P, 2, hw, n.A, &n.policy, err))) return rc;
     if ((rc = build_head(n, pm, "prediction_net.value_net", P, 1, hw, n.Sv, &n.value, err))) return rc;
     auto table = [&](const std::vector<ResBlockDev>& blocks, const float** w, const float** b) -> int {
-        if (blocks.empty() || P > 128 || (P & 15)) return 0;
+        if (blocks.empty() || P > 128 || (P & 15) || n.split) return 0;  // (split mode: one launch per conv)
         const size_t wn = (size_t)(P / 16) * (P / 16) * 9 * 256, n_convs = 2 * blocks.size();
         float *dw = nullptr, *db = nullptr;
         if (hipMalloc(&dw, n_convs * wn * sizeof(float)) != hipSuccess || hipMalloc(&db, n_convs * P * sizeof(float)) != hipSuccess) return -2;
@@ -421,6 +456,45 @@ inline void conv_launch_npt(int npt, dim3 grid, size_t lds, hipStream_t st, cons
     }
 }
 
+// Split mode (mz_conv_split.h): which build of k_conv3x3_bf16x3 runs a stride-1 conv on h x w images with cout output channels.  Whole-image
+// builds for 15 x 15 and 19 x 19 (MZ_CONV_SPEC), the shape-generic 8 x 8-tile build for everything else.  All builds sum in one order.
+struct SplitGeom {
+    int side, npt, nct, th, tw;
+    const char* name;
+};
+inline SplitGeom split_geometry(int h, int w, int cout) {
+    const bool spec = conv_switches().conv_spec != 0 && h == w;
+    const int nct = cout > 64 ? 2 : 1;
+    if (spec && h == 15) return SplitGeom{15, 15, nct, 15, 15, nct == 2 ? "k_conv3x3_bf16x3<NPT=15, NCT=2, SIDE=15> (whole image)" : "k_conv3x3_bf16x3<NPT=15, NCT=1, SIDE=15> (whole image)"};
+    if (spec && h == 19) return SplitGeom{19, 23, nct, 19, 19, nct == 2 ? "k_conv3x3_bf16x3<NPT=23, NCT=2, SIDE=19> (whole image)" : "k_conv3x3_bf16x3<NPT=23, NCT=1, SIDE=19> (whole image)"};
+    return SplitGeom{0, 4, 1, 8, 8, "k_conv3x3_bf16x3<NPT=4, NCT=1, SIDE=0> (shape-generic, 8 x 8 tiles)"};
+}
+
+template <int NPT, int NCT, int SIDE>
+inline void split_launch(dim3 grid, size_t lds, hipStream_t st, const SplitConvLaunch& L) {
+    static bool attr_set = false;  // one planner thread per process configures this instantiation once
+    if (!attr_set && lds > 64 * 1024) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_bf16x3<NPT, NCT, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((k_conv3x3_bf16x3<NPT, NCT, SIDE>), grid, dim3(256), lds, st, L);
+}
+
+inline void conv_run_split(hipStream_t st, const ConvLayerDev& Lr, int B, const float* in, const float* const* in_ptrs, const int* action, int A, int h,
+                           int w, const float* residual, float* out, bool relu) {
+    SplitConvLaunch L{};
+    L.in_ptrs = in_ptrs; L.in = in; L.action = action; L.num_actions = A > 0 ? A : 1; L.cin_real = Lr.cin_real; L.cin = Lr.cin; L.h = h; L.w = w;
+    L.cout = Lr.cout; L.w3 = Lr.w3; L.bias = Lr.b; L.residual = residual; L.out = out; L.relu = relu ? 1 : 0; L.B = B;
+    const SplitGeom g = split_geometry(h, w, Lr.cout);
+    L.th = g.th; L.tw = g.tw; L.tiles_x = (w + g.tw - 1) / g.tw;
+    const int tiles_y = (h + g.th - 1) / g.th;
+    const size_t lds = (size_t)3 * 4 * split_npos_pad((g.th + 2) * (g.tw + 2)) * 16;
+    const dim3 grid(L.tiles_x * tiles_y, B, (Lr.cout + 64 * g.nct - 1) / (64 * g.nct));
+    if (g.side == 15) { if (g.nct == 2) split_launch<15, 2, 15>(grid, lds, st, L); else split_launch<15, 1, 15>(grid, lds, st, L); }
+    else if (g.side == 19) { if (g.nct == 2) split_launch<23, 2, 19>(grid, lds, st, L); else split_launch<23, 1, 19>(grid, lds, st, L); }
+    else split_launch<4, 1, 0>(grid, lds, st, L);
+}
+
 static long long* g_conv_stamps = nullptr;  // diagnostic builds only (tools/micro/conv_bench.hip)
 
 // one 3x3 conv launch; input either dense `in` or per-image `in_ptrs`
@@ -435,6 +509,10 @@ struct ConvSparse {
 inline bool conv_run(hipStream_t st, const ConvLayerDev& Lr, int B, const float* in, const float* const* in_ptrs, const int* action, int A, int ih,
                      int iw, const float* residual, float* out, bool relu, const float* in_base = nullptr, size_t in_span_floats = 0,
                      const ConvSparse* sp = nullptr) {
+    if (Lr.w3) {  // split mode: the sparse action terms stay float32 and exact in k_action_sparse, after the pre-activation is stored
+        conv_run_split(st, Lr, B, in, in_ptrs, action, A, ih, iw, residual, out, relu && !sp);
+        return false;
+    }
     ConvLaunch L{};
     L.in_ptrs = in_ptrs; L.in = in; L.in_base = in_base; L.action = action; L.num_actions = A > 0 ? A : 1;
     L.cin_real = Lr.cin_real; L.cin = Lr.cin; L.ih = ih; L.iw = iw; L.stride = Lr.stride;

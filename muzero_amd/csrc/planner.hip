@@ -210,6 +210,9 @@ extern "C" const char* mz_planner_describe(mz_planner* p) {
              " | per process: MZ_ACTION_SPARSE=%d MZ_ACTION_FUSE=%d MZ_CONV_SPEC=%d MZ_TOWER=%d MZ_CONV_TILE=%d MZ_CONV_G=%d MZ_CONV_NCT=%d",
              (int)p->force_generic, p->hwx, (int)p->tree_old, (int)p->hbm_tree, cs.action_sparse, cs.action_fuse, cs.conv_spec, cs.tower, cs.conv_tile, cs.conv_g, cs.conv_nct);
     g_describe = "search: " + p->last_dispatch + b;
+    if (p->conv && p->cnet.split)  // the build conv_run_split dispatches this net's tower convs to (the same chooser)
+        g_describe += std::string(" | conv_precision=bf16x3: ") + split_geometry(p->cnet.hh, p->cnet.hw, p->cnet.P).name + ", one launch per conv";
+    else if (p->conv) g_describe += " | conv_precision=f32";
     return g_describe.c_str();
 }
 
@@ -371,6 +374,12 @@ extern "C" int mz_planner_create(const mz_config* cfg, int device_id, mz_planner
     if (cfg->value_support_size < 1 || cfg->reward_support_size < 1 || cfg->value_support_size > 1023 || cfg->reward_support_size > 1023)
         return fail(MZ_E_INVALID, "support sizes must be in [1, 1023]");
     if (cfg->is_board_game && cfg->discount != 1.0) return fail(MZ_E_INVALID, "board games require discount == 1.0 (mcts.py:349-350)");
+    if (cfg->conv_precision != MZ_CONV_F32 && cfg->conv_precision != MZ_CONV_BF16X3)
+        return fail(MZ_E_INVALID, "conv_precision must be MZ_CONV_F32 (0) or MZ_CONV_BF16X3 (1)");
+    if (cfg->conv_precision == MZ_CONV_BF16X3 && cfg->net_kind == MZ_NET_MLP)
+        return fail(MZ_E_INVALID, "conv_precision MZ_CONV_BF16X3 needs a conv net: MZ_NET_MLP has no convolutions");
+    if (cfg->conv_precision == MZ_CONV_BF16X3 && cfg->net_kind == MZ_NET_ATARI)
+        return fail(MZ_E_INVALID, "conv_precision MZ_CONV_BF16X3 is built for MZ_NET_BOARD only: MZ_NET_ATARI's strided stages and 6 x 6 tower have no split build");
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return fail(MZ_E_HIP, "no HIP device visible: the planner has no CPU fallback");
@@ -405,6 +414,7 @@ static int planner_init(mz_planner* p, bool conv) {
         ConvNetDev& n = p->cnet;
         n.kind = cfg->net_kind; n.in_c = cfg->obs_c; n.in_h = cfg->obs_h; n.in_w = cfg->obs_w; n.A = cfg->num_actions;
         n.R = cfg->num_res_blocks; n.P = cfg->num_planes; n.Sv = cfg->value_support_size; n.Sr = cfg->reward_support_size;
+        n.split = cfg->conv_precision == MZ_CONV_BF16X3 ? 1 : 0;
         n.hh = conv && cfg->net_kind == MZ_NET_ATARI ? 6 : cfg->obs_h;
         n.hw = conv && cfg->net_kind == MZ_NET_ATARI ? 6 : cfg->obs_w;
         p->cfg.hidden_dim = n.hidden_size();
@@ -1344,7 +1354,7 @@ static bool arena_same_config(const mz_config& a, const mz_config& b) {
            x.is_board_game == y.is_board_game && x.has_known_bounds == y.has_known_bounds && x.known_bounds_min == y.known_bounds_min &&
            x.known_bounds_max == y.known_bounds_max && x.root_dirichlet_alpha == y.root_dirichlet_alpha &&
            x.root_exploration_eps == y.root_exploration_eps && x.num_envs == y.num_envs && x.max_ties == y.max_ties &&
-           x.legacy_scalar_promotion == y.legacy_scalar_promotion;
+           x.legacy_scalar_promotion == y.legacy_scalar_promotion && x.conv_precision == y.conv_precision;
 }
 
 static ArenaLaunch arena_launch(mz_planner* p) {

@@ -41,6 +41,7 @@ class MzConfig(C.Structure):
         ('pb_c_init', C.c_double), ('is_board_game', C.c_int32), ('has_known_bounds', C.c_int32), ('known_bounds_min', C.c_double),
         ('known_bounds_max', C.c_double), ('root_dirichlet_alpha', C.c_double), ('root_exploration_eps', C.c_double),
         ('num_envs', C.c_int32), ('max_ties', C.c_int32), ('seed', C.c_uint64), ('legacy_scalar_promotion', C.c_int32),
+        ('conv_precision', C.c_int32),
     ]
 
 
@@ -120,6 +121,17 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+CONV_PRECISIONS = {'f32': 0, 'bf16x3': 1}  # MZ_CONV_F32 / MZ_CONV_BF16X3 (include/mzplanner.h)
+
+
+def _conv_precision(v):
+    if isinstance(v, str) and v in CONV_PRECISIONS:
+        return CONV_PRECISIONS[v]
+    if not isinstance(v, (str, bool)) and v in (0, 1):
+        return int(v)
+    raise ValueError(f"conv_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
+
+
 def make_mz_config(spec, config=None, num_envs=1, max_ties=0, seed=1, **search_overrides):
     """Build an mz_config from a network spec (MuZeroNet.planner_spec()) and a MuZeroConfig-like object."""
     shape = tuple(spec['input_shape'])
@@ -137,7 +149,7 @@ def make_mz_config(spec, config=None, num_envs=1, max_ties=0, seed=1, **search_o
         has_known_bounds=int(kb is not None), known_bounds_min=float(kb[0]) if kb is not None else 0.0,
         known_bounds_max=float(kb[1]) if kb is not None else 0.0, root_dirichlet_alpha=float(g('root_dirichlet_alpha', 0.25)),
         root_exploration_eps=float(g('root_exploration_eps', 0.25)), num_envs=int(num_envs), max_ties=int(max_ties), seed=int(seed),
-        legacy_scalar_promotion=int(bool(g('legacy_scalar_promotion', False))),
+        legacy_scalar_promotion=int(bool(g('legacy_scalar_promotion', False))), conv_precision=_conv_precision(g('conv_precision', 0)),
     )
 
 
