@@ -35,6 +35,8 @@ def main():
     ap.add_argument('--eval-episodes', type=int, default=3)
     ap.add_argument('--eval-every', type=int, default=0, help='also evaluate every N training steps (deterministic episodes on the host env); 0: only at the end')
     ap.add_argument('--out', default='')
+    ap.add_argument('--host-reload', action='store_true',
+                    help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--host-assembly', action='store_true', help='assemble (Transition, priority) items on the host instead of the device epilogue')
     ap.add_argument('--learner', choices=('hip', 'graphed', 'eager'), default='hip',
                     help='hip: hand-written gfx950 kernels (hip_learner.HipLearner, batch gathered from the HBM ring by index); graphed: the PyTorch '
@@ -72,7 +74,7 @@ def main():
 
     p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed), 0)
     net.eval()
-    p.load_state_dict(net.state_dict())
+    p.reload(hl.planner_weights() if hl is not None else net.state_dict(), host=args.host_reload)
     if not args.host_assembly:
         p.attach_replay(replay, cfg, obs_shape=(4, 5))
     p.selfplay_reset(pl.ENV_CARTPOLE)
@@ -142,7 +144,7 @@ def main():
                 log.append(rec)
                 print(json.dumps(rec), flush=True)
         net.eval()
-        p.load_state_dict(net.state_dict())  # actor <- learner (the reference does this every checkpoint_interval steps)
+        p.reload(hl.planner_weights() if hl is not None else net.state_dict(), host=args.host_reload)  # actor <- learner (the reference does this every checkpoint_interval steps)
         if args.eval_every and steps < args.train_steps and steps // args.eval_every > (steps - args.updates_per_iter) // args.eval_every:
             evals.append(dict(train_steps=steps, eval_episode_lengths=evaluate()))
             print(json.dumps(evals[-1]), flush=True)

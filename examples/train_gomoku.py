@@ -61,6 +61,8 @@ def main():
     ap.add_argument('--graphed', action='store_true', help='the PyTorch-ROCm update as one HIP graph (learner.GraphedTrainStep)')
     ap.add_argument('--autograd', action='store_true', help='the PyTorch-ROCm update, eager (learner.train_step)')
     ap.add_argument('--out', default='')
+    ap.add_argument('--host-reload', action='store_true',
+                    help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--conv-precision', choices=['f32', 'bf16x3'], default='f32',
                     help="the planner's conv arithmetic (mz_config.conv_precision): f32 is bit-equal to the oracle, bf16x3 the split-bf16 path; the learner stays float32")
     ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
@@ -101,7 +103,7 @@ def main():
     replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda')
     p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed, conv_precision=args.conv_precision), 0)
     net.eval()
-    p.load_state_dict(net.state_dict())
+    p.reload(hip.planner_weights() if hip is not None else net.state_dict(), host=args.host_reload)
     if not args.host_assembly:
         p.attach_replay(replay, cfg, obs_shape=obs_shape)
     p.selfplay_reset(pl.ENV_GOMOKU)
@@ -161,7 +163,7 @@ def main():
                 log.append(rec)
                 print(json.dumps(rec), flush=True)
         net.eval()
-        p.load_state_dict(net.state_dict())
+        p.reload(hip.planner_weights() if hip is not None else net.state_dict(), host=args.host_reload)
     if args.out:
         json.dump(dict(args=vars(args), log=log), open(args.out, 'w'), indent=1)
 

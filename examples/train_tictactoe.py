@@ -47,6 +47,8 @@ def main():
     ap.add_argument('--eval-games', type=int, default=50)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--out', default='')
+    ap.add_argument('--host-reload', action='store_true',
+                    help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--host-assembly', action='store_true',
                     help="round 1's path: (Transition, priority) items assembled on the host and the PyTorch learner step; default: device epilogue "
                          'into the HBM replay + the HIP learner kernels (hip_learner.HipLearner), in event order (a seed gives one run)')
@@ -75,7 +77,7 @@ def main():
     replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda')
     p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed), 0)
     net.eval()
-    p.load_state_dict(net.state_dict())
+    p.reload(hl.planner_weights() if hl is not None else net.state_dict(), host=args.host_reload)
     if hl is not None:
         p.attach_replay(replay, cfg, obs_shape=(9, 3, 3))
     p.selfplay_reset(pl.ENV_TICTACTOE)
@@ -120,7 +122,7 @@ def main():
                 log.append(rec)
                 print(json.dumps(rec), flush=True)
         net.eval()
-        p.load_state_dict(net.state_dict())
+        p.reload(hl.planner_weights() if hl is not None else net.state_dict(), host=args.host_reload)
     if args.out:
         json.dump(dict(args=vars(args), log=log), open(args.out, 'w'), indent=1)
 

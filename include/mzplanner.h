@@ -125,6 +125,27 @@ int mz_planner_destroy(mz_planner* p);
 int mz_planner_set_param(mz_planner* p, const char* name, const float* h_data, const int64_t* shape, int32_t ndim);
 int mz_planner_commit_params(mz_planner* p);
 
+/* Weights that already live on the planner's GPU (a learner's master copy): the same hand-off, actor_network.load_state_dict
+ * (pipeline.py:266), without the host.  mz_planner_bind_param_device records a DEVICE pointer to a contiguous float32 tensor in torch
+ * layout under its state_dict key; nothing is copied, the caller keeps the memory alive and at that address (bind again after it
+ * moved).  MZ_E_INVALID for a pointer that is not device memory of the planner's GPU (host, pinned, managed, another GPU), for a tensor
+ * that leaves its allocation and for "...num_batches_tracked", which is never bound.  Binding is set-up: it may drain the planner's stream.
+ *
+ * mz_planner_refresh_params (re)builds every packed operand copy a commit builds -- MFMA fragment order, eval-mode BatchNorm folded in
+ * the commit's float32 operation order, the split-bf16 streams of MZ_CONV_BF16X3, tower tables, the tuned search kernel's weight
+ * stream -- from the bound tensors with kernels on the planner's stream, bit-identical to a commit of the same values.
+ * `producer_stream` is the hipStream_t whose work wrote the tensors (NULL: the null stream): the pack kernels wait for what it holds at
+ * the call, and its later work waits for them, so the producer's next optimizer step cannot overwrite weights that are still being
+ * packed.  Searches already enqueued on the planner finish on the old weights.  No host synchronisation, no allocation, no host read of
+ * a weight -- except in the FIRST refresh after the set of bound names or shapes changed: that one drains the planner's stream, runs the
+ * commit's own packers over probe tensors to learn where every packed element comes from (names and shapes are validated there exactly
+ * as for host tensors: MZ_E_STATE names a missing tensor, MZ_E_INVALID a wrong shape) and leaves the packed buffers allocated, so a
+ * handle that never saw mz_planner_set_param is complete after bind + refresh.  Tensors set with mz_planner_set_param stay as they were.
+ * Whichever of commit and refresh ran last defines the weights; a commit on a handle with a refresh in flight is preceded by
+ * mz_planner_synchronize. */
+int mz_planner_bind_param_device(mz_planner* p, const char* name, const float* d_data, const int64_t* shape, int32_t ndim);
+int mz_planner_refresh_params(mz_planner* p, void* producer_stream);
+
 /* MuZeroNet.initial_inference (network.py:62-84), batched.  obs float32 [batch, obs_c*obs_h*obs_w];
  * outputs hidden [batch, hidden_size], pi [batch, A], value [batch]; reward is identically 0 (network.py:76). */
 int mz_planner_initial_inference(mz_planner* p, int32_t batch, const float* h_obs, float* h_hidden, float* h_pi, float* h_value);

@@ -14,6 +14,7 @@
 
 #include "mz_conv.h"
 #include "mz_conv_split.h"
+#include "mz_pack.h"
 #include "mz_search.h"
 #include "mz_tower.h"
 
@@ -336,6 +337,55 @@ inline int convnet_build(ConvNetDev& n, const ParamMap& pm, std::string* err) {
     if (n.kind == 1 && table(n.rep_res, &n.tw_rep, &n.tb_rep)) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
     if (table(n.dyn_res, &n.tw_dyn, &n.tb_dyn) || table(n.pred_res, &n.tw_pred, &n.tb_pred)) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
     return 0;
+}
+
+// Every packed weight buffer convnet_build allocated, in a fixed order, with its size and a name (mz_debug_read_packed; the device
+// reload of mz_pack.h writes exactly these).  All 3x3 convs; sizes as build_conv / build_head / the tower tables allocate them.
+inline void convnet_packed_buffers(const ConvNetDev& n, std::vector<PackBufferRef>& out) {
+    auto conv = [&](const ConvLayerDev& c, const std::string& name) {
+        if (!c.w) return;
+        const size_t co_tiles = (c.cout + 15) / 16, n_cb = (c.cin + 15) / 16, n_cb32 = (c.cin + 31) / 32;
+        out.push_back(PackBufferRef{c.w, co_tiles * n_cb * 9 * 256 * sizeof(float), PACK_F32, name + ".w"});
+        out.push_back(PackBufferRef{c.b, co_tiles * 16 * sizeof(float), PACK_F32, name + ".b"});
+        if (c.w3) out.push_back(PackBufferRef{const_cast<conv_u32x4*>(c.w3), co_tiles * n_cb32 * 9 * 3 * 64 * 8 * 2, PACK_W3, name + ".w3"});
+    };
+    auto tower = [&](const std::vector<ResBlockDev>& blocks, const std::string& name) {
+        for (size_t i = 0; i < blocks.size(); i++) {
+            conv(blocks[i].c1, name + "." + std::to_string(i) + ".c1");
+            conv(blocks[i].c2, name + "." + std::to_string(i) + ".c2");
+        }
+    };
+    auto head = [&](const HeadDev& h, const std::string& name) {
+        if (!h.cw) return;
+        const size_t hw = (size_t)n.hh * n.hw;
+        out.push_back(PackBufferRef{h.cw, (size_t)h.oc * h.C * sizeof(float), PACK_F32, name + ".cw"});
+        out.push_back(PackBufferRef{h.cb, (size_t)h.oc * sizeof(float), PACK_F32, name + ".cb"});
+        out.push_back(PackBufferRef{h.lw, (size_t)h.n_out * h.oc * hw * sizeof(float), PACK_F32, name + ".lw"});
+        out.push_back(PackBufferRef{h.lb, (size_t)h.n_out * sizeof(float), PACK_F32, name + ".lb"});
+    };
+    auto table = [&](const float* w, const float* b, size_t blocks, const std::string& name) {
+        if (!w || !b) return;
+        const size_t wn = (size_t)(n.P / 16) * (n.P / 16) * 9 * 256, n_convs = 2 * blocks;
+        out.push_back(PackBufferRef{const_cast<float*>(w), n_convs * wn * sizeof(float), PACK_F32, name + ".tw"});
+        out.push_back(PackBufferRef{const_cast<float*>(b), n_convs * n.P * sizeof(float), PACK_F32, name + ".tb"});
+    };
+    conv(n.rep_conv, "rep_conv");
+    conv(n.rep_conv2, "rep_conv2");
+    tower(n.rep_res, "rep_res");
+    conv(n.dyn_conv, "dyn_conv");
+    conv(n.dyn_real, "dyn_real");
+    const size_t hw = (size_t)n.hh * n.hw;
+    if (n.dyn_act_w) out.push_back(PackBufferRef{n.dyn_act_w, (size_t)n.P * n.A * 9 * sizeof(float), PACK_F32, "dyn_act_w"});
+    if (n.dyn_sp_w) out.push_back(PackBufferRef{n.dyn_sp_w, ((size_t)n.A * 9 + 1) * n.P * sizeof(float), PACK_F32, "dyn_sp_w"});
+    if (n.dyn_sp_terms) out.push_back(PackBufferRef{n.dyn_sp_terms, (size_t)n.A * hw * 12 * sizeof(int), PACK_STATIC, "dyn_sp_terms"});
+    tower(n.dyn_res, "dyn_res");
+    tower(n.pred_res, "pred_res");
+    head(n.reward, "reward");
+    head(n.policy, "policy");
+    head(n.value, "value");
+    table(n.tw_rep, n.tb_rep, n.rep_res.size(), "rep_res");
+    table(n.tw_dyn, n.tb_dyn, n.dyn_res.size(), "dyn_res");
+    table(n.tw_pred, n.tb_pred, n.pred_res.size(), "pred_res");
 }
 
 inline hipError_t convnet_ensure_buffers(ConvNetDev& n, int B) {

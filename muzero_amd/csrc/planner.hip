@@ -88,6 +88,38 @@ static std::string fast_name(const FastKey& k, bool own_layout) {
     return b;
 }
 
+// Device reload (mz_pack.h): the bound tensors, the source maps decoded from the host packers, and the tables the gather kernels read
+struct BoundTensor {
+    const float* d;
+    std::vector<int64_t> shape;
+    size_t numel;
+};
+struct PackState {
+    std::map<std::string, BoundTensor> bound;
+    bool maps_valid = false;   // false: the next refresh derives the maps (names or shapes changed)
+    bool srcs_dirty = true;    // a bound address changed: upload the source table
+    bool table_in_flight = false;  // an upload from the pinned tables was enqueued since the stream was last drained
+    std::vector<PackTensor> tensors;  // tensor ids = the order of `bound` when the maps were derived
+    std::vector<size_t> buf_bytes;
+    std::vector<int> buf_kind;
+    PackEntry* d_map = nullptr;
+    PackChunk *d_chunks_f32 = nullptr, *d_chunks_w3 = nullptr;
+    int n_chunks_f32 = 0, n_chunks_w3 = 0;
+    PackSrc *d_srcs = nullptr, *h_srcs = nullptr;  // h_*: pinned
+    void **d_dst = nullptr, **h_dst = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    long long bytes_read = 0, bytes_written = 0;  // per refresh: entries + sources, destinations
+    void free_maps() {
+        for (void* b : {(void*)d_map, (void*)d_chunks_f32, (void*)d_chunks_w3, (void*)d_srcs, (void*)d_dst})
+            if (b) (void)hipFree(b);
+        if (h_srcs) (void)hipHostFree(h_srcs);
+        if (h_dst) (void)hipHostFree(h_dst);
+        d_map = nullptr; d_chunks_f32 = d_chunks_w3 = nullptr; d_srcs = h_srcs = nullptr; d_dst = h_dst = nullptr;
+        n_chunks_f32 = n_chunks_w3 = 0;
+        maps_valid = false;
+    }
+};
+
 struct mz_planner {
     mz_config cfg;
     int device = 0;
@@ -185,6 +217,9 @@ struct mz_planner {
     int arena_ply = 0;
     mz_planner* arena_q = nullptr;  // the borrowed opponent planner (MZ_ARENA_PLANNER)
     hipEvent_t ev_arena_pre = nullptr, ev_arena_q = nullptr;  // order the two planners' streams within a ply
+
+    // weights bound in device memory (mz_planner_bind_param_device / mz_planner_refresh_params; mz_pack.h)
+    struct PackState* pk = nullptr;
 
     // profiling
     bool profiling = false;
@@ -549,6 +584,12 @@ extern "C" int mz_planner_destroy(mz_planner* p) {
     void* cbufs[] = {p->d_pi_scratch, p->d_regions, p->d_pi0, p->d_sim_reward, p->d_sim_value, (void*)p->d_srcptrs, p->d_dstptrs, p->d_rootptrs, p->d_sim_action};
     for (void* b : cbufs)
         if (b) (void)hipFree(b);
+    if (p->pk) {
+        p->pk->free_maps();
+        if (p->pk->ev_in) (void)hipEventDestroy(p->pk->ev_in);
+        if (p->pk->ev_out) (void)hipEventDestroy(p->pk->ev_out);
+        delete p->pk;
+    }
     convnet_free(p->cnet);
     env_free(p->env);
     arena_free(p->arena);
@@ -697,6 +738,277 @@ extern "C" int mz_planner_commit_params(mz_planner* p) {
         p->fw.wact = ax ? p->d_stream[0] + stream_floats : nullptr;
     }
     p->committed = true;
+    return MZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// weights from device memory (mz_pack.h)
+// ---------------------------------------------------------------------------------------------------------
+// every packed weight buffer of the handle in a fixed order: what a commit writes, what a refresh rewrites, what mz_debug_read_packed reads
+static void packed_buffers(const mz_planner* p, std::vector<PackBufferRef>& out) {
+    out.clear();
+    if (p->conv) {
+        convnet_packed_buffers(p->cnet, out);
+        return;
+    }
+    for (int l = 0; l < L_COUNT; l++) {
+        const MlpLayer& L = p->net.L[l];
+        if (p->d_w[l]) out.push_back(PackBufferRef{p->d_w[l], (size_t)L.n_tiles * L.kg * 256 * sizeof(float), PACK_F32, std::string(kMlpNames[l]) + ".w"});
+        if (p->d_b[l]) out.push_back(PackBufferRef{p->d_b[l], (size_t)L.n_tiles * 16 * sizeof(float), PACK_F32, std::string(kMlpNames[l]) + ".b"});
+    }
+    if (p->d_bias_all) out.push_back(PackBufferRef{p->d_bias_all, (size_t)(p->o.PM - p->o.BIAS) * sizeof(float), PACK_F32, "bias_all"});
+    if (p->d_stream[0]) {
+        const bool ax = kFastAX && p->fast.ac == 10;
+        out.push_back(PackBufferRef{p->d_stream[0], (size_t)p->fw.bytes + (ax ? (size_t)p->cfg.num_actions * p->fast.planes * sizeof(float) : 0), PACK_F32,
+                                    "fast_stream"});
+    }
+}
+
+extern "C" int mz_planner_bind_param_device(mz_planner* p, const char* name, const float* d_data, const int64_t* shape, int32_t ndim) {
+    if (!p || !name || !d_data || !shape || ndim < 1 || ndim > 4) return fail(MZ_E_INVALID, "bad argument to mz_planner_bind_param_device");
+    const std::string nm(name), nbt = "num_batches_tracked";
+    if (nm.size() >= nbt.size() && nm.compare(nm.size() - nbt.size(), nbt.size(), nbt) == 0)
+        return fail(MZ_E_INVALID, nm + ": num_batches_tracked is no float32 tensor and no weight of the planner");
+    BoundTensor t;
+    t.d = d_data; t.numel = 1;
+    for (int i = 0; i < ndim; i++) {
+        if (shape[i] < 1) return fail(MZ_E_INVALID, nm + ": empty dimension");
+        t.shape.push_back(shape[i]);
+        t.numel *= (size_t)shape[i];
+    }
+    if (t.numel > PACK_MAX_NUMEL) return fail(MZ_E_INVALID, nm + ": more than 2^24 - 2 elements (use mz_planner_set_param)");
+    HIPCHK(hipSetDevice(p->device));
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, d_data) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MZ_E_INVALID, nm + ": not a device pointer");
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != p->device)
+        return fail(MZ_E_INVALID, nm + ": not device memory of the planner's GPU (device " + std::to_string(p->device) + ")");
+    {
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<float*>(d_data)) == hipSuccess) {
+            const char *lo = static_cast<const char*>(base), *q = reinterpret_cast<const char*>(d_data);
+            if (q < lo || q + t.numel * sizeof(float) > lo + size) return fail(MZ_E_INVALID, nm + ": the tensor leaves its device allocation");
+        } else {
+            (void)hipGetLastError();  // (memory the runtime reports no range for, e.g. mapped virtual ranges: the attributes above stand)
+        }
+    }
+    if ((reinterpret_cast<uintptr_t>(d_data) & 3) != 0) return fail(MZ_E_INVALID, nm + ": misaligned float32 pointer");
+    if (!p->pk) p->pk = new PackState();
+    PackState& k = *p->pk;
+    if (k.table_in_flight) {  // the pinned source table may still be read by an enqueued upload
+        HIPCHK(hipStreamSynchronize(p->stream));
+        k.table_in_flight = false;
+    }
+    auto it = k.bound.find(nm);
+    if (it == k.bound.end() || it->second.shape != t.shape) k.maps_valid = false;
+    k.srcs_dirty = true;
+    k.bound[nm] = std::move(t);
+    return MZ_OK;
+}
+
+// Once per binding: the host commit over probe tensors (mz_pack.h), read back and decoded into the gather maps.  Leaves the packed
+// buffers allocated (by that commit, sizes and all) and the handle's kernel parameters pointing at them.
+static int pack_build_maps(mz_planner* p) {
+    PackState& k = *p->pk;
+    HIPCHK(hipStreamSynchronize(p->stream));  // searches in flight read the buffers the probe commits overwrite / reallocate
+    k.table_in_flight = false;
+    k.free_maps();
+    std::vector<PackTensor>& T = k.tensors;
+    T.clear();
+    for (auto& kv : k.bound) {
+        PackTensor t;
+        t.name = kv.first; t.shape = kv.second.shape; t.numel = kv.second.numel;
+        T.push_back(std::move(t));
+    }
+    pack_assign_roles(T);
+    const float unit_var = pack_unit_var();
+    if (unit_var == 0.0f) return fail(MZ_E_INVALID, "device reload: no running_var probes the BatchNorm fold exactly");
+    std::map<std::string, HostTensor> saved = std::move(p->params);
+    p->params.clear();
+    for (const PackTensor& t : T) {
+        HostTensor h;
+        h.shape = t.shape;
+        h.data.resize(t.numel);
+        p->params[t.name] = std::move(h);
+    }
+    std::vector<PackBufferRef> bufs;
+    std::vector<std::vector<unsigned char>> img[3];
+    int rc = MZ_OK;
+    for (int pass = 0; pass < 3 && rc == MZ_OK; pass++) {
+        for (size_t i = 0; i < T.size(); i++) pack_probe_values(T[i], (int)i, pass, unit_var, p->params[T[i].name].data.data());
+        rc = mz_planner_commit_params(p);  // validates names and shapes exactly as for host tensors
+        if (rc) break;
+        packed_buffers(p, bufs);
+        if (pass == 0) {
+            k.buf_bytes.clear(); k.buf_kind.clear();
+            for (const PackBufferRef& b : bufs) { k.buf_bytes.push_back(b.bytes); k.buf_kind.push_back(b.kind); }
+        } else if (bufs.size() != k.buf_bytes.size()) {
+            rc = fail(MZ_E_INVALID, "device reload: the packed buffers changed between two commits");
+            break;
+        }
+        img[pass].resize(bufs.size());
+        for (size_t b = 0; b < bufs.size() && rc == MZ_OK; b++) {
+            size_t alloc = 0;
+            if (bufs[b].bytes != k.buf_bytes[b] || !bufs[b].d || hipMemPtrGetInfo(bufs[b].d, &alloc) != hipSuccess || alloc < bufs[b].bytes) {
+                (void)hipGetLastError();
+                rc = fail(MZ_E_INVALID, "device reload: " + bufs[b].label + " is not the size the host path allocated");
+                break;
+            }
+            img[pass][b].resize(bufs[b].bytes);
+            if (bufs[b].kind != PACK_STATIC && hipMemcpy(img[pass][b].data(), bufs[b].d, bufs[b].bytes, hipMemcpyDeviceToHost) != hipSuccess)
+                rc = fail(MZ_E_HIP, "device reload: reading " + bufs[b].label + " back failed");
+        }
+    }
+    p->params = std::move(saved);
+    p->committed = false;  // the buffers hold probe values until the refresh that called this has written them
+    if (rc) return rc;
+    std::vector<PackChunk> cf, cw;
+    std::vector<PackEntry> map, ent;
+    std::vector<size_t> buf_elems(bufs.size(), 0);
+    std::string err;
+    for (size_t b = 0; b < bufs.size(); b++) {
+        if (bufs[b].kind == PACK_STATIC) continue;
+        const bool w3 = bufs[b].kind == PACK_W3;
+        if (w3 ? bufs[b].bytes % (1536 * 2) != 0 : bufs[b].bytes % 4 != 0) return fail(MZ_E_INVALID, "device reload: odd size of " + bufs[b].label);
+        const size_t n = w3 ? bufs[b].bytes / 2 / 3 : bufs[b].bytes / 4;
+        if (n >= ((size_t)1 << 31)) return fail(MZ_E_INVALID, "device reload: " + bufs[b].label + " is too large");
+        buf_elems[b] = n;
+        ent.resize(n);
+        const bool ok = w3 ? pack_decode_w3(reinterpret_cast<const uint16_t*>(img[0][b].data()), reinterpret_cast<const uint16_t*>(img[1][b].data()),
+                                            reinterpret_cast<const uint16_t*>(img[2][b].data()), n, T, ent.data(), &err)
+                           : pack_decode_f32(reinterpret_cast<const float*>(img[0][b].data()), reinterpret_cast<const float*>(img[1][b].data()),
+                                             reinterpret_cast<const float*>(img[2][b].data()), n, T, ent.data(), &err);
+        if (!ok) return fail(MZ_E_INVALID, "device reload: cannot derive the layout of " + bufs[b].label + ": " + err);
+        pack_make_chunks((int)b, n, w3 ? PACK_CHUNK_W3 : PACK_CHUNK_F32, ent.data(), w3 ? cw : cf, map);
+    }
+    if (map.size() >= ((size_t)1 << 31)) return fail(MZ_E_INVALID, "device reload: the network is too large");
+    if (!pack_check_bounds(cf, map, T, buf_elems, &err) || !pack_check_bounds(cw, map, T, buf_elems, &err)) return fail(MZ_E_INVALID, err);
+    for (const PackChunk& c : cw)
+        if (c.n % 512 || c.off % 512) return fail(MZ_E_INVALID, "device reload: a split-bf16 chunk is no whole number of term blocks");
+    HIPCHK(hipMalloc(&k.d_map, (map.size() + 4) * sizeof(PackEntry)));
+    HIPCHK(hipMemcpy(k.d_map, map.data(), map.size() * sizeof(PackEntry), hipMemcpyHostToDevice));
+    if (!cf.empty()) {
+        HIPCHK(hipMalloc(&k.d_chunks_f32, cf.size() * sizeof(PackChunk)));
+        HIPCHK(hipMemcpy(k.d_chunks_f32, cf.data(), cf.size() * sizeof(PackChunk), hipMemcpyHostToDevice));
+    }
+    if (!cw.empty()) {
+        HIPCHK(hipMalloc(&k.d_chunks_w3, cw.size() * sizeof(PackChunk)));
+        HIPCHK(hipMemcpy(k.d_chunks_w3, cw.data(), cw.size() * sizeof(PackChunk), hipMemcpyHostToDevice));
+    }
+    k.n_chunks_f32 = (int)cf.size(); k.n_chunks_w3 = (int)cw.size();
+    HIPCHK(hipMalloc(&k.d_srcs, T.size() * sizeof(PackSrc)));
+    HIPCHK(hipMalloc(&k.d_dst, bufs.size() * sizeof(void*)));
+    HIPCHK(hipHostMalloc(&k.h_srcs, T.size() * sizeof(PackSrc)));
+    HIPCHK(hipHostMalloc(&k.h_dst, bufs.size() * sizeof(void*)));
+    for (size_t b = 0; b < bufs.size(); b++) k.h_dst[b] = nullptr;
+    if (!k.ev_in) HIPCHK(hipEventCreateWithFlags(&k.ev_in, hipEventDisableTiming));
+    if (!k.ev_out) HIPCHK(hipEventCreateWithFlags(&k.ev_out, hipEventDisableTiming));
+    k.bytes_read = (long long)(map.size() * sizeof(PackEntry));
+    k.bytes_written = 0;
+    for (const PackEntry& e : map)
+        if (e.tid >= 0) k.bytes_read += 4;
+    for (size_t b = 0; b < bufs.size(); b++)
+        if (bufs[b].kind != PACK_STATIC) k.bytes_written += (long long)bufs[b].bytes;
+    k.srcs_dirty = true;
+    k.maps_valid = true;
+    return MZ_OK;
+}
+
+extern "C" int mz_planner_refresh_params(mz_planner* p, void* producer_stream) {
+    if (!p) return fail(MZ_E_INVALID, "null planner");
+    if (!p->pk || p->pk->bound.empty()) return fail(MZ_E_STATE, "no tensor bound: call mz_planner_bind_param_device for every tensor first");
+    HIPCHK(hipSetDevice(p->device));
+    PackState& k = *p->pk;
+    std::vector<PackBufferRef> bufs;
+    if (k.maps_valid) {  // a failed host commit may have released the buffers
+        packed_buffers(p, bufs);
+        if (bufs.size() != k.buf_bytes.size()) k.maps_valid = false;
+    }
+    if (!k.maps_valid) {
+        const int rc = pack_build_maps(p);
+        if (rc) return rc;
+        packed_buffers(p, bufs);
+    }
+    for (size_t b = 0; b < bufs.size(); b++)
+        if (!bufs[b].d || bufs[b].bytes != k.buf_bytes[b] || bufs[b].kind != k.buf_kind[b])
+            return fail(MZ_E_STATE, "device reload: " + bufs[b].label + " changed since the tensors were bound");
+    hipStream_t producer = static_cast<hipStream_t>(producer_stream);
+    // a host commit of a conv net reallocates (after draining the stream): follow the buffers
+    bool moved = false;
+    for (size_t b = 0; b < bufs.size(); b++) moved = moved || k.h_dst[b] != bufs[b].d;
+    if (moved) {
+        for (size_t b = 0; b < bufs.size(); b++) k.h_dst[b] = bufs[b].d;
+        HIPCHK(hipMemcpyAsync(k.d_dst, k.h_dst, bufs.size() * sizeof(void*), hipMemcpyHostToDevice, p->stream));
+        k.table_in_flight = true;
+    }
+    if (k.srcs_dirty) {
+        const std::vector<PackTensor>& T = k.tensors;
+        for (size_t i = 0; i < T.size(); i++) {
+            auto ptr = [&](int id) { return id >= 0 ? k.bound.find(T[id].name)->second.d : nullptr; };
+            PackSrc s{};
+            s.p = ptr((int)i);
+            s.kind = T[i].fold_kind < 0 ? 0 : T[i].fold_kind;
+            s.inner = 1;
+            if (s.kind == 1) {
+                const PackTensor& g = T[T[i].fold_gamma];
+                s.gamma = ptr(g.gamma); s.mean = ptr(g.mean); s.var = ptr(g.var);
+                s.inner = (int)(T[i].numel / (size_t)T[i].shape[0]);
+            } else if (s.kind == 2) {
+                s.gamma = ptr(T[i].gamma); s.mean = ptr(T[i].mean); s.var = ptr(T[i].var);
+            }
+            k.h_srcs[i] = s;
+        }
+        HIPCHK(hipMemcpyAsync(k.d_srcs, k.h_srcs, T.size() * sizeof(PackSrc), hipMemcpyHostToDevice, p->stream));
+        k.table_in_flight = true;
+        k.srcs_dirty = false;
+    }
+    // the producer's writes before this call -> the pack kernels -> the producer's next writes; searches already enqueued on the planner's
+    // stream finish on the old weights by stream order.  No host synchronisation.
+    HIPCHK(hipEventRecord(k.ev_in, producer));
+    HIPCHK(hipStreamWaitEvent(p->stream, k.ev_in, 0));
+    if (k.n_chunks_f32) hipLaunchKernelGGL(k_pack_f32, dim3(k.n_chunks_f32), dim3(256), 0, p->stream, k.d_chunks_f32, k.d_map, k.d_srcs, k.d_dst);
+    if (k.n_chunks_w3) hipLaunchKernelGGL(k_pack_w3, dim3(k.n_chunks_w3), dim3(256), 0, p->stream, k.d_chunks_w3, k.d_map, k.d_srcs, k.d_dst);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(k.ev_out, p->stream));
+    HIPCHK(hipStreamWaitEvent(producer, k.ev_out, 0));
+    p->committed = true;
+    return MZ_OK;
+}
+
+// test hooks, not part of the ABI header.  mz_debug_read_packed: packed weight buffer `index` of the handle (per-layer weights and biases,
+// bias block, fast stream; conv w / b / w3, tails, heads, tower tables), copied to h_out (NULL: only its size and name); MZ_E_INVALID past
+// the last buffer.  mz_debug_packed_info: [0] the buffer's device address, [1] pack kernels per refresh, [2] bytes a refresh reads
+// (entries + sources), [3] bytes it writes.
+extern "C" int mz_debug_read_packed(mz_planner* p, int32_t index, void* h_out, int64_t* bytes, const char** label) {
+    if (!p) return fail(MZ_E_INVALID, "null planner");
+    static thread_local std::string g_label;
+    std::vector<PackBufferRef> bufs;
+    packed_buffers(p, bufs);
+    if (index < 0 || (size_t)index >= bufs.size()) return fail(MZ_E_INVALID, "no packed buffer " + std::to_string(index));
+    if (bytes) *bytes = (int64_t)bufs[index].bytes;
+    g_label = bufs[index].label;
+    if (label) *label = g_label.c_str();
+    if (h_out) {
+        HIPCHK(hipSetDevice(p->device));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        HIPCHK(hipMemcpy(h_out, bufs[index].d, bufs[index].bytes, hipMemcpyDeviceToHost));
+    }
+    return MZ_OK;
+}
+
+extern "C" int mz_debug_packed_info(mz_planner* p, int32_t index, int64_t out[4]) {
+    if (!p || !out) return fail(MZ_E_INVALID, "null argument");
+    std::vector<PackBufferRef> bufs;
+    packed_buffers(p, bufs);
+    if (index < 0 || (size_t)index >= bufs.size()) return fail(MZ_E_INVALID, "no packed buffer " + std::to_string(index));
+    out[0] = (int64_t)reinterpret_cast<uintptr_t>(bufs[index].d);
+    const PackState* k = p->pk;
+    out[1] = k ? (k->n_chunks_f32 > 0) + (k->n_chunks_w3 > 0) : 0;
+    out[2] = k ? k->bytes_read : 0;
+    out[3] = k ? k->bytes_written : 0;
     return MZ_OK;
 }
 

@@ -263,6 +263,13 @@ class HipLearner:
         self.network = network
         self.commit()
 
+    def planner_weights(self):
+        """The network's weights as a planner binds them (`planner.Planner.bind_device_weights` / `reload`): the parameter views and the
+        BatchNorm running statistics, views of the learner's flat vectors -- stable device addresses the kernels of `apply()` write."""
+        out = dict(self.views)
+        out.update({k: v for k, v in self.buffer_views.items() if not k.endswith('num_batches_tracked')})
+        return out
+
     def _param_versions(self):
         return tuple(p._version for p in self.network.parameters())
 

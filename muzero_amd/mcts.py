@@ -284,7 +284,7 @@ def _planner_for(network, config, num_envs, device):
         entry = [pl, None]
         cache[key] = entry
     if entry[1] != version:
-        entry[0].load_state_dict(network.state_dict())
+        entry[0].reload(network.state_dict())  # (planner.Planner.reload: packed on the GPU when the module lives there)
         entry[1] = version
     return entry[0]
 

@@ -266,7 +266,7 @@ class MuZeroNet(nn.Module):
         if self._engine is None or self._engine_version != ver:
             if self._engine is None:
                 self._engine = _planner.InferenceEngine(self.planner_spec(), device=device)
-            self._engine.load_state_dict(self.state_dict())
+            self._engine.reload(self.state_dict())  # in place on the GPU where the tensors allow it, through the host otherwise
             self._engine_version = ver
         return self._engine
 

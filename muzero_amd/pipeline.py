@@ -310,7 +310,7 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     num_envs = int(getattr(config, 'num_envs', 1))
     idx = device.index if getattr(device, 'index', None) is not None else 0
     p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx)
-    p.load_state_dict(network.state_dict())
+    p.reload(network.state_dict())
     from muzero_amd.replay import PrioritizedReplay
 
     on_device = isinstance(data_queue, PrioritizedReplay)
@@ -327,7 +327,7 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     while not stop_event.is_set() and (max_moves is None or played < max_moves):
         key = weights_key(network)  # read BEFORE copying: a publish that lands during the copy makes the next check fire again
         if key != version:  # learner pushed new weights (pipeline.py:266)
-            p.load_state_dict(network.state_dict())
+            p.reload(network.state_dict())
             version = key
         n = moves_per_drain if max_moves is None else min(moves_per_drain, max_moves - played)
         # classic/atari schedules depend on train steps only; board games on the env's own step count (config.py:236-267)
@@ -370,7 +370,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
 
     idx = device.index if getattr(device, 'index', None) is not None else 0
     p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=B, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx)
-    p.load_state_dict(network.state_dict())
+    p.reload(network.state_dict())
     on_device = isinstance(data_queue, PrioritizedReplay)
     obs_shape = getattr(network, 'input_shape', None)
     if on_device:
@@ -406,7 +406,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
         while not stop_event.is_set() and (max_moves is None or played < max_moves):
             key = weights_key(network)
             if key != version:  # learner pushed new weights (pipeline.py:266)
-                p.load_state_dict(network.state_dict())
+                p.reload(network.state_dict())
                 version = key
             T = -1.0 if board else float(config.visit_softmax_temperature_fn(0, train_steps_counter.value))
             mask = np.stack([np.asarray(m, np.uint8).reshape(-1) for m in (getattr(e, 'actions_mask', None) for e in envs)]) \
@@ -558,10 +558,10 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729), idx)
     q = None
     try:
-        p.load_state_dict(challenger_network.state_dict())
+        p.reload(challenger_network.state_dict())
         if is_net:
             q = pl.Planner(pl.make_mz_config(opponent.planner_spec(), config, num_envs=num_games, seed=seed + 130003), idx)
-            q.load_state_dict(opponent.state_dict())
+            q.reload(opponent.state_dict())
         p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
         cap = 500 if not two else p.A - 1  # the env's own cap: CartPole's TimeLimit, a board's point count
         res = p.arena_result()

@@ -21,6 +21,7 @@ ARENA_UNFINISHED, ARENA_WIN_CHALLENGER, ARENA_WIN_OPPONENT, ARENA_DRAW = 0, 1, 2
 # every symbol include/mzplanner.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
     'mz_last_error', 'mz_version', 'mz_planner_describe', 'mz_planner_create', 'mz_planner_destroy', 'mz_planner_set_param', 'mz_planner_commit_params',
+    'mz_planner_bind_param_device', 'mz_planner_refresh_params',
     'mz_planner_initial_inference', 'mz_planner_recurrent_inference', 'mz_planner_hidden_size', 'mz_planner_search',
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
@@ -83,6 +84,10 @@ def load_library():
     L.mz_planner_destroy.argtypes = [vp]
     L.mz_planner_set_param.argtypes = [vp, C.c_char_p, vp, i64p, i32]
     L.mz_planner_commit_params.argtypes = [vp]
+    L.mz_planner_bind_param_device.argtypes = [vp, C.c_char_p, vp, i64p, i32]
+    L.mz_planner_refresh_params.argtypes = [vp, vp]
+    L.mz_debug_read_packed.argtypes = [vp, i32, vp, i64p, C.POINTER(C.c_char_p)]
+    L.mz_debug_packed_info.argtypes = [vp, i32, i64p]
     L.mz_planner_initial_inference.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mz_planner_recurrent_inference.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.mz_planner_hidden_size.argtypes = [vp]
@@ -153,6 +158,48 @@ def make_mz_config(spec, config=None, num_envs=1, max_ties=0, seed=1, **search_o
     )
 
 
+def _is_tensor(t):
+    import torch
+
+    return isinstance(t, torch.Tensor)
+
+
+def device_weights(state_dict, device_index, expect=None):
+    """The tensors of `state_dict` a planner on GPU `device_index` can bind in place (`Planner.bind_device_weights`): every entry except
+    `num_batches_tracked` must be a contiguous float32 CUDA tensor on that GPU; `expect`: keys that must be there (`num_batches_tracked`
+    aside).  Returns {key: tensor}; raises ValueError naming the first key that does not qualify.  Pure: touches no GPU."""
+    import torch
+
+    out = {}
+    for name, t in state_dict.items():
+        if name.endswith('num_batches_tracked'):
+            continue
+        if not _is_tensor(t):
+            raise ValueError(f'{name}: not a torch tensor ({type(t).__name__})')
+        if t.device.type != 'cuda':
+            raise ValueError(f'{name}: on {t.device}, not on the planner\'s GPU (cuda:{device_index})')
+        if t.device.index is not None and t.device.index != device_index:
+            raise ValueError(f'{name}: on {t.device}, the planner is on cuda:{device_index}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{name}: {t.dtype}, the planner binds float32')
+        if not t.is_contiguous():
+            raise ValueError(f'{name}: not contiguous')
+        out[name] = t.detach()
+    for name in expect or ():
+        if not name.endswith('num_batches_tracked') and name not in out:
+            raise ValueError(f'{name}: missing from the state_dict')
+    return out
+
+
+def can_bind(state_dict, device_index):
+    """Whether `device_weights` accepts `state_dict` (the owners of a planner fall back to `load_state_dict` otherwise)."""
+    try:
+        device_weights(state_dict, device_index)
+        return True
+    except ValueError:
+        return False
+
+
 class Planner:
     """One planner handle on one GPU (mz_planner*)."""
 
@@ -162,6 +209,7 @@ class Planner:
         h = C.c_void_p()
         _chk(self.lib.mz_planner_create(C.byref(mz_config), int(device_id), C.byref(h)))
         self.h = h
+        self.device_id = int(device_id)
         self.A = mz_config.num_actions
         self.S = mz_config.num_simulations
         self.B = mz_config.num_envs
@@ -187,6 +235,9 @@ class Planner:
 
     # ---- weights ----
     def load_state_dict(self, state_dict):
+        if getattr(self, '_refreshed', False):  # pack kernels of a refresh may still be writing the buffers this commit fills
+            self.synchronize()
+            self._refreshed = False
         for name, t in state_dict.items():
             if name.endswith('num_batches_tracked'):
                 continue
@@ -194,6 +245,63 @@ class Planner:
             shape = (C.c_int64 * max(a.ndim, 1))(*(a.shape if a.ndim else (1,)))
             _chk(self.lib.mz_planner_set_param(self.h, name.encode(), _p(a), shape, max(a.ndim, 1)))
         _chk(self.lib.mz_planner_commit_params(self.h))
+
+    def bind_device_weights(self, state_dict):
+        """Bind `state_dict`'s tensors where they are, in this planner's GPU memory (mz_planner_bind_param_device): contiguous float32 CUDA
+        tensors, e.g. `HipLearner.planner_weights()` or a module's `state_dict()`.  Nothing is copied: the planner keeps references and
+        `refresh_weights` reads them.  `num_batches_tracked` is skipped; anything else that cannot be bound raises ValueError with its key."""
+        w = device_weights(state_dict, self.device_id)
+        for name, t in w.items():
+            shape = (C.c_int64 * max(t.dim(), 1))(*(tuple(t.shape) if t.dim() else (1,)))
+            _chk(self.lib.mz_planner_bind_param_device(self.h, name.encode(), C.c_void_p(t.data_ptr()), shape, max(t.dim(), 1)))
+        self._bound = w
+        self._bound_ptrs = {k: t.data_ptr() for k, t in w.items()}
+
+    def refresh_weights(self, stream=None):
+        """Repack the bound tensors into the planner's operand copies on the GPU (mz_planner_refresh_params), ordered after the work
+        `stream` holds now and before its later work; `stream`: a torch.cuda.Stream, default torch's current stream on this GPU.  No host
+        synchronisation (but see the first refresh of a binding, include/mzplanner.h)."""
+        import torch
+
+        if not getattr(self, '_bound', None):
+            raise PlannerError('refresh_weights: bind_device_weights first')
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device_id)
+        _chk(self.lib.mz_planner_refresh_params(self.h, C.c_void_p(int(stream.cuda_stream))))
+        self._refreshed = True
+
+    def reload(self, state_dict, stream=None, host=False):
+        """Hand `state_dict` to the planner the cheapest way it allows: bound in place and refreshed on the GPU when every tensor is a
+        contiguous float32 tensor on this GPU (binding again only if an address or the key set changed), through the host
+        (`load_state_dict`) otherwise or with `host=True`.  Returns 'device' or 'host'."""
+        if not host and can_bind(state_dict, self.device_id):
+            ptrs = {k: t.data_ptr() for k, t in state_dict.items() if not k.endswith('num_batches_tracked')}
+            if ptrs != getattr(self, '_bound_ptrs', None):
+                self.bind_device_weights(state_dict)
+            self.refresh_weights(stream)
+            return 'device'
+        self.load_state_dict(state_dict)
+        return 'host'
+
+    def read_packed(self):
+        """Test hook (mz_debug_read_packed): every packed weight buffer of the handle as [(label, device address, bytes)]."""
+        out, i = [], 0
+        while True:
+            n, label, info = C.c_int64(), C.c_char_p(), (C.c_int64 * 4)()
+            if self.lib.mz_debug_read_packed(self.h, i, None, C.byref(n), C.byref(label)) != 0:
+                return out
+            name = label.value.decode()
+            buf = np.empty(n.value, np.uint8)
+            _chk(self.lib.mz_debug_read_packed(self.h, i, _p(buf), None, None))
+            _chk(self.lib.mz_debug_packed_info(self.h, i, info))
+            out.append((name, int(info[0]), buf.tobytes()))
+            i += 1
+
+    def pack_stats(self):
+        """Test / measurement hook: dict(launches, bytes_read, bytes_written) of one refresh."""
+        info = (C.c_int64 * 4)()
+        _chk(self.lib.mz_debug_packed_info(self.h, 0, info))
+        return dict(launches=int(info[1]), bytes_read=int(info[2]), bytes_written=int(info[3]))
 
     # ---- inference (network.py:62-111) ----
     def initial_inference(self, obs):
@@ -451,6 +559,9 @@ class InferenceEngine:
 
     def load_state_dict(self, sd):
         self.planner.load_state_dict(sd)
+
+    def reload(self, sd):
+        return self.planner.reload(sd)
 
     def initial_inference(self, obs):
         return self.planner.initial_inference(obs)
