@@ -1012,6 +1012,85 @@ extern "C" int mz_debug_packed_info(mz_planner* p, int32_t index, int64_t out[4]
     return MZ_OK;
 }
 
+// mz_debug_conv3x3: ONE 3x3 stride-1 conv layer through the production code -- build_conv (no BatchNorm: the commit's f32 and w3 packers on
+// h_weight [cout][cin][3][3]) in a temporary ConvNetDev whose `split` is the handle's conv_precision, h_bias (NULL: zeros) over the layer's
+// bias buffer, conv_run on the handle's stream: the build split_geometry / conv_geometry pick for the planner.  h_in [batch][cin_real][h][w];
+// h_rows: image b is row h_rows[b] of h_in, launched through per-image pointers (the search's node-store gather); h_action: channels
+// cin_real .. cin - 1 are the action planes of a num_actions-action net; h_residual / h_out [batch][cout][h][w].  *build_name: the build that
+// ran.  Everything lives in allocations of this call: the handle's weights and buffers are not touched.
+extern "C" int mz_debug_conv3x3(mz_planner* p, int32_t batch, int32_t cin_real, int32_t cin, int32_t cout, int32_t h, int32_t w, const float* h_weight,
+                                const float* h_bias, const float* h_in, const int32_t* h_rows, const int32_t* h_action, int32_t num_actions,
+                                const float* h_residual, int32_t relu, float* h_out, const char** build_name) {
+    if (!p || !h_weight || !h_in || !h_out) return fail(MZ_E_INVALID, "null argument to mz_debug_conv3x3");
+    if (!p->conv) return fail(MZ_E_INVALID, "mz_debug_conv3x3 needs a conv net: MZ_NET_MLP has no convolutions");
+    if (batch < 1 || batch > 4096) return fail(MZ_E_INVALID, "mz_debug_conv3x3: batch must be in [1, 4096]");
+    if (cin_real < 1 || cin_real > cin || cin > 1024 || cout < 1 || cout > 512) return fail(MZ_E_INVALID, "mz_debug_conv3x3: 1 <= cin_real <= cin <= 1024, 1 <= cout <= 512");
+    if (h < 3 || h > 19 || w < 3 || w > 19) return fail(MZ_E_INVALID, "mz_debug_conv3x3: h and w must be in [3, 19]");
+    if (h_action ? num_actions < 1 : cin != cin_real) return fail(MZ_E_INVALID, "mz_debug_conv3x3: channels past cin_real need h_action and num_actions >= 1");
+    for (int b = 0; b < batch; b++) {
+        if (h_rows && (h_rows[b] < 0 || h_rows[b] >= batch)) return fail(MZ_E_INVALID, "mz_debug_conv3x3: h_rows out of range");
+        if (h_action && (h_action[b] < 0 || h_action[b] >= num_actions)) return fail(MZ_E_INVALID, "mz_debug_conv3x3: h_action out of range");
+    }
+    HIPCHK(hipSetDevice(p->device));
+    struct Scratch {  // every device allocation of the call, the layer's included
+        ConvNetDev n;
+        ~Scratch() {
+            for (void* b : n.allocs) (void)hipFree(b);
+        }
+        hipError_t alloc(void** d, size_t bytes) {
+            hipError_t e = hipMalloc(d, bytes + 256);  // + slack: the f32 kernels read the last pixel quad of a channel as 16 bytes
+            if (e != hipSuccess) return e;
+            n.allocs.push_back(*d);
+            return hipMemset(*d, 0, bytes + 256);
+        }
+    } s;
+    s.n.kind = MZ_NET_BOARD;
+    s.n.split = p->cnet.split;
+    ParamMap pm;
+    pm["w"] = HostTensorRef{h_weight, {cout, cin, 3, 3}};
+    ConvLayerDev layer;
+    std::string err;
+    const int rc = build_conv(s.n, pm, "w", "", cin, cin_real, cout, 3, 1, &layer, &err);
+    if (rc) return fail(rc == -2 ? MZ_E_HIP : MZ_E_INVALID, "mz_debug_conv3x3: " + err);
+    const size_t hw = (size_t)h * w, in_floats = (size_t)batch * cin_real * hw, out_floats = (size_t)batch * cout * hw;
+    float *d_in = nullptr, *d_res = nullptr, *d_out = nullptr;
+    const float** d_ptrs = nullptr;
+    int* d_act = nullptr;
+    HIPCHK(s.alloc(reinterpret_cast<void**>(&d_in), in_floats * sizeof(float)));
+    HIPCHK(s.alloc(reinterpret_cast<void**>(&d_out), out_floats * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());  // (the memsets above run on the null stream)
+    if (h_bias) HIPCHK(hipMemcpyAsync(layer.b, h_bias, (size_t)cout * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(d_in, h_in, in_floats * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    std::vector<const float*> ptrs;  // (alive until the stream is drained)
+    if (h_rows) {
+        for (int b = 0; b < batch; b++) ptrs.push_back(d_in + (size_t)h_rows[b] * cin_real * hw);
+        HIPCHK(s.alloc(reinterpret_cast<void**>(&d_ptrs), (size_t)batch * sizeof(float*)));
+        HIPCHK(hipMemcpyAsync(d_ptrs, ptrs.data(), (size_t)batch * sizeof(float*), hipMemcpyHostToDevice, p->stream));
+    }
+    if (h_action) {
+        HIPCHK(s.alloc(reinterpret_cast<void**>(&d_act), (size_t)batch * sizeof(int)));
+        HIPCHK(hipMemcpyAsync(d_act, h_action, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    }
+    if (h_residual) {
+        HIPCHK(s.alloc(reinterpret_cast<void**>(&d_res), out_floats * sizeof(float)));
+        HIPCHK(hipMemcpyAsync(d_res, h_residual, out_floats * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    }
+    static thread_local std::string g_build;
+    if (layer.w3) {
+        g_build = split_geometry(h, w, cout).name;
+    } else {
+        const ConvGeom g = conv_geometry(batch, h, w, 1, cout, true);
+        g_build = "k_conv3x3 f32: " + std::to_string(g.th) + " x " + std::to_string(g.tw) + " tiles, G=" + std::to_string(g.G) + ", NPT=" + std::to_string(g.npt) +
+                  ", NCT=" + std::to_string(g.nct) + (g.whole ? " (whole image)" : " (tiled)");
+    }
+    if (build_name) *build_name = g_build.c_str();
+    conv_run(p->stream, layer, batch, h_rows ? nullptr : d_in, d_ptrs, d_act, h_action ? num_actions : 0, h, w, d_res, d_out, relu != 0, d_in, in_floats);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out, d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // inference API
 // ---------------------------------------------------------------------------------------------------------

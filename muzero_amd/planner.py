@@ -88,6 +88,7 @@ def load_library():
     L.mz_planner_refresh_params.argtypes = [vp, vp]
     L.mz_debug_read_packed.argtypes = [vp, i32, vp, i64p, C.POINTER(C.c_char_p)]
     L.mz_debug_packed_info.argtypes = [vp, i32, i64p]
+    L.mz_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, C.POINTER(C.c_char_p)]
     L.mz_planner_initial_inference.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mz_planner_recurrent_inference.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.mz_planner_hidden_size.argtypes = [vp]
@@ -296,6 +297,26 @@ class Planner:
             _chk(self.lib.mz_debug_packed_info(self.h, i, info))
             out.append((name, int(info[0]), buf.tobytes()))
             i += 1
+
+    def debug_conv3x3(self, x, weight, bias=None, rows=None, action=None, num_actions=0, cin=None, residual=None, relu=False):
+        """Test hook (mz_debug_conv3x3): one 3x3 stride-1 conv layer through the planner's own packers and launcher, in this handle's
+        conv_precision.  x [B, cin_real, h, w], weight [cout, cin, 3, 3], bias [cout]; rows [B]: image b is x[rows[b]], read through
+        per-image pointers; action [B]: channels cin_real .. cin - 1 are the action planes of a num_actions-action net; residual
+        [B, cout, h, w].  Returns (out [B, cout, h, w] float32, name of the kernel build that ran)."""
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        x, weight, bias, residual, rows, action = f32(x), f32(weight), f32(bias), f32(residual), i32(rows), i32(action)
+        B, cin_real, h, w = x.shape
+        cout = weight.shape[0]
+        cin = cin_real if cin is None else int(cin)
+        if weight.shape != (cout, cin, 3, 3) or (bias is not None and bias.shape != (cout,)) or \
+                (residual is not None and residual.shape != (B, cout, h, w)) or (rows is not None and rows.shape != (B,)) or \
+                (action is not None and action.shape != (B,)):
+            raise ValueError('debug_conv3x3: mis-shaped argument')
+        out, name = np.empty((B, cout, h, w), np.float32), C.c_char_p()
+        _chk(self.lib.mz_debug_conv3x3(self.h, B, cin_real, cin, cout, h, w, _p(weight), _p(bias), _p(x), _p(rows), _p(action), int(num_actions),
+                                       _p(residual), int(bool(relu)), _p(out), C.byref(name)))
+        return out, name.value.decode()
 
     def pack_stats(self):
         """Test / measurement hook: dict(launches, bytes_read, bytes_written) of one refresh."""

@@ -21,7 +21,7 @@ def test_entry_points_are_declared_listed_and_exported():
         assert re.search(r'\b%s\s*\(' % name, text), f'{name} is not declared in include/mzplanner.h'
         assert name in planner.ABI_SYMBOLS
         assert hasattr(lib, name), f'{name} is not exported'
-    for hook in ('mz_debug_read_packed', 'mz_debug_packed_info'):  # test hooks: exported, not part of the header
+    for hook in ('mz_debug_read_packed', 'mz_debug_packed_info', 'mz_debug_conv3x3'):  # test hooks: exported, not part of the header
         assert hasattr(lib, hook) and hook not in text
 
 
