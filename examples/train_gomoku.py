@@ -64,7 +64,10 @@ def main():
     ap.add_argument('--host-reload', action='store_true',
                     help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--conv-precision', choices=['f32', 'bf16x3'], default='f32',
-                    help="the planner's conv arithmetic (mz_config.conv_precision): f32 is bit-equal to the oracle, bf16x3 the split-bf16 path; the learner stays float32")
+                    help="the planner's conv arithmetic (mz_config.conv_precision): f32 is bit-equal to the oracle, bf16x3 the split-bf16 path; the learner has its own switch, --learner-conv-precision")
+    ap.add_argument('--learner-conv-precision', choices=['f32', 'bf16x3'], default='f32',
+                    help="the HIP learner's conv arithmetic (mzl_config.conv_precision): bf16x3 runs the towers' forward and data-gradient convs as split-bf16 MFMAs; "
+                         "the weight gradient, BatchNorm, the heads and Adam stay float32 either way")
     ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
                     help='also play N games (even) against the random opponent as one lock-step batch on the device (pipeline.play_match); 0: off')
     args = ap.parse_args()
@@ -95,7 +98,7 @@ def main():
         opt = learner.make_capturable_adam(net, cfg, dev)
         graphed = learner.prepare_graphed_step(cfg, net, opt, dev, obs_shape, A)
     elif use_hip:  # the conv learner's kernels; the module's parameters and BatchNorm buffers become views of the learner's flat vectors
-        hip = learner.make_hip_learner(cfg, net, dev)
+        hip = learner.make_hip_learner(cfg, net, dev, conv_precision=args.learner_conv_precision)
         opt = None
     else:
         opt = torch.optim.Adam(net.parameters(), lr=cfg.lr_init, weight_decay=cfg.weight_decay)

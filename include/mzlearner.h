@@ -31,6 +31,12 @@ extern "C" {
 #define MZL_NET_BOARD 1  /* MuZeroBoardGameNet (network.py:540-574); kernels: muzero_amd/csrc/mz_learn_conv.h */
 #define MZL_NET_ATARI 2  /* MuZeroAtariNet (network.py:501-537): the same kernels; the 96 x 96 representation (network.py:312-353) on 12 x 12 / 12 x 16 tiles */
 
+#define MZL_CONV_F32 0     /* the conv nets' 3x3 convs on the f32-input MFMA (default) */
+#define MZL_CONV_BF16X3 1  /* MZL_NET_BOARD only: the towers' forward and data-gradient convs as split-bf16 MFMAs -- every float32 operand the exact sum of
+                            * three bf16 values, six products per step accumulated in float32 (muzero_amd/csrc/mz_learn_conv_split.h).  Staging transforms,
+                            * saved tensors, masks, BatchNorm, the weight gradient, the heads and Adam stay float32.  Float32-grade, not bit-equal to
+                            * MZL_CONV_F32. */
+
 /* The network's constructor arguments (MuZeroMLPNet network.py:239-247 | MuZeroBoardGameNet :543-549) + the batch geometry of calc_loss
  * (pipeline.py:541-575). */
 typedef struct {
@@ -48,6 +54,7 @@ typedef struct {
     int32_t in_channels;          /* planes of the observation (network.py:549 / :508 input_shape[0]) */
     int32_t board_h, board_w;     /* MZL_NET_BOARD: the board, board_h * board_w <= 240; MZL_NET_ATARI: the frame, 96 x 96 (hidden state 6 x 6) */
     int32_t num_res_blocks;       /* residual blocks of each of the three towers (network.py:546) */
+    int32_t conv_precision;       /* MZL_CONV_F32 (0: a zero-initialised config) | MZL_CONV_BF16X3 (MZL_NET_BOARD only; mzl_create refuses it for the other nets) */
 } mzl_config;
 
 /* One batch of `Transition`s (replay.py:27-32) addressed inside the replay ring's storages. */

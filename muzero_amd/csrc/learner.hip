@@ -163,6 +163,15 @@ extern "C" int mzl_create(const mzl_config* cfg, int device_id, mz_learner** out
     if (!cfg || !out) return fail(MZL_E_INVALID, "null argument");
     if (cfg->net_kind != MZL_NET_MLP && cfg->net_kind != MZL_NET_BOARD && cfg->net_kind != MZL_NET_ATARI)
         return fail(MZL_E_INVALID, "net_kind must be MZL_NET_MLP, MZL_NET_BOARD or MZL_NET_ATARI");
+    {
+        const std::string kind = cfg->net_kind == MZL_NET_MLP ? "MZL_NET_MLP" : (cfg->net_kind == MZL_NET_BOARD ? "MZL_NET_BOARD" : "MZL_NET_ATARI");
+        if (cfg->conv_precision != MZL_CONV_F32 && cfg->conv_precision != MZL_CONV_BF16X3)
+            return fail(MZL_E_INVALID, "conv_precision must be MZL_CONV_F32 (0) or MZL_CONV_BF16X3 (1), not " + std::to_string(cfg->conv_precision) + " (net_kind " + kind + ")");
+        if (cfg->conv_precision == MZL_CONV_BF16X3 && cfg->net_kind == MZL_NET_MLP)
+            return fail(MZL_E_INVALID, "conv_precision MZL_CONV_BF16X3 needs net_kind MZL_NET_BOARD: " + kind + " has no convolutions");
+        if (cfg->conv_precision == MZL_CONV_BF16X3 && cfg->net_kind == MZL_NET_ATARI)
+            return fail(MZL_E_INVALID, "conv_precision MZL_CONV_BF16X3 needs net_kind MZL_NET_BOARD: the tap-set, tile and plane convs of " + kind + " have no split-bf16 build");
+    }
     if (cfg->net_kind != MZL_NET_MLP) {
         if (cfg->in_dim < 1 || cfg->num_actions < 1 || cfg->num_actions > 32767 || cfg->num_planes < 1 || cfg->unroll_steps < 1 || cfg->unroll_steps > 32 ||
             cfg->max_batch < 1)
@@ -353,6 +362,16 @@ extern "C" int mzl_bind_buffers(mz_learner* h, float* d_running, int64_t* d_num_
 extern "C" int mzl_debug_tensor(const mz_learner* h, const char* what, int a, int b, void** ptr, int64_t* count) {
     if (!h || !h->conv || !what || !ptr || !count || mzlc_debug_tensor(h->conv, what, a, b, ptr, count) != MZL_OK) return fail(MZL_E_INVALID, "no such tensor");
     return MZL_OK;
+}
+
+// diagnostic (tests): ONE 3x3 conv through the conv learner's packers, tiling chooser and dispatcher at the handle's conv_precision
+// (learner_conv.hip mzlc_debug_conv); host pointers
+extern "C" int mzl_debug_conv(mz_learner* h, int32_t direction, int32_t batch, int32_t cin_real, int32_t cin, int32_t cout, int32_t bh, int32_t bw,
+                              const float* h_weight, const float* h_in, const int32_t* h_action, int32_t num_actions, float* h_out, const char** build_name) {
+    if (!h || !h->conv) return fail(MZL_E_INVALID, "mzl_debug_conv: needs a conv-net learner (MZL_NET_BOARD)");
+    std::string err;
+    const int rc = mzlc_debug_conv(h->conv, direction, batch, cin_real, cin, cout, bh, bw, h_weight, h_in, h_action, num_actions, h_out, build_name, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv: " + err);
 }
 
 extern "C" int mzl_tensor_info(const mz_learner* h, int32_t i, const char** name, int64_t* offset, int32_t* rows, int32_t* cols) {

@@ -22,6 +22,7 @@
 //   image per workgroup.  The epilogue computes k_conv3x3's function (bias in the accumulator, + residual, ReLU) in float32.
 #pragma once
 #include "mz_conv.h"
+#include "mz_split3.h"
 
 namespace mz {
 
@@ -44,16 +45,7 @@ struct SplitConvLaunch {
     int B;
 };
 
-__host__ __device__ __forceinline__ unsigned conv_bf16_rne(unsigned u) { return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; }
-
-// x = h + m + l exactly (finite x): bf16 bit patterns of the three terms
-__device__ __forceinline__ void conv_split3(float x, unsigned& h, unsigned& m, unsigned& l) {
-    h = conv_bf16_rne(__float_as_uint(x));
-    const float r1 = x - __uint_as_float(h << 16);
-    m = conv_bf16_rne(__float_as_uint(r1));
-    const float r2 = r1 - __uint_as_float(m << 16);
-    l = conv_bf16_rne(__float_as_uint(r2));
-}
+// conv_bf16_rne / conv_split3 (x = h + m + l exactly): mz_split3.h, shared with the learner's split conv
 
 constexpr int split_npos_pad(int npos) { return (npos + 15) & ~15; }
 

@@ -24,3 +24,5 @@ int mzlc_grad(mzlc_learner* h, const mzl_batch* b, void* stream, std::string& er
 int mzlc_apply(mzlc_learner* h, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm, int64_t step, void* stream,
                std::string& err);
 int mzlc_debug_tensor(const mzlc_learner* h, const char* what, int a, int b, void** ptr, int64_t* count);
+int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int cin, int cout, int bh, int bw, const float* h_weight, const float* h_in,
+                    const int32_t* h_action, int num_actions, float* h_out, const char** build_name, std::string& err);

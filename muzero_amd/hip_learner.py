@@ -22,17 +22,26 @@ ABI_SYMBOLS = ['mzl_last_error', 'mzl_create', 'mzl_destroy', 'mzl_num_params', 
                'mzl_num_buffers', 'mzl_num_running', 'mzl_buffer_info', 'mzl_bind_buffers', 'mzl_bind', 'mzl_commit', 'mzl_grad', 'mzl_apply',
                'mzl_replay_scratch_doubles', 'mzl_replay_sample', 'mzl_replay_update_priorities', 'mzl_replay_set_error_counters']
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
+CONV_PRECISIONS = {'f32': 0, 'bf16x3': 1}  # MZL_CONV_F32 / MZL_CONV_BF16X3 (include/mzlearner.h)
 
 
 class LearnerError(RuntimeError):
     pass
 
 
+def _conv_precision(v):
+    if isinstance(v, str) and v in CONV_PRECISIONS:
+        return CONV_PRECISIONS[v]
+    if not isinstance(v, (str, bool)) and v in (0, 1):
+        return int(v)
+    raise ValueError(f"conv_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
+
+
 class MzlConfig(C.Structure):
     _fields_ = [('in_dim', C.c_int32), ('num_actions', C.c_int32), ('num_planes', C.c_int32), ('hidden_dim', C.c_int32),
                 ('value_support_size', C.c_int32), ('reward_support_size', C.c_int32), ('unroll_steps', C.c_int32), ('max_batch', C.c_int32),
                 ('grad_slices', C.c_int32), ('net_kind', C.c_int32), ('in_channels', C.c_int32), ('board_h', C.c_int32), ('board_w', C.c_int32),
-                ('num_res_blocks', C.c_int32)]
+                ('num_res_blocks', C.c_int32), ('conv_precision', C.c_int32)]
 
 
 class MzlReplayDraw(C.Structure):
@@ -83,6 +92,8 @@ def load_library():
     L.mzl_replay_sample.argtypes = [C.POINTER(MzlReplayDraw), vp]
     L.mzl_replay_update_priorities.argtypes = [vp, i64, vp, vp, i32, vp, vp]
     L.mzl_replay_set_error_counters.argtypes = [vp]
+    if hasattr(L, 'mzl_debug_conv'):  # (tools/split_learner_bench.py also loads the parent commit's library, which has no hook)
+        L.mzl_debug_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     _lib = L
     return L
 
@@ -167,8 +178,12 @@ class HipLearner:
     what `torch.optim.Adam.state_dict()` would."""
 
     def __init__(self, network, device, unroll_steps: int, max_batch: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 milestones: Sequence[int] = (), gamma: float = 0.1, clip_grad: bool = False, max_grad_norm: float = 40.0, grad_slices: Optional[int] = None):
+                 milestones: Sequence[int] = (), gamma: float = 0.1, clip_grad: bool = False, max_grad_norm: float = 40.0, grad_slices: Optional[int] = None,
+                 conv_precision=0):
+        """conv_precision: 'f32' (0, the default) or 'bf16x3' (1): board nets only -- the towers' forward and data-gradient convs as split-bf16
+        MFMAs (csrc/mz_learn_conv_split.h); the weight gradient, BatchNorm, heads and Adam stay float32 either way."""
         self._h = C.c_void_p()
+        self.conv_precision = _conv_precision(conv_precision)
         if not torch.cuda.is_available():
             raise LearnerError('HipLearner needs a GPU (no CPU fallback)')
         L = load_library()
@@ -191,10 +206,10 @@ class HipLearner:
         if self.kind in ('board', 'atari'):
             c0, bh, bw = spec['input_shape']
             cfg = MzlConfig(in_dim, spec['num_actions'], spec['num_planes'], 1, spec['value_support_size'], spec['reward_support_size'], unroll_steps, max_batch, 1,
-                            NET_BOARD if self.kind == 'board' else NET_ATARI, c0, bh, bw, spec['num_res_blocks'])
+                            NET_BOARD if self.kind == 'board' else NET_ATARI, c0, bh, bw, spec['num_res_blocks'], self.conv_precision)
         else:
             cfg = MzlConfig(in_dim, spec['num_actions'], spec['num_planes'], spec['hidden_dim'], spec['value_support_size'], spec['reward_support_size'],
-                            unroll_steps, max_batch, grad_slices, NET_MLP, 0, 0, 0, 0)
+                            unroll_steps, max_batch, grad_slices, NET_MLP, 0, 0, 0, 0, self.conv_precision)
         _check(L.mzl_create(C.byref(cfg), self.device.index or 0, C.byref(self._h)))
         self.K, self.A, self.in_dim, self.max_batch = unroll_steps, spec['num_actions'], in_dim, max_batch
         self.total = int(L.mzl_num_params(self._h))
@@ -416,6 +431,28 @@ class HipLearner:
                     pi_prob=dev(transitions.pi_prob, torch.float32), value=dev(transitions.value, torch.float32), reward=dev(transitions.reward, torch.float32))
         w = None if weights is None else dev(weights, torch.float32)
         return self.step(ring, None, w, B)
+
+    def debug_conv(self, direction: int, weight, x, action=None, num_actions: int = 0, cin: Optional[int] = None):
+        """Diagnostic (tests): ONE 3 x 3 conv through the learner's packers, tiling chooser and dispatcher at this handle's conv_precision
+        (identity staging; no statistics, skip or mask).  direction 0: the forward conv of x [B, cin_real, h, w] (+ action planes up to `cin`
+        channels) with weight [cout, cin, 3, 3]; direction 1: the data gradient of dy = x [B, cout, h, w].  Host arrays; returns (out, build name)."""
+        weight = np.ascontiguousarray(weight, np.float32)
+        x = np.ascontiguousarray(x, np.float32)
+        if weight.ndim != 4 or x.ndim != 4:
+            raise LearnerError('mzl_debug_conv: weight [cout, cin, 3, 3] and x [B, channels, h, w]')
+        cout, wcin = int(weight.shape[0]), int(weight.shape[1])
+        B, xc, bh, bw = (int(v) for v in x.shape)
+        cin = wcin if cin is None else int(cin)
+        if tuple(weight.shape[2:]) != (3, 3) or cin != wcin or (direction == 0 and xc > cin) or (direction != 0 and xc != cout):
+            raise LearnerError(f'mzl_debug_conv: weight {weight.shape} / cin {cin} do not fit x {x.shape} in direction {direction}')
+        cin_real = xc if direction == 0 else cin
+        out = np.zeros((B, cout if direction == 0 else cin, bh, bw), np.float32)
+        act = None if action is None else np.ascontiguousarray(action, np.int32)
+        name = C.c_char_p()
+        _check(load_library().mzl_debug_conv(self._h, int(direction), B, cin_real, cin, cout, bh, bw, weight.ctypes.data_as(C.c_void_p),
+                                             x.ctypes.data_as(C.c_void_p), None if act is None else act.ctypes.data_as(C.c_void_p), int(num_actions),
+                                             out.ctypes.data_as(C.c_void_p), C.byref(name)))
+        return out, (name.value or b'').decode()
 
     def close(self) -> None:
         if self._h:
