@@ -374,6 +374,16 @@ extern "C" int mzl_debug_conv(mz_learner* h, int32_t direction, int32_t batch, i
     return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv: " + err);
 }
 
+// diagnostic (tests): ONE layer's weight gradient through the conv learner's op builders, geometry chooser and dispatcher (learner_conv.hip
+// mzlc_debug_wgrad; the argument block is mz_learn_conv_host.h's); host pointers
+extern "C" int mzl_debug_wgrad(mz_learner* h, const mzl_wgrad_call* call, const char** build_name) {
+    if (!h || !h->conv) return fail(MZL_E_INVALID, "mzl_debug_wgrad: needs a conv-net learner (MZL_NET_BOARD or MZL_NET_ATARI)");
+    if (!call || !build_name) return fail(MZL_E_INVALID, "mzl_debug_wgrad: null argument");
+    std::string err;
+    const int rc = mzlc_debug_wgrad(h->conv, call, build_name, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_wgrad: " + err);
+}
+
 extern "C" int mzl_tensor_info(const mz_learner* h, int32_t i, const char** name, int64_t* offset, int32_t* rows, int32_t* cols) {
     if (h && h->conv) {
         if (mzlc_tensor_info(h->conv, i, name, offset, rows, cols) != MZL_OK) return fail(MZL_E_INVALID, "tensor index out of range");

@@ -82,8 +82,22 @@ int cdiv(int a, int b) { return (a + b - 1) / b; }
 // the tiling is then chosen by the time of one launch, (rounds of workgroups over the CUs) x (tiles per workgroup), `wg_per_group` workgroups
 // per image group (output-channel blocks x paired jobs): at batch 128 a 6 x 6 hidden state packs best as 4 images in 9 tiles, but that is 128
 // workgroups on 256 CUs, and 2 images in 6 tiles fills the chip in 2/3 of the time.  Ties / images == 0: the densest packing.
-bool make_geom(Geom& g, int hh, int ww, bool allow_side15, int images = 0, int wg_per_group = 1, int cus = 256, bool stack_wgrad = true, bool allow16 = false,
-               int wgrad_blocks = 0) {
+// how make_geom picks the weight-gradient kernel's images per staging round: creation-time switches (wgrad_pick_env) or, for mzlc_debug_wgrad, arguments
+struct WgradPick {
+    bool stack_rows = false;  // MZLC_STACK_ROWS
+    int sg_cap = 16;          // MZLC_WGRAD_SG
+    bool sg_max = false;      // MZLC_WGRAD_SG_MAX: as many as fit, whatever the batch
+    int sg_force = 0;         // > 0: exactly this many or no geometry (never from the environment)
+};
+WgradPick wgrad_pick_env() {
+    WgradPick p;
+    p.stack_rows = getenv("MZLC_STACK_ROWS") != nullptr;
+    if (const char* m = getenv("MZLC_WGRAD_SG")) p.sg_cap = atoi(m);
+    p.sg_max = getenv("MZLC_WGRAD_SG_MAX") != nullptr;
+    return p;
+}
+bool make_geom(Geom& g, int hh, int ww, bool allow_side15, const WgradPick& pick, int images = 0, int wg_per_group = 1, int cus = 256, bool stack_wgrad = true,
+               bool allow16 = false, int wgrad_blocks = 0) {
     g.h = hh; g.w = ww; g.hw = hh * ww;
     if (g.hw < 1 || g.hw > (allow16 ? 256 : 240)) return false;
     const int QP = (g.hw + 3) / 4;
@@ -112,17 +126,18 @@ bool make_geom(Geom& g, int hh, int ww, bool allow_side15, int images = 0, int w
     // staging rounds per workgroup x steps per round, with wgrad_ops' own chunking -- a 6 x 6 plane takes 5 per round, but at batch 128 that is 13 chunks
     // of 10 images = 416 workgroups of a paired launch on 512 slots; 4 per round is 16 chunks of 8 = 512, and 11 steps for 14 (Atari update: 29.0 -> 28.55 ms).
     g.SG = 1;
-    g.stack_rows = getenv("MZLC_STACK_ROWS") != nullptr;
-    const int sg_cap = getenv("MZLC_WGRAD_SG") ? atoi(getenv("MZLC_WGRAD_SG")) : 16;
+    g.stack_rows = pick.stack_rows;
+    const int sg_cap = pick.sg_force > 0 ? pick.sg_force : pick.sg_cap;
+    if (pick.sg_force > 1 && !stack_wgrad) return false;
     if (stack_wgrad) {
         long best_c = 0;
         bool have = false;
-        for (int sg = 1; sg <= sg_cap && sg * QP <= 64; sg++) {
+        for (int sg = pick.sg_force > 0 ? pick.sg_force : 1; sg <= sg_cap && sg * QP <= 64; sg++) {
             const int p4 = (g.stack_rows || sg == 1) ? g.P4 : 4 * cdiv(sg * (g.w + 1), 4);
             const int ns = (g.stack_rows && sg > 1) ? cdiv((sg * (g.h + 1) - 1) * p4, 16) : cdiv(g.h * p4, 16);
             if (sg > 1 && ((size_t)32 * (32 * ns + 2 * p4 + 16) + 160) * sizeof(float) > 80 * 1024) continue;
             long c = -(long)sg;  // (no batch given: as many as fit)
-            if (images > 0 && wgrad_blocks > 0 && !getenv("MZLC_WGRAD_SG_MAX")) {
+            if (images > 0 && wgrad_blocks > 0 && !pick.sg_max) {
                 int chunks = cus / wgrad_blocks;  // (the towers' layers run paired: wgrad_ops)
                 chunks = chunks < 1 ? 1 : (chunks > images ? images : chunks);
                 const int ipw = cdiv(cdiv(images, chunks), sg) * sg;
@@ -130,6 +145,7 @@ bool make_geom(Geom& g, int hh, int ww, bool allow_side15, int images = 0, int w
             }
             if (!have || c <= best_c) { best_c = c; g.SG = sg; have = true; }  // (ties: more images per round)
         }
+        if (pick.sg_force > 0 && !have) return false;  // (the staging lanes or the LDS of two workgroups per CU do not hold that many)
     }
     if (g.SG > 1 && !g.stack_rows) g.P4 = 4 * cdiv(g.SG * (g.w + 1), 4);
     g.nsteps = (g.SG > 1 && g.stack_rows) ? cdiv((g.SG * (g.h + 1) - 1) * g.P4, 16) : cdiv(g.h * g.P4, 16);
@@ -160,6 +176,8 @@ struct mzlc_learner {
     size_t packed3_words = 0;
     LcPackSplitJob* d_pack3 = nullptr;
     std::string debug_name;  // mzlc_debug_conv: the build it ran
+    int dbg_wgrad_remap = 0;                // launch_ops: the last weight-gradient launch's XCD remap and kernel build (mzlc_debug_wgrad's name)
+    const char* dbg_wgrad_build = "";
     bool paired = true;  // the two towers of an unroll step in paired launches (MZLC_NO_PAIR=1 at create: one job per launch; same results)
     int lastB = 0;
     std::vector<void*> allocs;
@@ -337,7 +355,11 @@ struct Sched {
     bool lane_pairs;  // this tower's launches are paired with another tower's
     Geom g;           // geometry of the images these ops work on
     int C;            // channels of the activation tensors (num_planes; 128 in the Atari net's first stage)
+    // mzlc_debug_wgrad only (0 / -1: what the update itself does): images per chunk, the action planes' route (1 inside the MFMA kernel, 2 the gather),
+    // the number of actions of the hook's own layer
+    int ipw_force = 0, act_route = 0, A_force = -1;
     int groups() const { return cdiv(B, g.G); }
+    int A() const { return A_force >= 0 ? A_force : h->A; }
 
     LcConv conv_base(const LayerInfo& L, bool dgrad) const {
         LcConv c{};
@@ -388,11 +410,11 @@ struct Sched {
                    const int* action, int accumulate) const {
         // hidden channels here, action planes by k_lc_wgrad_act -- where that removes at least four 16-channel tiles from the MFMA work (board games:
         // A = hw + 1 planes; the Atari net's 6-18 planes ride in the hidden channels' last tile and stay)
-        const bool split = action && h->act_sparse && cdiv(L.cin, 16) - cdiv(L.cin_real, 16) >= 4;
+        const bool split = action && (act_route ? act_route == 2 : (h->act_sparse && cdiv(L.cin, 16) - cdiv(L.cin_real, 16) >= 4));
         Op o{};
         o.kind = OP_WGRAD;
         LcWgrad& g = o.wg;
-        g.dz = dz; g.y = y; g.dcoef = bcoef; g.x0 = x0; g.xcoef = xcoef; g.x_mode = x_mode; g.action = split ? nullptr : action; g.num_actions = h->A;
+        g.dz = dz; g.y = y; g.dcoef = bcoef; g.x0 = x0; g.xcoef = xcoef; g.x_mode = x_mode; g.action = split ? nullptr : action; g.num_actions = A();
         g.cin_real = L.cin_real; g.cin = split ? L.cin_real : L.cin; g.cout = L.cout; g.ci_tiles = cdiv(g.cin, 16); g.co_tiles = L.co_tiles;
         g.cpad_in = pad16(L.cin_real); g.cpad_out = pad16(L.cout);
         g.B = B; g.h = this->g.h; g.w_img = this->g.w; g.P4 = this->g.P4; g.nsteps = this->g.nsteps; g.SPY = this->g.SPY; g.SPX = this->g.SPX; g.sg = this->g.SG; g.sg_cols = (this->g.SG > 1 && !this->g.stack_rows) ? 1 : 0;
@@ -405,6 +427,7 @@ struct Sched {
         g.ipw = cdiv(B, chunks);
         if (g.ipw < h->wgrad_min_ipw) g.ipw = h->wgrad_min_ipw < B ? h->wgrad_min_ipw : B;
         g.ipw = cdiv(g.ipw, g.sg) * g.sg;  // whole staging rounds
+        if (ipw_force > 0) g.ipw = ipw_force < B ? ipw_force : B;
         chunks = cdiv(B, g.ipw);
         g.part = h->wpart[lane];
         ops.push_back(o);
@@ -419,7 +442,7 @@ struct Sched {
             a.kind = OP_WGRAD_ACT;
             LcWgradAct& w = a.wa;
             w.dz = dz; w.y = y; w.dcoef = bcoef; w.action = action; w.part = h->wpart_act; w.grad = h->grads + L.w_off;
-            w.B = B; w.cout = L.cout; w.cpad_out = pad16(L.cout); w.cin = L.cin; w.cin_real = L.cin_real; w.A = h->A; w.h = this->g.h; w.w = this->g.w;
+            w.B = B; w.cout = L.cout; w.cpad_out = pad16(L.cout); w.cin = L.cin; w.cin_real = L.cin_real; w.A = A(); w.h = this->g.h; w.w = this->g.w;
             w.nchunk = B < ACT_CHUNKS ? B : ACT_CHUNKS; w.bchunk = cdiv(B, w.nchunk); w.nchunk = cdiv(B, w.bchunk); w.accumulate = accumulate;
             ops.push_back(a);
         }
@@ -480,7 +503,7 @@ struct Sched {
         Op o{};
         o.kind = OP_WGRAD;
         LcWgrad& g = o.wg;
-        g.srcs = srcs; g.nsrc = nsrc; g.x_mode = x_mode; g.num_actions = h->A;
+        g.srcs = srcs; g.nsrc = nsrc; g.x_mode = x_mode; g.num_actions = A();
         g.cin_real = L.cin_real; g.cin = L.cin; g.cout = L.cout; g.ci_tiles = cdiv(g.cin, 16); g.co_tiles = L.co_tiles;
         g.cpad_in = pad16(L.cin_real); g.cpad_out = pad16(L.cout);
         g.B = B; g.h = this->g.h; g.w_img = this->g.w; g.P4 = this->g.P4; g.nsteps = this->g.nsteps; g.SPY = this->g.SPY; g.SPX = this->g.SPX; g.sg = this->g.SG; g.sg_cols = (this->g.SG > 1 && !this->g.stack_rows) ? 1 : 0;
@@ -491,6 +514,7 @@ struct Sched {
         g.ipw = cdiv(B, cps);
         if (g.ipw < h->wgrad_min_ipw) g.ipw = h->wgrad_min_ipw < B ? h->wgrad_min_ipw : B;
         g.ipw = cdiv(g.ipw, g.sg) * g.sg;  // whole staging rounds
+        if (ipw_force > 0) g.ipw = ipw_force < B ? ipw_force : B;
         g.cps = cdiv(B, g.ipw);
         g.part = h->wpart[lane];
         ops.push_back(o);
@@ -700,6 +724,9 @@ int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
             pj.remap = (h->xcd_remap && (!b || (b->wg.co_blocks == a->wg.co_blocks && cdiv(b->wg.ci_tiles, 2) == cdiv(a->wg.ci_tiles, 2))) && groups % 8 == 0) ? 1 : 0;
             const size_t wlds = ((size_t)32 * (a->wg.SPY + a->wg.SPX) + 160) * sizeof(float);
             const dim3 wgrid(x, ya + yb);
+            h->dbg_wgrad_remap = pj.remap;  // (mzlc_debug_wgrad reports the build and the placement that ran)
+            h->dbg_wgrad_build = (a->wg.tapmask && a->wg.tapmask != 0x1ff) ? "k_lc_wgrad<ACT=0,RING=1,TAPS>" : a->wg.ring_zero ? "k_lc_wgrad<ACT=0,RING=1>"
+                                 : (a->wg.action || (b && b->wg.action)) ? "k_lc_wgrad<ACT=1,RING=0>" : "k_lc_wgrad<ACT=0,RING=0>";
             if (a->wg.tapmask && a->wg.tapmask != 0x1ff) {  // a parity plane (tile path: ring_zero, no action planes, unpaired)
                 if (b || !a->wg.ring_zero || a->wg.action) { h->bad_dispatch = true; return MZL_E_INVALID; }
                 switch (a->wg.tapmask) {
@@ -951,10 +978,15 @@ struct AtariRun {
     }
     // weight gradient of layer L from dy tiles (already BatchNorm-backward transformed, halo included: ring_zero) and x tiles
     void wgrad_tiles(const LayerInfo& L, int cin, int H, int W, const float* dy_tiles, const float* x_tiles, const signed char* tapmap) const {
-        const Sched s = tiles(L.cout, H, W);
+        std::vector<Op> ops;
+        wgrad_tile_ops(ops, tiles(L.cout, H, W), L, cin, dy_tiles, x_tiles, tapmap);
+        run(ops[0]);
+        run(ops[1]);
+    }
+    // the two ops of that weight gradient (k_lc_wgrad, k_lc_wreduce) over the tiles of `s` (also built by mzlc_debug_wgrad, on buffers of its own)
+    void wgrad_tile_ops(std::vector<Op>& ops, const Sched& s, const LayerInfo& L, int cin, const float* dy_tiles, const float* x_tiles, const signed char* tapmap) const {
         LayerInfo Lw = L;
         Lw.cin_real = cin; Lw.cin = cin;
-        std::vector<Op> ops;
         s.wgrad_ops(ops, Lw, dy_tiles, dy_tiles, h->coef_ident, x_tiles, IN_IDENT, nullptr, nullptr, 0);
         ops[0].wg.ring_zero = 1;
         ops[0].wg.cpad_out = pad16(h->P > 128 ? h->P : 128);  // (the stride of coef_ident's rows)
@@ -981,8 +1013,6 @@ struct AtariRun {
             }
             if (h->par_compact) ops[0].wg.tapmask = mask;
         }
-        run(ops[0]);
-        run(ops[1]);
     }
 
     // ---- forward of two residual blocks on a tiled stage ----
@@ -1230,13 +1260,13 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
     if (cfg->value_support_size < 1 || cfg->reward_support_size < 1 || cfg->value_support_size > 1024 || cfg->reward_support_size > 1024) return bad("support sizes must be in [1, 1024]");
     if (h->hw > 240 || h->P > 1024) return bad("conv learner: boards up to 240 points and 1024 planes (larger nets train through muzero_amd.learner.train_step)");
     if (h->split && h->atari) return bad("conv_precision MZL_CONV_BF16X3 needs net_kind MZL_NET_BOARD: MZL_NET_ATARI has no split-bf16 builds");
-    if (!make_geom(h->gm, h->h, h->w, h->allow_side, getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, cdiv(cdiv(h->P, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
+    if (!make_geom(h->gm, h->h, h->w, h->allow_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, cdiv(cdiv(h->P, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
                    cdiv(cdiv(h->P, 16), 2) * cdiv(cdiv(h->P, 16), 2))) return bad("board does not fit the conv kernels' tiling");
     if (wgrad_lds(h->gm) > 160 * 1024 || conv_lds(h->gm.qstride, pad16(h->P + h->A)) > 160 * 1024) return bad("board too large for the conv learner's LDS layout");
     if (h->split && conv_split_lds(h->gm.G, h->h, h->w, pad16(h->P + h->A)) > 160 * 1024) return bad("conv_precision MZL_CONV_BF16X3: board too large for the split conv's LDS slab");
     h->wide_tiles = !getenv("MZLC_NO_WIDE_TILES");
-    if (h->atari && (!make_geom(h->gt, TILE + 2, TILE + 2, false) || !make_geom(h->g12, TILE, TILE, false) ||
-                     !make_geom(h->gt16, TILE + 2, 18, false, 0, 1, 256, true, true)))
+    if (h->atari && (!make_geom(h->gt, TILE + 2, TILE + 2, false, wgrad_pick_env()) || !make_geom(h->g12, TILE, TILE, false, wgrad_pick_env()) ||
+                     !make_geom(h->gt16, TILE + 2, 18, false, wgrad_pick_env(), 0, 1, 256, true, true)))
         return bad("internal: tile geometry");
     if (h->atari && (wgrad_lds(h->gt16) > 80 * 1024 || h->gt16.npt != 16)) h->wide_tiles = false;  // (two weight-gradient workgroups per CU need their LDS)
     // ---- parameter / buffer tables in state_dict order (network.py:312-498) ----
@@ -1792,7 +1822,7 @@ int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int
     if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
     const int k_in = direction == 0 ? cin : cout, c_in_mem = direction == 0 ? cin_real : cout, c_out = direction == 0 ? cout : cin;
     Geom g;
-    if (!make_geom(g, bh, bw, h->allow_side, batch, cdiv(cdiv(c_out, 16), 4), h->num_cus)) { err = "image does not fit the conv kernels' tiling"; return MZL_E_INVALID; }
+    if (!make_geom(g, bh, bw, h->allow_side, wgrad_pick_env(), batch, cdiv(cdiv(c_out, 16), 4), h->num_cus)) { err = "image does not fit the conv kernels' tiling"; return MZL_E_INVALID; }
     const size_t lds = h->split ? conv_split_lds(g.G, bh, bw, pad16(c_in_mem)) : conv_lds(g.qstride, pad16(c_in_mem));
     if (lds > 160 * 1024) { err = "image too large for the conv kernel's LDS layout"; return MZL_E_INVALID; }
     const int hw = bh * bw, co_tiles = cdiv(c_out, 16), n_cb = cdiv(k_in, h->split ? 32 : 16);
@@ -1862,6 +1892,182 @@ int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int
     char name[192];
     snprintf(name, sizeof(name), "%s %s NPT=%d SIDE=%d G=%d %s us=%.1f", h->split ? "bf16x3" : "f32", h->split ? "k_lc_conv_bf16x3" : "k_lc_conv", g.npt, g.side15 ? 15 : 0,
              g.G, direction == 0 ? "forward" : "dgrad", (double)ms * 1e3);
+    h->debug_name = name;
+    *build_name = h->debug_name.c_str();
+    return done(MZL_OK, "");
+}
+
+// diagnostic (tests): ONE layer's weight gradient, the ops built by the update's own builders -- Sched::wgrad_ops on a board handle (mode plain, and two
+// different layers in one paired launch: pair), Sched::wgrad_ops_steps (steps: nsrc sources of `batch` images in one launch), AtariRun::wgrad_tile_ops
+// on an Atari handle (ring: haloed tiles, the dy ring zeroed) -- with make_geom called as mzlc_create calls it for that batch, launched by launch_ops.
+// The builders point the partials and the result at the handle's buffers, sized for its own net: both (and the sparse action route's partials) are
+// redirected to temporary buffers sized for the chunks of THIS call; the handle's weights, gradients, saved tensors and operand copies are not
+// touched.  NULL stream; *build_name stays valid until the next call and says what ran:
+//   "<precision> <kernel build> mode= SG= cols|rows|single P4= nsteps= ipw= chunks= cps= nsrc= remap= act=none|kernel|sparse ring_rows= taps=0x.. us=<launch time>"
+int mzlc_debug_wgrad(mzlc_learner* h, const mzl_wgrad_call* c, const char** build_name, std::string& err) {
+    const int mode = c->mode, B = c->batch, bh = c->h, bw = c->w;
+    if (mode < MZL_WGRAD_PLAIN || mode > MZL_WGRAD_RING) { err = "mode must be 0 (plain), 1 (pair), 2 (steps) or 3 (ring)"; return MZL_E_INVALID; }
+    if (mode == MZL_WGRAD_RING && !h->atari) { err = "mode ring needs an Atari handle (MZL_NET_ATARI): board nets have no tile path"; return MZL_E_INVALID; }
+    if (mode != MZL_WGRAD_RING && h->atari) { err = "modes plain, pair and steps need a board handle (MZL_NET_BOARD); an Atari handle takes mode ring"; return MZL_E_INVALID; }
+    const int nl = mode == MZL_WGRAD_PAIR ? 2 : 1, nsrc = mode == MZL_WGRAD_STEPS ? c->nsrc : 1;
+    if (B < 1 || B > 4096 || bh < 1 || bw < 1) { err = "bad shape: batch in [1, 4096], h and w at least 1"; return MZL_E_INVALID; }
+    if (bh * bw > (mode == MZL_WGRAD_RING ? 256 : 240)) { err = "h * w outside what the weight-gradient kernel's geometry takes (240 positions; 256 for the Atari net's wide tiles)"; return MZL_E_INVALID; }
+    if (mode == MZL_WGRAD_STEPS && (nsrc < 1 || nsrc > 64)) { err = "mode steps: nsrc in [1, 64]"; return MZL_E_INVALID; }
+    if (c->sg < 0 || c->ipw < 0 || c->layout < 0 || c->layout > 2 || c->remap < 0 || c->remap > 2 || c->act_route < 0 || c->act_route > 2) { err = "bad override (sg, ipw >= 0; layout, remap, act_route in [0, 2])"; return MZL_E_INVALID; }
+    if (c->ipw > B) { err = "ipw override above the batch"; return MZL_E_INVALID; }
+    for (int l = 0; l < nl; l++) {
+        const mzl_wgrad_layer& J = c->layer[l];
+        if (!J.dz || !J.x || !J.out) { err = "null argument (dz, x, out)"; return MZL_E_INVALID; }
+        if (J.cin_real < 1 || J.cin < J.cin_real || J.cin > 4096 || J.cout < 1 || J.cout > 1024) { err = "bad channels: 1 <= cin_real <= cin <= 4096, cout in [1, 1024] (cin < cin_real is no layer)"; return MZL_E_INVALID; }
+        if ((J.y != nullptr) != (J.dcoef != nullptr)) { err = "y and dcoef come together"; return MZL_E_INVALID; }
+        if (J.cin > J.cin_real) {
+            if (mode != MZL_WGRAD_PLAIN) { err = "action planes (cin > cin_real) in mode plain only: the update never pairs or defers that layer"; return MZL_E_INVALID; }
+            if (!J.action || c->num_actions < 1) { err = "cin > cin_real needs action and num_actions >= 1 (the action planes)"; return MZL_E_INVALID; }
+            for (int b = 0; b < B; b++)
+                if (J.action[b] < 0 || J.action[b] >= c->num_actions) { err = "action out of [0, num_actions)"; return MZL_E_INVALID; }
+            if (c->act_route == 2 && (J.cin - J.cin_real != c->num_actions || c->num_actions > 256)) { err = "the sparse action route needs cin - cin_real == num_actions <= 256 (one thread per plane)"; return MZL_E_INVALID; }
+        } else if (J.action || c->act_route) { err = "action / act_route without action planes (cin == cin_real)"; return MZL_E_INVALID; }
+        if (mode == MZL_WGRAD_RING && (J.y || J.xcoef || c->accumulate)) { err = "mode ring: the tile path stages dy and x as they are and never accumulates"; return MZL_E_INVALID; }
+        if (mode == MZL_WGRAD_STEPS && c->accumulate) { err = "mode steps never accumulates"; return MZL_E_INVALID; }
+    }
+    if (mode == MZL_WGRAD_RING) {
+        if (c->tapmask != 0 && c->tapmask != 0x1ff && c->tapmask != 0x010 && c->tapmask != 0x018 && c->tapmask != 0x012 && c->tapmask != 0x01b) { err = "tap mask: 0 / 0x1ff, 0x010, 0x018, 0x012 or 0x01b"; return MZL_E_INVALID; }
+        if (c->ring_rows < -1 || c->ring_rows > 3) { err = "ring_rows in [-1, 3]"; return MZL_E_INVALID; }
+        if (c->ring_rows > 0 && c->sg > 1) { err = "ring_rows > 0 needs one image per staging round (SG = 1)"; return MZL_E_INVALID; }
+        if (bh < 3 || bw < 3) { err = "mode ring: a tile with its halo is at least 3 x 3"; return MZL_E_INVALID; }
+        if (c->layer[0].cout > pad16(h->P > 128 ? h->P : 128)) { err = "mode ring: cout above the handle's identity-coefficient rows"; return MZL_E_INVALID; }
+    } else if (c->ring_rows > 0 || (c->tapmask && c->tapmask != 0x1ff)) { err = "ring_rows / tap masks belong to mode ring"; return MZL_E_INVALID; }
+    if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+
+    // ---- geometry: make_geom as mzlc_create calls it (board: for this batch and this layer's block grid; ring: the tile geometries, no batch) ----
+    const mzl_wgrad_layer& J0 = c->layer[0];
+    WgradPick pick = wgrad_pick_env();
+    if (c->sg > 0) pick.sg_force = c->sg;
+    if (c->layout) pick.stack_rows = c->layout == 2;
+    Geom g;
+    bool fits;
+    if (mode == MZL_WGRAD_RING) fits = make_geom(g, bh, bw, false, pick, 0, 1, 256, true, bh * bw > 240);
+    else fits = make_geom(g, bh, bw, h->allow_side, pick, B, cdiv(cdiv(J0.cout, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
+                          cdiv(cdiv(J0.cout, 16), 2) * cdiv(cdiv(J0.cin_real, 16), 2));
+    if (!fits) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of two workgroups per CU do not hold that many images per round" : "image does not fit the kernels' geometry"; return MZL_E_INVALID; }
+    if (wgrad_lds(g) > 160 * 1024) { err = "the weight-gradient planes of this geometry exceed the LDS"; return MZL_E_INVALID; }
+
+    // ---- device buffers ----
+    std::vector<void*> tmp;
+    auto A = [&](void** p, size_t bytes) {
+        if (hipMalloc(p, bytes + 256) != hipSuccess) return false;
+        tmp.push_back(*p);
+        return hipMemset(*p, 0, bytes + 256) == hipSuccess;
+    };
+    const bool sv_remap = h->xcd_remap, sv_sparse = h->act_sparse, sv_rr = h->ring_rows, sv_row = h->row_steps, sv_quad = h->quad_steps, sv_bad = h->bad_dispatch;
+    auto done = [&](int rc, const char* m) {
+        (void)hipDeviceSynchronize();
+        for (void* p : tmp) (void)hipFree(p);
+        h->xcd_remap = sv_remap; h->act_sparse = sv_sparse; h->ring_rows = sv_rr; h->row_steps = sv_row; h->quad_steps = sv_quad; h->bad_dispatch = sv_bad;
+        if (rc != MZL_OK) { err = m; (void)hipGetLastError(); }
+        return rc;
+    };
+    const size_t hw = (size_t)bh * bw;
+    struct Dev { float *dz = nullptr, *x = nullptr, *y = nullptr, *dcoef = nullptr, *xcoef = nullptr, *out = nullptr, *part = nullptr, *part_act = nullptr; int* act = nullptr; LcWgradSrc* srcs = nullptr; };
+    Dev d[2];
+    for (int l = 0; l < nl; l++) {
+        const mzl_wgrad_layer& J = c->layer[l];
+        const size_t n_dz = (size_t)nsrc * B * J.cout * hw, n_x = (size_t)nsrc * B * J.cin_real * hw, n_out = (size_t)J.cout * J.cin * 9;
+        const int cpo = pad16(J.cout), cpi = pad16(J.cin_real);
+        if (!A((void**)&d[l].dz, n_dz * 4) || !A((void**)&d[l].x, n_x * 4) || !A((void**)&d[l].out, n_out * 4) || !A((void**)&d[l].dcoef, (size_t)nsrc * 3 * cpo * 4) ||
+            !A((void**)&d[l].xcoef, (size_t)nsrc * 3 * cpi * 4) || !A((void**)&d[l].act, (size_t)B * 4) || !A((void**)&d[l].srcs, (size_t)nsrc * sizeof(LcWgradSrc)) ||
+            (J.y && !A((void**)&d[l].y, n_dz * 4)))
+            return done(MZL_E_HIP, "hipMalloc failed");
+        std::vector<float> dc((size_t)nsrc * 3 * cpo, 0.0f), xc((size_t)nsrc * 3 * cpi, 0.0f);
+        for (int s = 0; s < nsrc; s++)
+            for (int k = 0; k < 3; k++)
+                for (int ch = 0; ch < J.cout; ch++) dc[((size_t)s * 3 + k) * cpo + ch] = J.dcoef ? J.dcoef[((size_t)s * 3 + k) * J.cout + ch] : (k == 0 ? 1.0f : 0.0f);
+        if (J.xcoef)
+            for (int s = 0; s < nsrc; s++)
+                for (int k = 0; k < 2; k++)
+                    for (int ch = 0; ch < J.cin_real; ch++) xc[((size_t)s * 3 + k) * cpi + ch] = J.xcoef[((size_t)s * 2 + k) * J.cin_real + ch];
+        bool ok = hipMemcpy(d[l].dz, J.dz, n_dz * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d[l].x, J.x, n_x * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d[l].dcoef, dc.data(), dc.size() * 4, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d[l].xcoef, xc.data(), xc.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (J.y) ok = ok && hipMemcpy(d[l].y, J.y, n_dz * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (J.action) ok = ok && hipMemcpy(d[l].act, J.action, (size_t)B * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (J.preload) ok = ok && hipMemcpy(d[l].out, J.preload, n_out * 4, hipMemcpyHostToDevice) == hipSuccess;
+        if (!d[l].y) d[l].y = d[l].dz;  // (identity coefficients: c2 = 0, as the tile path passes its dy tiles twice)
+        std::vector<LcWgradSrc> tab(nsrc);
+        for (int s = 0; s < nsrc; s++) {
+            tab[s].dz = d[l].dz + (size_t)s * B * J.cout * hw; tab[s].y = d[l].y + (size_t)s * B * J.cout * hw; tab[s].dcoef = d[l].dcoef + (size_t)s * 3 * cpo;
+            tab[s].x0 = d[l].x + (size_t)s * B * J.cin_real * hw; tab[s].xcoef = J.xcoef ? d[l].xcoef + (size_t)s * 3 * cpi : nullptr;
+        }
+        ok = ok && hipMemcpy(d[l].srcs, tab.data(), tab.size() * sizeof(LcWgradSrc), hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) return done(MZL_E_HIP, "hipMemcpy failed");
+    }
+
+    // ---- the ops, by the update's builders ----
+    if (c->remap) h->xcd_remap = c->remap == 1;
+    if (mode == MZL_WGRAD_RING && c->ring_rows >= 0) { h->ring_rows = c->ring_rows > 0; h->row_steps = c->ring_rows == 2; h->quad_steps = c->ring_rows == 3; }
+    std::vector<Op> ops[2];
+    for (int l = 0; l < nl; l++) {
+        const mzl_wgrad_layer& J = c->layer[l];
+        LayerInfo L;
+        L.cin_real = J.cin_real; L.cin = J.cin; L.cout = J.cout; L.co_tiles = cdiv(J.cout, 16); L.w_off = 0;
+        Sched s{h, B, l, mode == MZL_WGRAD_PAIR, g, J.cout};
+        s.ipw_force = c->ipw; s.act_route = c->act_route; s.A_force = c->num_actions;
+        const int x_mode = J.xcoef ? IN_BNRELU : IN_IDENT;
+        if (mode == MZL_WGRAD_RING) {
+            signed char m[9];
+            int pq = -1;
+            for (int k = 0; k < 4; k++)
+                if (par_tapmask(k >> 1, k & 1, false) == c->tapmask) pq = k;
+            if (pq >= 0) par_tapmap(pq >> 1, pq & 1, false, m);
+            const AtariRun R{h, B, nullptr};
+            R.wgrad_tile_ops(ops[l], s, L, J.cin_real, d[l].dz, d[l].x, pq >= 0 ? m : nullptr);
+        } else if (mode == MZL_WGRAD_STEPS) {
+            s.wgrad_ops_steps(ops[l], L, d[l].srcs, nsrc, x_mode);
+        } else {
+            s.wgrad_ops(ops[l], L, d[l].dz, d[l].y, d[l].dcoef, d[l].x, x_mode, J.xcoef ? d[l].xcoef : nullptr, J.cin > J.cin_real ? d[l].act : nullptr, c->accumulate ? 1 : 0);
+        }
+        if (ops[l].size() < 2 || ops[l][0].kind != OP_WGRAD || ops[l][1].kind != OP_WREDUCE) return done(MZL_E_STATE, "internal: unexpected op list");
+        // partials and result: buffers of this call, sized from the ops the builder made
+        LcWreduce& wr = ops[l][1].wr;
+        if (!A((void**)&d[l].part, (size_t)wr.chunks * 9 * wr.co_pad * wr.ci_pad * 4)) return done(MZL_E_HIP, "hipMalloc failed");
+        ops[l][0].wg.part = d[l].part; wr.part = d[l].part; wr.grad = d[l].out;
+        if (ops[l].size() > 2) {
+            if (ops[l].size() != 3 || ops[l][2].kind != OP_WGRAD_ACT) return done(MZL_E_STATE, "internal: unexpected op list");
+            LcWgradAct& wa = ops[l][2].wa;
+            if (!A((void**)&d[l].part_act, (size_t)wa.nchunk * wa.cout * wa.A * 9 * 4)) return done(MZL_E_HIP, "hipMalloc failed");
+            wa.part = d[l].part_act; wa.grad = d[l].out;
+        }
+    }
+    const LcWgrad& W0 = ops[0][0].wg;
+    if (mode == MZL_WGRAD_RING && c->ring_rows >= 0 && W0.ring_rows != c->ring_rows) return done(MZL_E_INVALID, "the update's conditions do not give this ring_rows build for this tile (1: any; 2: pitch above 16 and at most 16 inner columns; 3: 12 inner columns)");
+    if (mode == MZL_WGRAD_PAIR && ops[0].size() != ops[1].size()) return done(MZL_E_STATE, "internal: op lists of the pair do not line up");
+
+    // ---- launch ----
+    hipStream_t st = nullptr;
+    h->bad_dispatch = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) return done(MZL_E_HIP, "hipEventCreate failed");
+    int rc = 0;
+    for (size_t i = 0; i < ops[0].size() && rc == 0; i++) {
+        if (i == 0) (void)hipEventRecord(ev0, st);
+        rc = launch_ops(h, &ops[0][i], nl == 2 ? &ops[1][i] : nullptr, st);
+        if (i == 0) (void)hipEventRecord(ev1, st);
+    }
+    const bool bad = h->bad_dispatch;
+    const bool ran = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    float ms = 0.0f;
+    if (ran) (void)hipEventElapsedTime(&ms, ev0, ev1);
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    if (rc != 0 || bad) return done(MZL_E_INVALID, "no kernel build for this weight gradient");
+    if (!ran) return done(MZL_E_HIP, "the weight gradient failed to launch or run");
+    for (int l = 0; l < nl; l++)
+        if (hipMemcpy(c->layer[l].out, d[l].out, (size_t)c->layer[l].cout * c->layer[l].cin * 9 * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+    static const char* modes[4] = {"plain", "pair", "steps", "ring"};
+    const bool has_act = J0.cin > J0.cin_real;
+    char name[320];
+    snprintf(name, sizeof(name), "%s %s mode=%s SG=%d %s P4=%d nsteps=%d ipw=%d chunks=%d cps=%d nsrc=%d remap=%d act=%s ring_rows=%d taps=0x%03x us=%.1f", h->split ? "bf16x3" : "f32",
+             h->dbg_wgrad_build, modes[mode], W0.sg, W0.sg == 1 ? "single" : (W0.sg_cols ? "cols" : "rows"), W0.P4, W0.nsteps, W0.ipw, ops[0][1].wr.chunks, W0.srcs ? W0.cps : 0,
+             W0.srcs ? W0.nsrc : 0, h->dbg_wgrad_remap, !has_act ? "none" : (ops[0].size() > 2 ? "sparse" : "kernel"), W0.ring_rows, W0.tapmask ? W0.tapmask : 0x1ff, (double)ms * 1e3);
     h->debug_name = name;
     *build_name = h->debug_name.c_str();
     return done(MZL_OK, "");

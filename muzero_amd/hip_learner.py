@@ -59,6 +59,21 @@ class MzlBatch(C.Structure):
 _lib = None
 
 
+class MzlWgradLayer(C.Structure):
+    """mzl_wgrad_layer (csrc/mz_learn_conv_host.h): one layer's host operands of mzl_debug_wgrad."""
+    _fields_ = [(n, C.c_void_p) for n in ('dz', 'x', 'y', 'dcoef', 'xcoef', 'action', 'preload', 'out')] + \
+               [(n, C.c_int32) for n in ('cin_real', 'cin', 'cout', 'pad_')]
+
+
+class MzlWgradCall(C.Structure):
+    """mzl_wgrad_call (csrc/mz_learn_conv_host.h)."""
+    _fields_ = [(n, C.c_int32) for n in ('mode', 'batch', 'h', 'w', 'num_actions', 'nsrc', 'accumulate', 'sg', 'layout', 'ipw', 'remap', 'act_route',
+                                         'ring_rows', 'tapmask')] + [('layer', MzlWgradLayer * 2)]
+
+
+WGRAD_MODES = {'plain': 0, 'pair': 1, 'steps': 2, 'ring': 3}
+
+
 def load_library():
     global _lib
     if _lib is not None:
@@ -94,6 +109,8 @@ def load_library():
     L.mzl_replay_set_error_counters.argtypes = [vp]
     if hasattr(L, 'mzl_debug_conv'):  # (tools/split_learner_bench.py also loads the parent commit's library, which has no hook)
         L.mzl_debug_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
+    if hasattr(L, 'mzl_debug_wgrad'):
+        L.mzl_debug_wgrad.argtypes = [vp, C.POINTER(MzlWgradCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     _lib = L
     return L
 
@@ -453,6 +470,66 @@ class HipLearner:
                                              x.ctypes.data_as(C.c_void_p), None if act is None else act.ctypes.data_as(C.c_void_p), int(num_actions),
                                              out.ctypes.data_as(C.c_void_p), C.byref(name)))
         return out, (name.value or b'').decode()
+
+    def debug_wgrad(self, dz, x, mode: str = 'plain', y=None, dcoef=None, xcoef=None, action=None, num_actions: int = 0, cin: Optional[int] = None,
+                    preload=None, accumulate: bool = False, second=None, sg: int = 0, layout: int = 0, ipw: int = 0, remap: int = 0, act_route: int = 0,
+                    ring_rows: int = -1, tapmask: int = 0):
+        """Diagnostic (tests): ONE layer's weight gradient through the learner's op builders, geometry chooser and dispatcher (mzl_debug_wgrad).
+        dz [B, cout, h, w] and x [B, cin_real, h, w] (mode 'steps': a leading source axis on dz, x, y, dcoef, xcoef); optional y with dcoef
+        [3, cout] (dy = c1 dz + c2 y + c3), xcoef [2, cin_real] (x' = relu(a x + b)), action [B] with num_actions and cin > cin_real, preload
+        [cout, cin, 3, 3] (+ accumulate).  mode 'pair': `second` = dict(dz=, x=, ...) of the other layer of the launch; 'ring' (Atari handles):
+        haloed tiles, ring_rows -1 .. 3 and a tap mask.  Overrides (0: what the update chooses): sg images per staging round, layout 1 side by
+        side / 2 stacked, ipw images per chunk, remap 1 on / 2 off, act_route 1 in-kernel / 2 sparse.  Returns (dW [cout, cin, 3, 3], name of
+        what ran); mode 'pair': ((dW, dW of the second layer), name)."""
+        lib = load_library()
+        if not hasattr(lib, 'mzl_debug_wgrad'):
+            raise LearnerError('mzl_debug_wgrad: this library has no such hook')
+        if mode not in WGRAD_MODES:
+            raise LearnerError(f'mzl_debug_wgrad: mode {mode!r} (one of {sorted(WGRAD_MODES)})')
+        lead = 1 if mode == 'steps' else 0
+        call = MzlWgradCall()
+        keep = []
+
+        def arr(a, dt=np.float32):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            keep.append(a)
+            return a.ctypes.data
+
+        def fill(J, dz, x, y=None, dcoef=None, xcoef=None, action=None, cin=None, preload=None):
+            dz, x = np.ascontiguousarray(dz, np.float32), np.ascontiguousarray(x, np.float32)
+            if dz.ndim != 4 + lead or x.ndim != 4 + lead or dz.shape[:lead + 1] != x.shape[:lead + 1] or dz.shape[-2:] != x.shape[-2:]:
+                raise LearnerError(f'mzl_debug_wgrad: dz {dz.shape} and x {x.shape} do not fit (mode {mode})')
+            cout, cr = int(dz.shape[lead + 1]), int(x.shape[lead + 1])
+            cin = cr if cin is None else int(cin)
+            for a, shape, what in ((y, dz.shape, 'y'), (dcoef, dz.shape[:lead] + (3, cout), 'dcoef'), (xcoef, dz.shape[:lead] + (2, cr), 'xcoef'),
+                                   (action, (dz.shape[lead],), 'action'), (preload, (cout, cin, 3, 3), 'preload')):
+                if a is not None and tuple(np.shape(a)) != tuple(shape):
+                    raise LearnerError(f'mzl_debug_wgrad: {what} {np.shape(a)} is not {tuple(shape)}')
+            out = np.zeros((cout, max(cin, 0), 3, 3), np.float32)
+            keep.append(out)
+            J.dz, J.x, J.y, J.dcoef, J.xcoef = arr(dz), arr(x), arr(y), arr(dcoef), arr(xcoef)
+            J.action, J.preload, J.out = arr(action, np.int32), arr(preload), out.ctypes.data
+            J.cin_real, J.cin, J.cout = cr, cin, cout
+            return out, dz.shape
+
+        out0, shp = fill(call.layer[0], dz, x, y, dcoef, xcoef, action, cin, preload)
+        outs = [out0]
+        if mode == 'pair':
+            if second is None:
+                raise LearnerError("mzl_debug_wgrad: mode 'pair' needs `second`")
+            o1, shp1 = fill(call.layer[1], **second)
+            if shp1[0] != shp[0] or shp1[-2:] != shp[-2:]:
+                raise LearnerError('mzl_debug_wgrad: the two layers of a pair share batch and board')
+            outs.append(o1)
+        call.mode, call.batch, call.h, call.w = WGRAD_MODES[mode], int(shp[lead]), int(shp[-2]), int(shp[-1])
+        call.num_actions, call.nsrc, call.accumulate = int(num_actions), int(shp[0]) if lead else 1, int(bool(accumulate))
+        call.sg, call.layout, call.ipw, call.remap, call.act_route = int(sg), int(layout), int(ipw), int(remap), int(act_route)
+        call.ring_rows, call.tapmask = int(ring_rows), int(tapmask)
+        name = C.c_char_p()
+        _check(lib.mzl_debug_wgrad(self._h, C.byref(call), C.byref(name)))
+        return (tuple(outs) if mode == 'pair' else out0), (name.value or b'').decode()
 
     def close(self) -> None:
         if self._h:

@@ -85,8 +85,9 @@ def test_header_and_ctypes_mirror_carry_the_field_last():
     assert all(t is C.c_int32 for _, t in hl.MzlConfig._fields_)
     assert C.sizeof(hl.MzlConfig) == 4 * len(fields) and hl.MzlConfig.conv_precision.offset == 4 * (len(fields) - 1)
     assert hl.MzlConfig().conv_precision == 0  # a zero-initialised config stays float32
-    # the diagnostic hook is exported, not declared
-    assert 'mzl_debug_conv' not in re.sub(r'/\*.*?\*/', '', text, flags=re.S) and 'mzl_debug_conv' not in hl.ABI_SYMBOLS
+    # the diagnostic hooks are exported, not declared
+    for hook in ('mzl_debug_conv', 'mzl_debug_wgrad'):
+        assert hook not in re.sub(r'/\*.*?\*/', '', text, flags=re.S) and hook not in hl.ABI_SYMBOLS
 
 
 RUNS = [(c, s, d) for c in cc.INT_CLASSES for s in INT_SHAPES for d in (0, 1) if not (d == 1 and INT_SHAPES[s][3])]
