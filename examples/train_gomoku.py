@@ -67,7 +67,10 @@ def main():
                     help="the planner's conv arithmetic (mz_config.conv_precision): f32 is bit-equal to the oracle, bf16x3 the split-bf16 path; the learner has its own switch, --learner-conv-precision")
     ap.add_argument('--learner-conv-precision', choices=['f32', 'bf16x3'], default='f32',
                     help="the HIP learner's conv arithmetic (mzl_config.conv_precision): bf16x3 runs the towers' forward and data-gradient convs as split-bf16 MFMAs; "
-                         "the weight gradient, BatchNorm, the heads and Adam stay float32 either way")
+                         "BatchNorm, the heads and Adam stay float32 either way; the weight gradient has its own switch, --learner-wgrad-precision")
+    ap.add_argument('--learner-wgrad-precision', choices=['f32', 'bf16x3'], default='f32',
+                    help="the HIP learner's weight-gradient arithmetic (mzl_set_wgrad_precision): bf16x3 runs the towers' weight gradients as split-bf16 MFMAs, "
+                         "independent of --learner-conv-precision")
     ap.add_argument('--arena-eval', type=int, default=0, metavar='N',
                     help='also play N games (even) against the random opponent as one lock-step batch on the device (pipeline.play_match); 0: off')
     args = ap.parse_args()
@@ -98,7 +101,7 @@ def main():
         opt = learner.make_capturable_adam(net, cfg, dev)
         graphed = learner.prepare_graphed_step(cfg, net, opt, dev, obs_shape, A)
     elif use_hip:  # the conv learner's kernels; the module's parameters and BatchNorm buffers become views of the learner's flat vectors
-        hip = learner.make_hip_learner(cfg, net, dev, conv_precision=args.learner_conv_precision)
+        hip = learner.make_hip_learner(cfg, net, dev, conv_precision=args.learner_conv_precision, wgrad_precision=args.learner_wgrad_precision)
         opt = None
     else:
         opt = torch.optim.Adam(net.parameters(), lr=cfg.lr_init, weight_decay=cfg.weight_decay)

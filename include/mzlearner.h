@@ -34,8 +34,13 @@ extern "C" {
 #define MZL_CONV_F32 0     /* the conv nets' 3x3 convs on the f32-input MFMA (default) */
 #define MZL_CONV_BF16X3 1  /* MZL_NET_BOARD only: the towers' forward and data-gradient convs as split-bf16 MFMAs -- every float32 operand the exact sum of
                             * three bf16 values, six products per step accumulated in float32 (muzero_amd/csrc/mz_learn_conv_split.h).  Staging transforms,
-                            * saved tensors, masks, BatchNorm, the weight gradient, the heads and Adam stay float32.  Float32-grade, not bit-equal to
-                            * MZL_CONV_F32. */
+                            * saved tensors, masks, BatchNorm, the heads and Adam stay float32, and so does the weight gradient by default (switchable on
+                            * its own: mzl_set_wgrad_precision).  Float32-grade, not bit-equal to MZL_CONV_F32. */
+
+#define MZL_WGRAD_F32 0     /* the towers' weight gradients on the f32-input MFMA (default) */
+#define MZL_WGRAD_BF16X3 1  /* MZL_NET_BOARD only: the towers' weight gradients as split-bf16 MFMAs (muzero_amd/csrc/mz_learn_conv_split_wgrad.h): dy and the
+                             * transformed x formed in float32, split into three bf16 terms, six products per step accumulated in float32.  The sparse
+                             * action-plane gather, the partials' reduction, BatchNorm, the heads and Adam stay float32. */
 
 /* The network's constructor arguments (MuZeroMLPNet network.py:239-247 | MuZeroBoardGameNet :543-549) + the batch geometry of calc_loss
  * (pipeline.py:541-575). */
@@ -119,6 +124,12 @@ int mzl_buffer_info(const mz_learner* h, int32_t i, const char** name, int64_t* 
 /* Caller-owned device buffers of the BatchNorm statistics (float32 [mzl_num_running], int64 [mzl_num_buffers]); required before mzl_grad
  * for conv nets.  Replaces: the module buffers that network.state_dict() carries (pipeline.py:224-230). */
 int mzl_bind_buffers(mz_learner* h, float* d_running, int64_t* d_num_batches);
+
+/* The weight-gradient kernel of the towers' convs: MZL_WGRAD_F32 (default) | MZL_WGRAD_BF16X3.  Legal after mzl_create and before mzl_bind
+ * (MZL_E_STATE later).  MZL_E_INVALID, the message naming wgrad_precision, for an unknown value, an MLP net, an Atari net, or a board whose split
+ * planes do not fit the LDS; the handle then stays as it was.  Independent of mzl_config.conv_precision: all four combinations are valid for
+ * MZL_NET_BOARD.  Redoes the weight-gradient geometry mzl_create derived (images per staging round, pitch, steps, LDS). */
+int mzl_set_wgrad_precision(mz_learner* h, int32_t precision);
 
 /* Caller-owned flat device buffers: master weights, gradients, Adam's exp_avg / exp_avg_sq (torch.optim.Adam state), all float32.
  * Replaces: network.parameters() / optimizer.state (pipeline.py:224-230).  The caller keeps them alive while bound. */

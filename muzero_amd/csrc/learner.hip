@@ -398,6 +398,16 @@ extern "C" int mzl_tensor_info(const mz_learner* h, int32_t i, const char** name
     return MZL_OK;
 }
 
+extern "C" int mzl_set_wgrad_precision(mz_learner* h, int32_t precision) {
+    if (!h) return fail(MZL_E_INVALID, "null learner");
+    if (precision != MZL_WGRAD_F32 && precision != MZL_WGRAD_BF16X3)
+        return fail(MZL_E_INVALID, "wgrad_precision must be MZL_WGRAD_F32 (0) or MZL_WGRAD_BF16X3 (1), not " + std::to_string(precision));
+    if (!h->conv) return fail(MZL_E_INVALID, "wgrad_precision needs net_kind MZL_NET_BOARD: MZL_NET_MLP has no convolutions");
+    std::string err;
+    const int rc = mzlc_set_wgrad_precision(h->conv, precision, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, err);
+}
+
 extern "C" int mzl_bind(mz_learner* h, float* d_params, float* d_grads, float* d_exp_avg, float* d_exp_avg_sq) {
     if (!h || !d_params || !d_grads || !d_exp_avg || !d_exp_avg_sq) return fail(MZL_E_INVALID, "null argument to mzl_bind");
     if (h->conv) return mzlc_bind(h->conv, d_params, d_grads, d_exp_avg, d_exp_avg_sq);

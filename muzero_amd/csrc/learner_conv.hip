@@ -21,6 +21,7 @@
 
 #include "mz_learn_conv.h"
 #include "mz_learn_conv_split.h"
+#include "mz_learn_conv_split_wgrad.h"
 #include "mz_learn_conv_host.h"
 
 using namespace mzlc;
@@ -154,6 +155,41 @@ bool make_geom(Geom& g, int hh, int ww, bool allow_side15, const WgradPick& pick
     return true;
 }
 
+// the weight-gradient fields of `g` (P4, nsteps, SPY, SPX, SG, stack_rows) for k_lc_wgrad_bf16x3, after make_geom has filled the rest: the split
+// planes are bf16 in three terms (6 bytes per position against 4), the pitch is a multiple of 8 and a step is 32 positions, so the budget is this
+// function's own and make_geom's float32 choices do not move.  The planes of 32 + 32 channels must fit ONE workgroup's LDS (160 KB; a 15 x 15 board
+// takes 111 KB): the kernel's registers (345 of 512) hold one workgroup per CU whatever the planes' size, so the launch-time estimate counts one
+// slot per CU.  false: nothing fits (pick.sg_force: that count does not fit).
+bool make_geom_wsplit(Geom& g, const WgradPick& pick, int images, int cus, bool stack_wgrad, int wgrad_blocks) {
+    const int QP = (g.hw + 3) / 4;
+    const int sg_cap = (stack_wgrad || pick.sg_force > 0) ? (pick.sg_force > 0 ? pick.sg_force : pick.sg_cap) : 1;
+    if (pick.sg_force > 1 && !stack_wgrad) return false;
+    long best_c = 0;
+    bool have = false;
+    for (int sg = pick.sg_force > 0 ? pick.sg_force : 1; sg <= (sg_cap < 1 ? 1 : sg_cap) && sg * QP <= 64; sg++) {
+        const bool rows = pick.stack_rows && sg > 1;
+        const int p8 = 8 * cdiv((rows || sg == 1) ? g.w + 1 : sg * (g.w + 1), 8);
+        const int ns = cdiv((rows ? sg * (g.h + 1) - 1 : g.h) * p8, 32);
+        const size_t lds = wgrad_split_lds(wgrad_split_spy(ns), wgrad_split_spx(ns, p8));
+        if (lds > 160 * 1024) continue;
+        long c = -(long)sg;  // (no batch given: as many as fit)
+        if (images > 0 && wgrad_blocks > 0 && !pick.sg_max) {
+            int chunks = cus / wgrad_blocks;  // (the towers' layers run paired: wgrad_ops)
+            chunks = chunks < 1 ? 1 : (chunks > images ? images : chunks);
+            const int ipw = cdiv(cdiv(images, chunks), sg) * sg;
+            c = (long)cdiv(cdiv(images, ipw) * wgrad_blocks * 2, cus) * (ipw / sg) * ns;
+        }
+        if (!have || c <= best_c) {  // (ties: more images per round)
+            best_c = c; have = true;
+            g.SG = sg; g.stack_rows = pick.stack_rows; g.P4 = p8; g.nsteps = ns;
+        }
+    }
+    if (!have) return false;
+    g.SPY = wgrad_split_spy(g.nsteps);
+    g.SPX = wgrad_split_spx(g.nsteps, g.P4);
+    return true;
+}
+
 }  // namespace
 
 struct mzlc_learner {
@@ -170,6 +206,8 @@ struct mzlc_learner {
     std::vector<BnInfo> bns;  // every BatchNorm (towers, then heads): buffer table
     LchHead head[3];
     int64_t total = 0, nrunning = 0;
+    bool wsplit = false;     // mzlc_set_wgrad_precision(MZL_WGRAD_BF16X3): the towers' weight gradients run k_lc_wgrad_bf16x3 (mz_learn_conv_split_wgrad.h), gm's
+                             // weight-gradient fields are make_geom_wsplit's
     bool split = false;      // mzl_config.conv_precision == MZL_CONV_BF16X3: the towers' convs run k_lc_conv_bf16x3 (mz_learn_conv_split.h)
     bool allow_side = true;  // the 15 x 15 conv builds (MZLC_NO_SIDE=1 at create: the generic ones)
     u32x4* packed3 = nullptr;  // split: three bf16 fragment streams per (output-channel tile, 32-channel block, tap), both orientations
@@ -725,6 +763,15 @@ int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
             const size_t wlds = ((size_t)32 * (a->wg.SPY + a->wg.SPX) + 160) * sizeof(float);
             const dim3 wgrid(x, ya + yb);
             h->dbg_wgrad_remap = pj.remap;  // (mzlc_debug_wgrad reports the build and the placement that ran)
+            if (h->wsplit) {  // a board net's towers: whole images, nine taps, no ring (make_geom_wsplit's planes)
+                if (a->wg.ring_zero || (a->wg.tapmask && a->wg.tapmask != 0x1ff) || (a->wg.P4 & 7)) { h->bad_dispatch = true; return MZL_E_INVALID; }
+                const size_t slds = wgrad_split_lds(a->wg.SPY, a->wg.SPX);
+                const bool act = a->wg.action || (b && b->wg.action);
+                h->dbg_wgrad_build = act ? "k_lc_wgrad_bf16x3<ACT=1>" : "k_lc_wgrad_bf16x3<ACT=0>";
+                if (act) hipLaunchKernelGGL((k_lc_wgrad_bf16x3<true>), wgrid, dim3(256), slds, st, pj);
+                else hipLaunchKernelGGL((k_lc_wgrad_bf16x3<false>), wgrid, dim3(256), slds, st, pj);
+                break;
+            }
             h->dbg_wgrad_build = (a->wg.tapmask && a->wg.tapmask != 0x1ff) ? "k_lc_wgrad<ACT=0,RING=1,TAPS>" : a->wg.ring_zero ? "k_lc_wgrad<ACT=0,RING=1>"
                                  : (a->wg.action || (b && b->wg.action)) ? "k_lc_wgrad<ACT=1,RING=0>" : "k_lc_wgrad<ACT=0,RING=0>";
             if (a->wg.tapmask && a->wg.tapmask != 0x1ff) {  // a parity plane (tile path: ring_zero, no action planes, unpaired)
@@ -1571,6 +1618,32 @@ int mzlc_buffer_info(const mzlc_learner* h, int i, const char** name, int64_t* o
 }
 int64_t mzlc_num_running(const mzlc_learner* h) { return h->nrunning; }
 
+// the weight-gradient kernel of the towers' convs (board nets; before mzlc_bind).  Redoes the weight-gradient fields of the board geometry: make_geom's
+// own for MZL_WGRAD_F32, make_geom_wsplit's over them for MZL_WGRAD_BF16X3.  The one-launch-per-layer decision of the unroll steps (defer_wgrad) sizes
+// buffers and stays as mzlc_create made it.  A refusal leaves the handle as it was.
+int mzlc_set_wgrad_precision(mzlc_learner* h, int precision, std::string& err) {
+    if (precision != MZL_WGRAD_F32 && precision != MZL_WGRAD_BF16X3) { err = "wgrad_precision must be MZL_WGRAD_F32 (0) or MZL_WGRAD_BF16X3 (1), not " + std::to_string(precision); return MZL_E_INVALID; }
+    if (h->atari) { err = "wgrad_precision: MZL_NET_ATARI has no split-bf16 weight gradient (its ring and tap-set builds are float32 only); the setter needs net_kind MZL_NET_BOARD"; return MZL_E_INVALID; }
+    if (h->params) { err = "wgrad_precision is set after mzl_create and before mzl_bind"; return MZL_E_STATE; }
+    Geom g;
+    if (!make_geom(g, h->h, h->w, h->allow_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, cdiv(cdiv(h->P, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
+                   cdiv(cdiv(h->P, 16), 2) * cdiv(cdiv(h->P, 16), 2))) { err = "wgrad_precision: internal: board geometry"; return MZL_E_INVALID; }
+    if (precision == MZL_WGRAD_BF16X3) {
+        if (!make_geom_wsplit(g, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), cdiv(cdiv(h->P, 16), 2) * cdiv(cdiv(h->P, 16), 2))) {
+            err = "wgrad_precision MZL_WGRAD_BF16X3: the split planes of this board do not fit the LDS";
+            return MZL_E_INVALID;
+        }
+        if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad_bf16x3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad_bf16x3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) { err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e); return MZL_E_HIP; }
+    }
+    h->gm = g;
+    h->wsplit = precision == MZL_WGRAD_BF16X3;
+    return MZL_OK;
+}
+int mzlc_wgrad_precision(const mzlc_learner* h) { return h->wsplit ? MZL_WGRAD_BF16X3 : MZL_WGRAD_F32; }
+
 int mzlc_bind(mzlc_learner* h, float* params, float* grads, float* m, float* v) {
     h->params = params; h->grads = grads; h->m = m; h->v = v;
     h->committed = false;
@@ -1946,11 +2019,15 @@ int mzlc_debug_wgrad(mzlc_learner* h, const mzl_wgrad_call* c, const char** buil
     if (c->layout) pick.stack_rows = c->layout == 2;
     Geom g;
     bool fits;
+    WgradPick pick32 = pick;
+    if (h->wsplit) pick32.sg_force = 0;  // (the override is judged by the split planes' budget below, not by the float32 planes' that make_geom fills first)
     if (mode == MZL_WGRAD_RING) fits = make_geom(g, bh, bw, false, pick, 0, 1, 256, true, bh * bw > 240);
-    else fits = make_geom(g, bh, bw, h->allow_side, pick, B, cdiv(cdiv(J0.cout, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
+    else fits = make_geom(g, bh, bw, h->allow_side, pick32, B, cdiv(cdiv(J0.cout, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
                           cdiv(cdiv(J0.cout, 16), 2) * cdiv(cdiv(J0.cin_real, 16), 2));
     if (!fits) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of two workgroups per CU do not hold that many images per round" : "image does not fit the kernels' geometry"; return MZL_E_INVALID; }
-    if (wgrad_lds(g) > 160 * 1024) { err = "the weight-gradient planes of this geometry exceed the LDS"; return MZL_E_INVALID; }
+    if (fits && h->wsplit) fits = make_geom_wsplit(g, pick, B, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), cdiv(cdiv(J0.cout, 16), 2) * cdiv(cdiv(J0.cin_real, 16), 2));
+    if (!fits) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of one workgroup (160 KB of split planes) do not hold that many images per round" : "image does not fit the split weight gradient's planes"; return MZL_E_INVALID; }
+    if ((h->wsplit ? wgrad_split_lds(g.SPY, g.SPX) : wgrad_lds(g)) > 160 * 1024) { err = "the weight-gradient planes of this geometry exceed the LDS"; return MZL_E_INVALID; }
 
     // ---- device buffers ----
     std::vector<void*> tmp;

@@ -17,6 +17,7 @@ int mzlc_tensor_info(const mzlc_learner* h, int i, const char** name, int64_t* o
 int mzlc_num_buffers(const mzlc_learner* h);
 int mzlc_buffer_info(const mzlc_learner* h, int i, const char** name, int64_t* offset, int32_t* count);
 int64_t mzlc_num_running(const mzlc_learner* h);
+int mzlc_set_wgrad_precision(mzlc_learner* h, int precision, std::string& err);
 int mzlc_bind(mzlc_learner* h, float* params, float* grads, float* m, float* v);
 int mzlc_bind_buffers(mzlc_learner* h, float* running, int64_t* num_batches);
 int mzlc_commit(mzlc_learner* h, void* stream, std::string& err);

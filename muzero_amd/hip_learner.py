@@ -18,11 +18,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libmzlearner_hip.so')
 
 # every symbol include/mzlearner.h declares (tests/test_abi.py checks the library exports all of them)
-ABI_SYMBOLS = ['mzl_last_error', 'mzl_create', 'mzl_destroy', 'mzl_num_params', 'mzl_grad_floats', 'mzl_num_tensors', 'mzl_tensor_info',
+ABI_SYMBOLS = ['mzl_last_error', 'mzl_create', 'mzl_destroy', 'mzl_set_wgrad_precision', 'mzl_num_params', 'mzl_grad_floats', 'mzl_num_tensors', 'mzl_tensor_info',
                'mzl_num_buffers', 'mzl_num_running', 'mzl_buffer_info', 'mzl_bind_buffers', 'mzl_bind', 'mzl_commit', 'mzl_grad', 'mzl_apply',
                'mzl_replay_scratch_doubles', 'mzl_replay_sample', 'mzl_replay_update_priorities', 'mzl_replay_set_error_counters']
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
 CONV_PRECISIONS = {'f32': 0, 'bf16x3': 1}  # MZL_CONV_F32 / MZL_CONV_BF16X3 (include/mzlearner.h)
+WGRAD_PRECISIONS = {'f32': 0, 'bf16x3': 1}  # MZL_WGRAD_F32 / MZL_WGRAD_BF16X3
 
 
 class LearnerError(RuntimeError):
@@ -35,6 +36,14 @@ def _conv_precision(v):
     if not isinstance(v, (str, bool)) and v in (0, 1):
         return int(v)
     raise ValueError(f"conv_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
+
+
+def _wgrad_precision(v):
+    if isinstance(v, str) and v in WGRAD_PRECISIONS:
+        return WGRAD_PRECISIONS[v]
+    if not isinstance(v, (str, bool)) and v in (0, 1):
+        return int(v)
+    raise ValueError(f"wgrad_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
 
 
 class MzlConfig(C.Structure):
@@ -85,6 +94,8 @@ def load_library():
     L.mzl_last_error.restype = C.c_char_p
     L.mzl_create.argtypes = [C.POINTER(MzlConfig), C.c_int, C.POINTER(vp)]
     L.mzl_destroy.argtypes = [vp]
+    if hasattr(L, 'mzl_set_wgrad_precision'):  # (an older library loaded for an A/B run, tools/*_vs_parent.py, has none; wgrad_precision != 0 then fails at the call)
+        L.mzl_set_wgrad_precision.argtypes = [vp, i32]
     L.mzl_num_params.argtypes = [vp]
     L.mzl_num_params.restype = i64
     L.mzl_grad_floats.argtypes = [vp]
@@ -196,11 +207,14 @@ class HipLearner:
 
     def __init__(self, network, device, unroll_steps: int, max_batch: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  milestones: Sequence[int] = (), gamma: float = 0.1, clip_grad: bool = False, max_grad_norm: float = 40.0, grad_slices: Optional[int] = None,
-                 conv_precision=0):
+                 conv_precision=0, wgrad_precision=0):
         """conv_precision: 'f32' (0, the default) or 'bf16x3' (1): board nets only -- the towers' forward and data-gradient convs as split-bf16
-        MFMAs (csrc/mz_learn_conv_split.h); the weight gradient, BatchNorm, heads and Adam stay float32 either way."""
+        MFMAs (csrc/mz_learn_conv_split.h).  wgrad_precision: 'f32' (0, the default) or 'bf16x3' (1): board nets only, independent of
+        conv_precision -- the towers' weight gradients as split-bf16 MFMAs (csrc/mz_learn_conv_split_wgrad.h).  BatchNorm, heads and Adam stay
+        float32 either way."""
         self._h = C.c_void_p()
         self.conv_precision = _conv_precision(conv_precision)
+        self.wgrad_precision = _wgrad_precision(wgrad_precision)
         if not torch.cuda.is_available():
             raise LearnerError('HipLearner needs a GPU (no CPU fallback)')
         L = load_library()
@@ -228,6 +242,8 @@ class HipLearner:
             cfg = MzlConfig(in_dim, spec['num_actions'], spec['num_planes'], spec['hidden_dim'], spec['value_support_size'], spec['reward_support_size'],
                             unroll_steps, max_batch, grad_slices, NET_MLP, 0, 0, 0, 0, self.conv_precision)
         _check(L.mzl_create(C.byref(cfg), self.device.index or 0, C.byref(self._h)))
+        if self.wgrad_precision:  # (the default never calls the setter: the handle is what mzl_create made)
+            _check(L.mzl_set_wgrad_precision(self._h, self.wgrad_precision))
         self.K, self.A, self.in_dim, self.max_batch = unroll_steps, spec['num_actions'], in_dim, max_batch
         self.total = int(L.mzl_num_params(self._h))
         gfl = int(L.mzl_grad_floats(self._h))
