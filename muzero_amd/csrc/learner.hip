@@ -384,6 +384,16 @@ extern "C" int mzl_debug_wgrad(mz_learner* h, const mzl_wgrad_call* call, const 
     return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_wgrad: " + err);
 }
 
+// diagnostic (tests): ONE conv with its staging transform, write-through, epilogue and statistics, and the BatchNorm finalize that follows it (or a
+// finalize / k_lc_apply alone), through the conv learner's op builders and dispatcher (learner_conv.hip mzlc_debug_conv_fused); host pointers
+extern "C" int mzl_debug_conv_fused(mz_learner* h, mzl_fused_call* call, const char** build_name) {
+    if (!h || !h->conv) return fail(MZL_E_INVALID, "mzl_debug_conv_fused: needs a conv-net learner (MZL_NET_BOARD)");
+    if (!call || !build_name) return fail(MZL_E_INVALID, "mzl_debug_conv_fused: null argument");
+    std::string err;
+    const int rc = mzlc_debug_conv_fused(h->conv, call, build_name, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv_fused: " + err);
+}
+
 extern "C" int mzl_tensor_info(const mz_learner* h, int32_t i, const char** name, int64_t* offset, int32_t* rows, int32_t* cols) {
     if (h && h->conv) {
         if (mzlc_tensor_info(h->conv, i, name, offset, rows, cols) != MZL_OK) return fail(MZL_E_INVALID, "tensor index out of range");

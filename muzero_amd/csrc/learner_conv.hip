@@ -2149,3 +2149,235 @@ int mzlc_debug_wgrad(mzlc_learner* h, const mzl_wgrad_call* c, const char** buil
     *build_name = h->debug_name.c_str();
     return done(MZL_OK, "");
 }
+
+// diagnostic (tests): ONE conv of a BatchNorm tower as the update runs it -- staging transform (all four IN_ modes), write-through, epilogue (skip, mask,
+// ST_FWD / ST_BWD partials) and the finalize kernel that follows -- or two such convs of different layers in one paired launch (pair), a finalize
+// kernel alone on host-supplied partials of any group count (finalize), or k_lc_apply alone (apply).  Production code throughout: the packers, make_geom
+// as mzlc_create calls it for that batch, the Sched builders conv_base / op_conv / op_bnfwd / op_bnbwd / op_apply with the LcConv fields set as tower_fwd and
+// tower_bwd set them, launch_ops.  The builders point at the handle's weights, statistics, parameters, gradients and running statistics: every one of
+// those pointers is redirected to a temporary buffer of this call (NULL stream), the handle is not touched.  *build_name stays valid until the next call:
+//   "<precision> <kernel> NPT= SIDE= G= groups= z= mode=IN_.. stat=ST_.. dir=forward|dgrad pair=0|1 fin=none|fwd|bwd"   (conv, pair)
+//   "<precision> k_lc_bn_fwd|k_lc_bn_bwd groups= C= cpad= accumulate="   (finalize)        "<precision> k_lc_apply n= C= hw= res=0|1"   (apply)
+int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build_name, std::string& err) {
+    if (h->atari) { err = "board nets only (MZL_NET_BOARD)"; return MZL_E_INVALID; }
+    const int mode = c->mode, B = c->batch, bh = c->h, bw = c->w;
+    if (mode < MZL_FUSED_CONV || mode > MZL_FUSED_APPLY) { err = "mode must be 0 (conv), 1 (pair), 2 (finalize) or 3 (apply)"; return MZL_E_INVALID; }
+    if (B < 1 || B > 4096 || bh < 1 || bw < 1 || bh * bw > 240) { err = "bad shape: batch in [1, 4096], h * w in [1, 240]"; return MZL_E_INVALID; }
+    const int nj = mode == MZL_FUSED_PAIR ? 2 : 1, hw = bh * bw;
+    for (int l = 0; l < nj; l++) {
+        const mzl_fused_conv& J = c->conv[l];
+        if (J.cin < 1 || J.cin > 4096 || J.cout < 1 || J.cout > 1024) { err = "bad channels: cin in [1, 4096], cout in [1, 1024]"; return MZL_E_INVALID; }
+        if (mode == MZL_FUSED_APPLY) {
+            if (!J.in0 || !J.coef || !J.out) { err = "null argument (mode apply: in0 = y, coef, out)"; return MZL_E_INVALID; }
+            continue;
+        }
+        if (J.finalize < 0 || J.finalize > 2) { err = "finalize must be 0 (none), 1 (OP_BNFWD) or 2 (OP_BNBWD)"; return MZL_E_INVALID; }
+        if (J.finalize == 1 && (!J.gamma || !J.beta || !J.coef_out || !J.save_out)) { err = "null argument (finalize 1: gamma, beta, coef_out, save_out)"; return MZL_E_INVALID; }
+        if (J.finalize == 1 && ((J.running_mean != nullptr) != (J.running_var != nullptr))) { err = "inconsistent arguments: running_mean and running_var come together"; return MZL_E_INVALID; }
+        if (J.finalize == 2 && (!J.gamma || !J.save_in || !J.coef_out || !J.dgamma || !J.dbeta)) { err = "null argument (finalize 2: gamma, save_in, coef_out, dgamma, dbeta)"; return MZL_E_INVALID; }
+        if (mode == MZL_FUSED_FINALIZE) {
+            if (J.finalize == 0 || !J.part_in) { err = "null argument (mode finalize: finalize 1 or 2 and part_in)"; return MZL_E_INVALID; }
+            if (c->groups < 1 || c->groups > (1 << 20) || !(c->count >= 1.0f)) { err = "mode finalize: groups in [1, 2^20], count at least 1"; return MZL_E_INVALID; }
+            continue;
+        }
+        if (!J.weight || !J.in0 || !J.out) { err = "null argument (weight, in0, out)"; return MZL_E_INVALID; }
+        if (J.direction != 0 && J.direction != 1) { err = "direction must be 0 (forward) or 1 (data gradient)"; return MZL_E_INVALID; }
+        if (J.in_mode < IN_IDENT || J.in_mode > IN_BNRES) { err = "in_mode must be 0 (IN_IDENT), 1 (IN_BNRELU), 2 (IN_BNBWD) or 3 (IN_BNRES)"; return MZL_E_INVALID; }
+        if (J.stat_mode < ST_NONE || J.stat_mode > ST_BWD) { err = "stat_mode must be 0 (ST_NONE), 1 (ST_FWD) or 2 (ST_BWD)"; return MZL_E_INVALID; }
+        if ((J.in_mode != IN_IDENT) != (J.coef != nullptr)) { err = "inconsistent arguments: coef comes with a staging transform (in_mode 1, 2, 3) and only with one"; return MZL_E_INVALID; }
+        if ((J.in_mode == IN_BNBWD || J.in_mode == IN_BNRES) != (J.in1 != nullptr)) { err = "inconsistent arguments: in1 comes with IN_BNBWD and IN_BNRES and only with them"; return MZL_E_INVALID; }
+        if ((J.mat_preload != nullptr) != (J.mat_out != nullptr)) { err = "inconsistent arguments: mat_preload and mat_out come together"; return MZL_E_INVALID; }
+        if (J.mat_out && J.in_mode != IN_BNRELU && J.in_mode != IN_BNRES) { err = "inconsistent arguments: the write-through (mat_out) exists for IN_BNRELU and IN_BNRES staging only"; return MZL_E_INVALID; }
+        if (J.mcoef && !J.mask) { err = "inconsistent arguments: mcoef without mask"; return MZL_E_INVALID; }
+        if (J.partner_is_mask && (!J.mask || J.partner)) { err = "inconsistent arguments: partner_is_mask needs mask and no partner array of its own"; return MZL_E_INVALID; }
+        if ((J.stat_mode == ST_BWD) != (J.partner != nullptr || J.partner_is_mask != 0)) { err = "inconsistent arguments: ST_BWD needs a partner (or partner_is_mask), and a partner needs ST_BWD"; return MZL_E_INVALID; }
+        if ((J.stat_mode != ST_NONE) != (J.part != nullptr)) { err = "inconsistent arguments: part comes with a stat_mode and only with one"; return MZL_E_INVALID; }
+        if (J.finalize && J.finalize != J.stat_mode) { err = "inconsistent arguments: finalize 1 follows ST_FWD, finalize 2 follows ST_BWD"; return MZL_E_INVALID; }
+    }
+    if (nj == 2 && (c->conv[0].in_mode != c->conv[1].in_mode || c->conv[0].finalize != c->conv[1].finalize)) { err = "mode pair: the two jobs share in_mode and finalize (one kernel build per launch)"; return MZL_E_INVALID; }
+    if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+
+    std::vector<void*> tmp;
+    const bool sv_bad = h->bad_dispatch;
+    auto A = [&](void** p, size_t bytes, int fill = 0) {
+        if (hipMalloc(p, bytes + 256) != hipSuccess) return false;
+        tmp.push_back(*p);
+        return hipMemset(*p, fill, bytes + 256) == hipSuccess;
+    };
+    auto done = [&](int rc, const char* m) {
+        (void)hipDeviceSynchronize();
+        for (void* p : tmp) (void)hipFree(p);
+        h->bad_dispatch = sv_bad;
+        if (rc != MZL_OK) { err = m; (void)hipGetLastError(); }
+        return rc;
+    };
+    // host [rows][C] -> device [3][cpad] (rows beyond `rows` and padding channels zero), as the finalize kernels leave their coefficient tables
+    auto up_rows = [&](float** d, const float* src, int rows, int C, int cpad) {
+        std::vector<float> t((size_t)3 * cpad, 0.0f);
+        for (int k = 0; k < rows; k++)
+            for (int ch = 0; ch < C; ch++) t[(size_t)k * cpad + ch] = src[(size_t)k * C + ch];
+        return A((void**)d, t.size() * 4) && hipMemcpy(*d, t.data(), t.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    auto up = [&](float** d, const float* src, size_t n) { return A((void**)d, n * 4) && (!src || hipMemcpy(*d, src, n * 4, hipMemcpyHostToDevice) == hipSuccess); };
+    hipStream_t st = nullptr;
+    char name[320];
+    const char* prec = h->split ? "bf16x3" : "f32";
+
+    // ---- geometry: make_geom as mzlc_create calls it, for this batch and the first job's layer ----
+    Geom g;
+    if (!make_geom(g, bh, bw, h->allow_side && !c->no_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : B, cdiv(cdiv(c->conv[0].cout, 16), 4) * 2, h->num_cus,
+                   !getenv("MZLC_NO_WGRAD_STACK"), false, cdiv(cdiv(c->conv[0].cout, 16), 2) * cdiv(cdiv(c->conv[0].cout, 16), 2))) {
+        err = "image does not fit the conv kernels' tiling";
+        return MZL_E_INVALID;
+    }
+
+    if (mode == MZL_FUSED_APPLY) {
+        const mzl_fused_conv& J = c->conv[0];
+        const int C = J.cin, cpad = pad16(C);
+        const size_t n = (size_t)B * C * hw;
+        float *d_y = nullptr, *d_res = nullptr, *d_coef = nullptr, *d_out = nullptr;
+        if (!up(&d_y, J.in0, n) || (J.in1 && !up(&d_res, J.in1, n)) || !up_rows(&d_coef, J.coef, 2, C, cpad) || !A((void**)&d_out, n * 4, 0xff)) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        const Sched s{h, B, 0, false, g, C};
+        const Op o = s.op_apply(d_y, d_res, d_coef, d_out);
+        h->bad_dispatch = false;
+        const int rc = launch_ops(h, &o, nullptr, st);
+        if (rc != 0 || h->bad_dispatch) return done(MZL_E_INVALID, "no kernel for this op");
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(MZL_E_HIP, "k_lc_apply failed to launch or run");
+        if (hipMemcpy(J.out, d_out, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+        snprintf(name, sizeof(name), "%s k_lc_apply n=%lld C=%d hw=%d res=%d", prec, o.ap.n, C, hw, J.in1 ? 1 : 0);
+        h->debug_name = name;
+        *build_name = h->debug_name.c_str();
+        return done(MZL_OK, "");
+    }
+
+    struct Dev {
+        float *w = nullptr, *packed = nullptr, *in0 = nullptr, *in1 = nullptr, *coef = nullptr, *mat = nullptr, *skip = nullptr, *mask = nullptr, *mcoef = nullptr, *partner = nullptr,
+              *out = nullptr, *part = nullptr, *gamma = nullptr, *beta = nullptr, *save_in = nullptr, *coef_out = nullptr, *save_out = nullptr, *rm = nullptr, *rv = nullptr,
+              *dgamma = nullptr, *dbeta = nullptr;
+        int64_t* nbt = nullptr;
+        void* job = nullptr;
+        int c_in = 0, c_out = 0, cpo = 0, groups = 0;
+    };
+    Dev d[2];
+    std::vector<Op> ops[2];
+    for (int l = 0; l < nj; l++) {
+        const mzl_fused_conv& J = c->conv[l];
+        Dev& D = d[l];
+        const bool conv = mode != MZL_FUSED_FINALIZE;
+        D.c_in = conv && J.direction == 1 ? J.cout : J.cin;
+        D.c_out = conv && J.direction == 1 ? J.cin : J.cout;
+        D.cpo = pad16(D.c_out);
+        D.groups = conv ? cdiv(B, g.G) : c->groups;
+        const int cpi = pad16(D.c_in), C = D.c_out;
+        const size_t n_in = (size_t)B * D.c_in * hw, n_out = (size_t)B * D.c_out * hw, n_part = (size_t)D.groups * D.cpo * 4;
+        LayerInfo L;  // the layer of the conv (its packed copies at offset 0 of this call's buffer) and the BatchNorm behind the conv's OUTPUT
+        L.cin_real = J.cin; L.cin = J.cin; L.cout = J.cout; L.cin_d = conv && J.direction == 1 ? J.cin : 0;
+        L.n_cb = cdiv(L.cin, 16); L.co_tiles = cdiv(L.cout, 16); L.n_cb_d = cdiv(L.cout, 16); L.co_tiles_d = L.cin_d ? cdiv(L.cin_d, 16) : 0;
+        L.n_cb3 = cdiv(L.cin, 32); L.n_cb3_d = cdiv(L.cout, 32);
+        L.bn.C = C; L.bn.cpad = D.cpo;
+        Sched s{h, B, l, nj == 2, g, C};
+        bool ok = A((void**)&D.part, n_part * 4, 0xff);
+        if (conv) {
+            const bool dg = J.direction == 1;
+            const int co_tiles = dg ? L.co_tiles_d : L.co_tiles, n_cb = h->split ? (dg ? L.n_cb3_d : L.n_cb3) : (dg ? L.n_cb_d : L.n_cb);
+            const size_t n_w = (size_t)J.cout * J.cin * 9, n_packed = (size_t)co_tiles * n_cb * 9 * (h->split ? 192 * 4 : 256);
+            const size_t lds = h->split ? conv_split_lds(g.G, bh, bw, cpi) : conv_lds(g.qstride, cpi);
+            if (lds > 160 * 1024) return done(MZL_E_INVALID, "image too large for the conv kernel's LDS layout");
+            ok = ok && up(&D.w, J.weight, n_w) && A((void**)&D.packed, n_packed * 4) && up(&D.in0, J.in0, n_in) && A((void**)&D.out, n_out * 4, 0xff) &&
+                 A(&D.job, sizeof(LcPackSplitJob) > sizeof(LcPackJob) ? sizeof(LcPackSplitJob) : sizeof(LcPackJob));
+            if (J.in1) ok = ok && up(&D.in1, J.in1, n_in);
+            if (J.coef) ok = ok && up_rows(&D.coef, J.coef, 3, D.c_in, cpi);
+            if (J.mat_out) ok = ok && up(&D.mat, J.mat_preload, n_in);
+            if (J.skip) ok = ok && up(&D.skip, J.skip, n_out);
+            if (J.mask) ok = ok && up(&D.mask, J.mask, n_out);
+            if (J.mcoef) ok = ok && up_rows(&D.mcoef, J.mcoef, 2, C, D.cpo);
+            if (J.partner) ok = ok && up(&D.partner, J.partner, n_out);
+            if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+            // the production packers on a one-layer table: only the copy of the asked direction exists (the other has no tiles)
+            if (h->split) {
+                LcPackSplitJob j{};
+                j.w_off = 0; j.cout = J.cout; j.cin = J.cin; j.cin_d = L.cin_d;
+                if (!dg) { j.n_cb = n_cb; j.co_tiles = co_tiles; } else { j.n_cb_d = n_cb; j.co_tiles_d = co_tiles; }
+                if (hipMemcpy(D.job, &j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+                hipLaunchKernelGGL(k_lc_pack_bf16x3, dim3(64, 1), dim3(256), 0, st, reinterpret_cast<const LcPackSplitJob*>(D.job), D.w, reinterpret_cast<u32x4*>(D.packed));
+            } else {
+                LcPackJob j{};
+                j.w_off = 0; j.cout = J.cout; j.cin = J.cin; j.cin_d = L.cin_d;
+                if (!dg) { j.n_cb = n_cb; j.co_tiles = co_tiles; } else { j.n_cb_d = n_cb; j.co_tiles_d = co_tiles; }
+                if (hipMemcpy(D.job, &j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+                hipLaunchKernelGGL(k_lc_pack, dim3(64, 1), dim3(256), 0, st, reinterpret_cast<const LcPackJob*>(D.job), D.w, D.packed);
+            }
+            LcConv k = s.conv_base(L, dg);  // (the fields below: as tower_fwd / tower_bwd fill them)
+            k.w = D.packed;
+            k.in0 = D.in0; k.in1 = D.in1; k.coef = D.coef; k.in_mode = J.in_mode; k.mat_out = D.mat; k.out = D.out;
+            k.skip = D.skip; k.mask = D.mask; k.mcoef = D.mcoef; k.partner = J.partner_is_mask ? D.mask : D.partner;
+            k.stat_mode = J.stat_mode; k.stat_part = J.stat_mode != ST_NONE ? D.part : nullptr;
+            if (k.cin_real != D.c_in || k.cout != D.c_out || k.cpad_out != D.cpo || k.cpad_in != cpi) return done(MZL_E_STATE, "internal: conv_base disagrees with the call's channels");
+            ops[l].push_back(s.op_conv(k));
+        } else {
+            ok = ok && hipMemcpy(D.part, J.part_in, (size_t)D.groups * D.cpo * (J.finalize == 1 ? 4 : 2) * 4, hipMemcpyHostToDevice) == hipSuccess;
+        }
+        if (J.finalize == 1) {
+            ok = ok && up(&D.gamma, J.gamma, C) && up(&D.beta, J.beta, C) && A((void**)&D.coef_out, (size_t)3 * D.cpo * 4, 0xff) && A((void**)&D.save_out, (size_t)2 * D.cpo * 4, 0xff);
+            if (J.running_mean) ok = ok && up(&D.rm, J.running_mean, C) && up(&D.rv, J.running_var, C);
+            if (J.num_batches) ok = ok && A((void**)&D.nbt, 8) && hipMemcpy(D.nbt, J.num_batches, 8, hipMemcpyHostToDevice) == hipSuccess;
+            if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+            Op o = s.op_bnfwd(L, D.coef_out, D.save_out);
+            o.bf.part = D.part; o.bf.gamma = D.gamma; o.bf.beta = D.beta; o.bf.running_mean = D.rm; o.bf.running_var = D.rv; o.bf.num_batches = D.nbt;
+            if (!conv) { o.bf.groups = D.groups; o.bf.count = c->count; }
+            ops[l].push_back(o);
+        } else if (J.finalize == 2) {
+            ok = ok && up(&D.gamma, J.gamma, C) && up_rows(&D.save_in, J.save_in, 2, C, D.cpo) && A((void**)&D.coef_out, (size_t)3 * D.cpo * 4, 0xff) && up(&D.dgamma, J.dgamma, C) &&
+                 up(&D.dbeta, J.dbeta, C);
+            if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+            Op o = s.op_bnbwd(L, D.save_in, D.coef_out, D.groups, J.accumulate ? 1 : 0);
+            o.bb.part = D.part; o.bb.gamma = D.gamma; o.bb.dgamma = D.dgamma; o.bb.dbeta = D.dbeta;
+            if (!conv) o.bb.count = c->count;
+            ops[l].push_back(o);
+        }
+        if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+    }
+    if (nj == 2 && ops[0].size() != ops[1].size()) return done(MZL_E_STATE, "internal: op lists of the pair do not line up");
+
+    // ---- launch ----
+    h->bad_dispatch = false;
+    int rc = 0;
+    for (size_t i = 0; i < ops[0].size() && rc == 0; i++) rc = launch_ops(h, &ops[0][i], nj == 2 ? &ops[1][i] : nullptr, st);
+    const bool bad = h->bad_dispatch;
+    const bool ran = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (rc != 0 || bad) return done(MZL_E_INVALID, "launch_ops refused the job: no kernel build for it (a conv that leaves ST_FWD statistics carries no skip and no mask)");
+    if (!ran) return done(MZL_E_HIP, "the kernels failed to launch or run");
+    for (int l = 0; l < nj; l++) {
+        const mzl_fused_conv& J = c->conv[l];
+        const Dev& D = d[l];
+        const int C = D.c_out;
+        const size_t n_in = (size_t)B * D.c_in * hw, n_out = (size_t)B * D.c_out * hw;
+        auto dn = [&](void* dst, const void* src, size_t bytes) { return !dst || !src || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+        bool ok = true;
+        if (mode != MZL_FUSED_FINALIZE) {
+            ok = dn(J.out, D.out, n_out * 4) && dn(J.mat_out, D.mat, n_in * 4);
+            if (J.stat_mode != ST_NONE) ok = ok && dn(J.part, D.part, (size_t)D.groups * D.cpo * (J.stat_mode == ST_FWD ? 4 : 2) * 4);
+        }
+        if (J.finalize) ok = ok && dn(J.coef_out, D.coef_out, (size_t)3 * D.cpo * 4);
+        if (J.finalize == 1) ok = ok && dn(J.save_out, D.save_out, (size_t)2 * D.cpo * 4) && dn(J.running_mean, D.rm, (size_t)C * 4) && dn(J.running_var, D.rv, (size_t)C * 4) && dn(J.num_batches, D.nbt, 8);
+        if (J.finalize == 2) ok = ok && dn(J.dgamma, D.dgamma, (size_t)C * 4) && dn(J.dbeta, D.dbeta, (size_t)C * 4);
+        if (!ok) return done(MZL_E_HIP, "hipMemcpy failed");
+    }
+    const mzl_fused_conv& J0 = c->conv[0];
+    if (mode == MZL_FUSED_FINALIZE) {
+        snprintf(name, sizeof(name), "%s %s groups=%d C=%d cpad=%d accumulate=%d", prec, J0.finalize == 1 ? "k_lc_bn_fwd" : "k_lc_bn_bwd", d[0].groups, d[0].c_out, d[0].cpo, J0.accumulate ? 1 : 0);
+    } else {
+        static const char* in_names[4] = {"IN_IDENT", "IN_BNRELU", "IN_BNBWD", "IN_BNRES"};
+        static const char* st_names[3] = {"ST_NONE", "ST_FWD", "ST_BWD"};
+        static const char* fin_names[3] = {"none", "fwd", "bwd"};
+        const Op& o = ops[0][0];
+        int z = cdiv(o.conv.co_tiles, 4);
+        if (nj == 2 && cdiv(ops[1][0].conv.co_tiles, 4) > z) z = cdiv(ops[1][0].conv.co_tiles, 4);
+        c->groups = d[0].groups;
+        snprintf(name, sizeof(name), "%s %s NPT=%d SIDE=%d G=%d groups=%d z=%d mode=%s stat=%s dir=%s pair=%d fin=%s", prec, h->split ? "k_lc_conv_bf16x3" : "k_lc_conv", o.npt,
+                 o.side15 ? 15 : 0, o.conv.G, d[0].groups, z, in_names[J0.in_mode], st_names[J0.stat_mode], J0.direction == 0 ? "forward" : "dgrad", nj == 2 ? 1 : 0, fin_names[J0.finalize]);
+    }
+    h->debug_name = name;
+    *build_name = h->debug_name.c_str();
+    return done(MZL_OK, "");
+}

@@ -57,3 +57,46 @@ struct mzl_wgrad_call {
     mzl_wgrad_layer layer[2];  // [1]: the second layer of mode `pair`
 };
 int mzlc_debug_wgrad(mzlc_learner* h, const mzl_wgrad_call* c, const char** build_name, std::string& err);
+
+// diagnostic (tests): ONE conv of a BatchNorm tower as the update runs it (mzl_debug_conv_fused; exported, not part of include/mzlearner.h): staging
+// transform, write-through, epilogue (skip, mask, statistics) and the finalize kernel behind it.  Host pointers throughout; null = absent.
+// direction 0: the forward conv, c_in = cin input and c_out = cout output channels; 1: the data gradient (c_in = cout, c_out = cin).
+struct mzl_fused_conv {
+    const float* weight;       // [cout][cin][3][3], the LAYER's weight in both directions
+    const float* in0;          // [B][c_in][h][w]      (mode apply: y, [B][cin][h][w])
+    const float* in1;          // the same shape: y (IN_BNBWD) | the residual (IN_BNRES; mode apply: the residual or null)
+    const float* coef;         // [3][c_in]: (a, b, -) | (c1, c2, c3); null with in_mode 0   (mode apply: [2][cin])
+    const float* mat_preload;  // [B][c_in][h][w]: what mat_out holds before the launch; null: no write-through
+    const float* skip;         // [B][c_out][h][w] or null
+    const float* mask;         // [B][c_out][h][w] or null
+    const float* mcoef;        // [2][c_out] or null
+    const float* partner;      // [B][c_out][h][w] or null (partner_is_mask: the mask buffer itself is passed as the partner)
+    const float* gamma;        // [c_out]  finalize 1, 2
+    const float* beta;         // [c_out]  finalize 1
+    const float* save_in;      // [2][c_out] (mean, invstd)  finalize 2
+    const float* part_in;      // mode finalize: [groups][pad16(c_out)][4 | 2]
+    float* out;                // [B][c_out][h][w]; preset to NaN bits, so an unwritten element shows
+    float* mat_out;            // [B][c_in][h][w]
+    float* part;               // [groups][pad16(c_out)][4 | 2] as the conv wrote them (NaN bits where it wrote nothing), or null
+    float* coef_out;           // [3][pad16(c_out)]  finalize 1, 2 (NaN bits before the launch: the padding channels show)
+    float* save_out;           // [2][pad16(c_out)]  finalize 1
+    float* running_mean;       // [c_out] in / out, or null  finalize 1
+    float* running_var;
+    float* dgamma;             // [c_out] in / out  finalize 2
+    float* dbeta;
+    int64_t* num_batches;      // in / out, or null  finalize 1
+    int32_t direction, in_mode, stat_mode;  // IN_* and ST_* of mz_learn_conv.h
+    int32_t finalize;          // 0 none, 1 OP_BNFWD (needs ST_FWD), 2 OP_BNBWD (needs ST_BWD)
+    int32_t accumulate, partner_is_mask, cin, cout;
+};
+enum { MZL_FUSED_CONV = 0, MZL_FUSED_PAIR = 1, MZL_FUSED_FINALIZE = 2, MZL_FUSED_APPLY = 3 };
+struct mzl_fused_call {
+    int32_t mode;        // MZL_FUSED_*
+    int32_t batch, h, w;
+    int32_t groups;      // mode finalize: in, the groups of part_in; otherwise out: the image groups (workgroup rows) of the conv
+    int32_t no_side;     // 1: the generic build on a 15 x 15 board too (0: the handle's choice)
+    float count;         // mode finalize: the statistics' element count (the update: batch * h * w)
+    int32_t pad_;
+    mzl_fused_conv conv[2];  // [1]: the second job of mode pair
+};
+int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build_name, std::string& err);

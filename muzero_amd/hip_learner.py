@@ -82,6 +82,25 @@ class MzlWgradCall(C.Structure):
 
 WGRAD_MODES = {'plain': 0, 'pair': 1, 'steps': 2, 'ring': 3}
 
+_FUSED_IN = ('weight', 'in0', 'in1', 'coef', 'mat_preload', 'skip', 'mask', 'mcoef', 'partner', 'gamma', 'beta', 'save_in', 'part_in')
+_FUSED_OUT = ('out', 'mat_out', 'part', 'coef_out', 'save_out', 'running_mean', 'running_var', 'dgamma', 'dbeta', 'num_batches')
+
+
+class MzlFusedConv(C.Structure):
+    """mzl_fused_conv (csrc/mz_learn_conv_host.h): one job's host operands of mzl_debug_conv_fused."""
+    _fields_ = [(n, C.c_void_p) for n in _FUSED_IN + _FUSED_OUT] + \
+               [(n, C.c_int32) for n in ('direction', 'in_mode', 'stat_mode', 'finalize', 'accumulate', 'partner_is_mask', 'cin', 'cout')]
+
+
+class MzlFusedCall(C.Structure):
+    """mzl_fused_call (csrc/mz_learn_conv_host.h)."""
+    _fields_ = [(n, C.c_int32) for n in ('mode', 'batch', 'h', 'w', 'groups', 'no_side')] + [('count', C.c_float), ('pad_', C.c_int32), ('conv', MzlFusedConv * 2)]
+
+
+FUSED_MODES = {'conv': 0, 'pair': 1, 'finalize': 2, 'apply': 3}
+IN_MODES = {'ident': 0, 'bnrelu': 1, 'bnbwd': 2, 'bnres': 3}
+STAT_MODES = {None: 0, 'none': 0, 'fwd': 1, 'bwd': 2}
+
 
 def load_library():
     global _lib
@@ -122,6 +141,8 @@ def load_library():
         L.mzl_debug_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     if hasattr(L, 'mzl_debug_wgrad'):
         L.mzl_debug_wgrad.argtypes = [vp, C.POINTER(MzlWgradCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
+    if hasattr(L, 'mzl_debug_conv_fused'):
+        L.mzl_debug_conv_fused.argtypes = [vp, C.POINTER(MzlFusedCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     _lib = L
     return L
 
@@ -546,6 +567,128 @@ class HipLearner:
         name = C.c_char_p()
         _check(lib.mzl_debug_wgrad(self._h, C.byref(call), C.byref(name)))
         return (tuple(outs) if mode == 'pair' else out0), (name.value or b'').decode()
+
+    def debug_conv_fused(self, job, mode: str = 'conv', second=None, no_side: bool = False, batch: Optional[int] = None, hw=None, count: Optional[float] = None):
+        """Diagnostic (tests): ONE conv of a BatchNorm tower as the update runs it (mzl_debug_conv_fused: the op builders, make_geom, launch_ops).
+        `job` (and `second`, mode 'pair') is a dict:
+          weight [cout, cin, 3, 3], direction 0 forward | 1 data gradient, in0 [B, c_in, h, w], in_mode 'ident' | 'bnrelu' | 'bnbwd' | 'bnres', in1, coef
+          [3, c_in]; mat_preload (asks for the write-through); skip, mask, mcoef [2, c_out], partner (an array, or the string 'mask': the mask buffer
+          itself); stat 'fwd' | 'bwd' | None; finalize 'fwd' | 'bwd' | None with gamma, beta, save [2, c_out], running_mean, running_var, num_batches,
+          accumulate, dgamma, dbeta.
+        mode 'finalize': part [groups, pad16(C), 4 | 2], finalize, count and the finalize operands, no conv; mode 'apply': y, res (or None), coef [2, C].
+        Returns (dict of what came back -- out, mat_out, part, groups, coef [3, cpad], save [2, cpad], running_mean, running_var, num_batches, dgamma,
+        dbeta -- or a tuple of two for a pair, the name of what ran)."""
+        lib = load_library()
+        if not hasattr(lib, 'mzl_debug_conv_fused'):
+            raise LearnerError('mzl_debug_conv_fused: this library has no such hook')
+        if mode not in FUSED_MODES:
+            raise LearnerError(f'mzl_debug_conv_fused: mode {mode!r} (one of {sorted(FUSED_MODES)})')
+        call = MzlFusedCall()
+        keep = []
+        f32 = np.float32
+
+        def arr(a, dt=f32):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            keep.append(a)
+            return a.ctypes.data
+
+        def new(shape, src=None, dt=f32):
+            a = np.zeros(shape, dt) if src is None else np.array(src, dt).reshape(shape)
+            keep.append(a)
+            return a
+
+        def fill(J, job):
+            res = {}
+            fin = STAT_MODES[job.get('finalize')]
+            J.finalize, J.accumulate = fin, int(bool(job.get('accumulate', False)))
+            if mode == 'apply':
+                y = np.ascontiguousarray(job['y'], f32)
+                B, Cc, bh, bw = y.shape
+                J.cin = J.cout = Cc
+                res['out'] = new(y.shape)
+                J.in0, J.in1, J.coef, J.out = arr(y), arr(job.get('res')), arr(job['coef']), res['out'].ctypes.data
+                return res, (B, bh, bw)
+            if mode == 'finalize':
+                part = np.ascontiguousarray(job['part'], f32)
+                Cc = int(np.shape(job['gamma'])[0])
+                J.cin = J.cout = Cc
+                J.part_in = arr(part)
+                res['groups'] = int(part.shape[0])
+                shape = (batch or 1,) + tuple(hw or (1, 1))
+            else:
+                weight, in0 = np.ascontiguousarray(job['weight'], f32), np.ascontiguousarray(job['in0'], f32)
+                if weight.ndim != 4 or in0.ndim != 4 or tuple(weight.shape[2:]) != (3, 3):
+                    raise LearnerError('mzl_debug_conv_fused: weight [cout, cin, 3, 3] and in0 [B, channels, h, w]')
+                J.direction = int(job.get('direction', 0))
+                J.cout, J.cin = int(weight.shape[0]), int(weight.shape[1])
+                c_in, c_out = (J.cout, J.cin) if J.direction else (J.cin, J.cout)
+                B, xc, bh, bw = in0.shape
+                if xc != c_in:
+                    raise LearnerError(f'mzl_debug_conv_fused: in0 {in0.shape} does not fit weight {weight.shape} in direction {J.direction}')
+                shape = (B, bh, bw)
+                oshape = (B, c_out, bh, bw)
+                for k, shp in (('in1', in0.shape), ('mat_preload', in0.shape), ('coef', (3, c_in)), ('skip', oshape), ('mask', oshape), ('mcoef', (2, c_out))):
+                    if job.get(k) is not None and tuple(np.shape(job[k])) != tuple(shp):
+                        raise LearnerError(f'mzl_debug_conv_fused: {k} {np.shape(job[k])} is not {tuple(shp)}')
+                J.in_mode, J.stat_mode = IN_MODES[job.get('in_mode', 'ident')], STAT_MODES[job.get('stat')]
+                J.weight, J.in0, J.in1, J.coef = arr(weight), arr(in0), arr(job.get('in1')), arr(job.get('coef'))
+                J.skip, J.mask, J.mcoef = arr(job.get('skip')), arr(job.get('mask')), arr(job.get('mcoef'))
+                partner = job.get('partner')
+                if isinstance(partner, str):
+                    J.partner_is_mask = 1
+                else:
+                    J.partner = arr(partner)
+                res['out'] = new(oshape)
+                J.out = res['out'].ctypes.data
+                if job.get('mat_preload') is not None:
+                    res['mat_out'] = new(in0.shape)
+                    J.mat_preload, J.mat_out = arr(job['mat_preload']), res['mat_out'].ctypes.data
+                Cc = c_out
+            cpad = (Cc + 15) // 16 * 16
+            if mode != 'finalize' and J.stat_mode:
+                res['part'] = new((shape[0], cpad, 4 if J.stat_mode == 1 else 2))  # (at most one group per image; cut to the groups that ran)
+                J.part = res['part'].ctypes.data
+            if fin:
+                res['coef'] = new((3, cpad))
+                J.coef_out, J.gamma = res['coef'].ctypes.data, arr(job['gamma'])
+            if fin == 1:
+                res['save'] = new((2, cpad))
+                J.save_out, J.beta = res['save'].ctypes.data, arr(job['beta'])
+                if job.get('running_mean') is not None:
+                    res['running_mean'], res['running_var'] = new((Cc,), job['running_mean']), new((Cc,), job['running_var'])
+                    J.running_mean, J.running_var = res['running_mean'].ctypes.data, res['running_var'].ctypes.data
+                if job.get('num_batches') is not None:
+                    res['num_batches'] = new((1,), [job['num_batches']], np.int64)
+                    J.num_batches = res['num_batches'].ctypes.data
+            if fin == 2:
+                res['dgamma'], res['dbeta'] = new((Cc,), job.get('dgamma')), new((Cc,), job.get('dbeta'))
+                J.save_in, J.dgamma, J.dbeta = arr(job['save']), res['dgamma'].ctypes.data, res['dbeta'].ctypes.data
+            return res, shape
+
+        res0, shape = fill(call.conv[0], job)
+        results = [res0]
+        if mode == 'pair':
+            if second is None:
+                raise LearnerError("mzl_debug_conv_fused: mode 'pair' needs `second`")
+            res1, shape1 = fill(call.conv[1], second)
+            if shape1 != shape:
+                raise LearnerError('mzl_debug_conv_fused: the two jobs of a pair share batch and board')
+            results.append(res1)
+        call.mode, call.batch, call.h, call.w, call.no_side = FUSED_MODES[mode], int(shape[0]), int(shape[1]), int(shape[2]), int(bool(no_side))
+        if mode == 'finalize':
+            call.groups, call.count = res0['groups'], float(count)
+        name = C.c_char_p()
+        _check(lib.mzl_debug_conv_fused(self._h, C.byref(call), C.byref(name)))
+        for r in results:
+            if mode in ('conv', 'pair'):
+                r['groups'] = int(call.groups)
+                if 'part' in r:
+                    r['part'] = r['part'][:call.groups]
+            if 'num_batches' in r:
+                r['num_batches'] = int(r['num_batches'][0])
+        return (tuple(results) if mode == 'pair' else res0), (name.value or b'').decode()
 
     def close(self) -> None:
         if self._h:

@@ -86,7 +86,7 @@ def test_header_and_ctypes_mirror_carry_the_field_last():
     assert C.sizeof(hl.MzlConfig) == 4 * len(fields) and hl.MzlConfig.conv_precision.offset == 4 * (len(fields) - 1)
     assert hl.MzlConfig().conv_precision == 0  # a zero-initialised config stays float32
     # the diagnostic hooks are exported, not declared
-    for hook in ('mzl_debug_conv', 'mzl_debug_wgrad'):
+    for hook in ('mzl_debug_conv', 'mzl_debug_wgrad', 'mzl_debug_conv_fused'):
         assert hook not in re.sub(r'/\*.*?\*/', '', text, flags=re.S) and hook not in hl.ABI_SYMBOLS
 
 
