@@ -165,7 +165,8 @@ typedef struct {
 int64_t mzl_replay_scratch_doubles(int64_t capacity);
 /* Optional (round 6): a device int32[2] that the replay kernels bump where the reference would have raised -- [0] a draw from an EMPTY replay
  * (replay.py:83-84; the draw returns slot 0), [1] a non-finite or negative priority in mzl_replay_update_priorities (replay.py:106-110; the value
- * is skipped).  The kernels cannot raise: the caller reads the counters at a point where it synchronises anyway.  NULL (default): no counting.
+ * is skipped: of a repeated index the last VALID value wins, a slot with none keeps its priority; every finite float32 >= 0 is valid).  The
+ * kernels cannot raise: the caller reads the counters at a point where it synchronises anyway.  NULL (default): no counting.
  * Process-wide; the pointer is read when a call is enqueued. */
 int mzl_replay_set_error_counters(int32_t* d_counters);
 int mzl_replay_sample(const mzl_replay_draw* draw, void* stream);

@@ -6,7 +6,8 @@
 //   proportional (replay.py:90-98): w_i = priority_i ^ alpha, inverse-CDF picks on the inclusive prefix sums (float64; what
 //       np.random.choice(p = w / sum w) does with its own uniforms: searchsorted(cumsum, u, side='right')), importance weights
 //       ((1 / size) / (w_i / sum w)) ^ beta, divided by their maximum over the batch
-//   update (replay.py:106-113): priority[index[b]] = new[b]; of a repeated index the LAST b wins, as in the reference's loop
+//   update (replay.py:106-113): priority[index[b]] = new[b]; of a repeated index the LAST b wins, as in the reference's loop (an invalid new[b] is
+//       skipped and counted: the last VALID b wins)
 // Randomness: Philox4x32-10 keyed by (seed; draw number, sample) -- the stream the planner's device randomness uses (mz_device.h).  Everything is
 // enqueued on the caller's stream; nothing synchronises.
 #include <hip/hip_runtime.h>
@@ -155,23 +156,25 @@ __global__ __launch_bounds__(1024) void k_rp_normalize(float* weights, int batch
     for (int i = threadIdx.x; i < batch; i += 1024) weights[i] = m > 0.0f ? weights[i] / m : 1.0f;  // (all priorities zero / empty replay: plain weights, not 0 / 0)
 }
 
-// priority[index[b]] = value[b], the last b of a repeated index wins: the owner array records the largest b per touched slot (max is order-free)
+// priority[index[b]] = value[b], the last b of a repeated index wins: the owner array records the largest valid b per touched slot (max is order-free)
 __global__ __launch_bounds__(256) void k_rp_owner_clear(const int64_t* index, int batch, int* owner) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b < batch) owner[index[b]] = -1;
 }
-__global__ __launch_bounds__(256) void k_rp_owner_max(const int64_t* index, int batch, int* owner) {
+// replay.py:106-110 raises on a non-finite or negative priority; the device cannot raise: such a value is SKIPPED -- it neither writes nor owns its
+// slot, so the last VALID b of a repeated index wins, as in a sequential loop that skips it -- and counted.  Every finite float32 >= 0 is valid (-0.0
+// and FLT_MAX included), as np.isfinite has it.
+__device__ __forceinline__ bool valid_priority(float v) { return v >= 0.0f && v < __builtin_inff(); }
+__global__ __launch_bounds__(256) void k_rp_owner_max(const int64_t* index, const float* value, int batch, int* owner) {
     const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b < batch) atomicMax(&owner[index[b]], b);
+    if (b < batch && valid_priority(value[b])) atomicMax(&owner[index[b]], b);
 }
 __global__ __launch_bounds__(256) void k_rp_scatter(const int64_t* index, const float* value, int batch, const int* owner, float* prio, int* errors) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= batch) return;
     const float v = value[b];
-    // replay.py:106-110 raises on a non-finite or negative priority before writing anything; the device cannot raise: the value is not
-    // written (one NaN would poison every later prefix sum and importance weight) and the caller reads the count at its next sync point
-    const bool bad = !(v >= 0.0f) || v > 3.0e38f;
-    if (bad) { if (errors) atomicAdd(&errors[1], 1); return; }
+    // (one NaN would poison every later prefix sum and importance weight; the caller reads the count at its next sync point)
+    if (!valid_priority(v)) { if (errors) atomicAdd(&errors[1], 1); return; }
     if (owner[index[b]] == b) prio[index[b]] = v;
 }
 
@@ -222,7 +225,7 @@ extern "C" int mzl_replay_update_priorities(float* d_priority, int64_t capacity,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int gb = (batch + 255) / 256;
     hipLaunchKernelGGL(k_rp_owner_clear, dim3(gb), dim3(256), 0, st, d_index, batch, d_owner);
-    hipLaunchKernelGGL(k_rp_owner_max, dim3(gb), dim3(256), 0, st, d_index, batch, d_owner);
+    hipLaunchKernelGGL(k_rp_owner_max, dim3(gb), dim3(256), 0, st, d_index, d_new, batch, d_owner);
     hipLaunchKernelGGL(k_rp_scatter, dim3(gb), dim3(256), 0, st, d_index, d_new, batch, d_owner, d_priority, g_replay_errors);
     if (hipGetLastError() != hipSuccess) { g_rerr_set("mzl_replay_update_priorities: kernel launch failed"); return MZL_E_HIP; }
     return MZL_OK;
