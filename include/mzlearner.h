@@ -49,8 +49,10 @@ typedef struct {
     int32_t num_actions;
     int32_t num_planes;
     int32_t hidden_dim;
-    int32_t value_support_size;   /* 1: squared-error value head (network.py:126-134) */
-    int32_t reward_support_size;
+    int32_t value_support_size;   /* 1: squared-error value head (network.py:126-134); otherwise ODD: mzl_create refuses an even size -- the kernels take the
+                                   * expectation over the support with unit spacing, which linspace(-half, half, size), half = (size - 1) / 2 in integers
+                                   * (util.py:62-67,84-85), has at odd sizes only.  The planner (mz_create) refuses it too. */
+    int32_t reward_support_size;  /* the same */
     int32_t unroll_steps;         /* K, config.py:87 */
     int32_t max_batch;            /* capacity: mzl_grad accepts any batch <= max_batch */
     int32_t grad_slices;          /* >= 1: the weight-gradient kernel splits its reduction over this many workgroup rows (large batches); conv nets: 1 */

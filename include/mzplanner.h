@@ -46,7 +46,7 @@ typedef struct {
     int32_t num_planes;
     int32_t hidden_dim;          /* MLP only */
     int32_t num_res_blocks;      /* conv nets only */
-    int32_t value_support_size;
+    int32_t value_support_size;  /* 1 (scalar head) or odd: an even size is refused (unit spacing of the support, see mzlearner.h) */
     int32_t reward_support_size;
     /* search: config.py:58-78 */
     int32_t num_simulations;

@@ -196,6 +196,8 @@ extern "C" int mzl_create(const mzl_config* cfg, int device_id, mz_learner** out
         cfg->reward_support_size < 1 || cfg->unroll_steps < 1 || cfg->unroll_steps > 32 || cfg->max_batch < 1 || cfg->grad_slices < 1 || cfg->grad_slices > 64)
         return fail(MZL_E_INVALID, "bad learner dimensions");
     if (cfg->num_actions > 32767) return fail(MZL_E_INVALID, "num_actions must fit int16");
+    if ((cfg->value_support_size > 1 && cfg->value_support_size % 2 == 0) || (cfg->reward_support_size > 1 && cfg->reward_support_size % 2 == 0))
+        return fail(MZL_E_INVALID, "support sizes must be odd (or 1): the kernels take the expectation over the support with unit spacing, which linspace(-half, half, size) has at odd sizes only");
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (ndev <= 0) return fail(MZL_E_HIP, "no HIP device visible: the learner kernels have no CPU fallback");
@@ -392,6 +394,17 @@ extern "C" int mzl_debug_conv_fused(mz_learner* h, mzl_fused_call* call, const c
     std::string err;
     const int rc = mzlc_debug_conv_fused(h->conv, call, build_name, err);
     return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv_fused: " + err);
+}
+
+// diagnostic (tests; exported, NOT part of include/mzlearner.h): the conv learner's head block alone -- 1x1 conv, BatchNorm with running statistics,
+// Linear, the three losses, priorities, the gradients wrt both tower outputs and every head weight gradient -- through the update's own launch code
+// (learner_conv.hip mzlc_debug_heads); host pointers
+extern "C" int mzl_debug_heads(mz_learner* h, const mzl_heads_call* call) {
+    if (!h || !h->conv) return fail(MZL_E_INVALID, "mzl_debug_heads: needs a conv-net learner (MZL_NET_BOARD or MZL_NET_ATARI)");
+    if (!call) return fail(MZL_E_INVALID, "mzl_debug_heads: null argument");
+    std::string err;
+    const int rc = mzlc_debug_heads(h->conv, call, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_heads: " + err);
 }
 
 extern "C" int mzl_tensor_info(const mz_learner* h, int32_t i, const char** name, int64_t* offset, int32_t* rows, int32_t* cols) {

@@ -1305,6 +1305,8 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
     if (h->C0 < 1 || h->h < 1 || h->w < 1 || h->R < 1 || h->P < 1) return bad("bad conv-net geometry (in_channels, board_h, board_w, num_res_blocks, num_planes)");
     if (cfg->in_dim != h->C0 * h->obsH * h->obsW) return bad("in_dim must equal in_channels * board_h * board_w");
     if (cfg->value_support_size < 1 || cfg->reward_support_size < 1 || cfg->value_support_size > 1024 || cfg->reward_support_size > 1024) return bad("support sizes must be in [1, 1024]");
+    if ((cfg->value_support_size > 1 && cfg->value_support_size % 2 == 0) || (cfg->reward_support_size > 1 && cfg->reward_support_size % 2 == 0))
+        return bad("support sizes must be odd (or 1): the kernels take the expectation over the support with unit spacing, which linspace(-half, half, size) has at odd sizes only");
     if (h->hw > 240 || h->P > 1024) return bad("conv learner: boards up to 240 points and 1024 planes (larger nets train through muzero_amd.learner.train_step)");
     if (h->split && h->atari) return bad("conv_precision MZL_CONV_BF16X3 needs net_kind MZL_NET_BOARD: MZL_NET_ATARI has no split-bf16 builds");
     if (!make_geom(h->gm, h->h, h->w, h->allow_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, cdiv(cdiv(h->P, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
@@ -1654,14 +1656,18 @@ int mzlc_bind_buffers(mzlc_learner* h, float* running, int64_t* num_batches) {
     return MZL_OK;
 }
 
+// the heads' transposed Linear weights (k_lch_loss reads them); also mzlc_debug_heads, on parameters of its own
+static void pack_lin(const LchHead* head, const int* lwT_off, int hw, const float* params, float* lwT, hipStream_t st) {
+    for (int i = 0; i < 3; i++) {
+        const int nf = head[i].oc * hw, n = head[i].n_out * nf;
+        hipLaunchKernelGGL(k_lc_pack_lin, dim3(cdiv(n, 256)), dim3(256), 0, st, params, lwT + lwT_off[i], head[i].lw_off, head[i].n_out, nf);
+    }
+}
 static int pack_all(mzlc_learner* h, hipStream_t st) {
     if (h->split) hipLaunchKernelGGL(k_lc_pack_bf16x3, dim3(64, h->n_pack), dim3(256), 0, st, h->d_pack3, h->params, h->packed3);  // (no conv reads the f32 copies then)
     else hipLaunchKernelGGL(k_lc_pack, dim3(64, h->n_pack), dim3(256), 0, st, h->d_pack, h->params, h->packed);
     if (h->n_pack_par) hipLaunchKernelGGL(k_lc_pack_par, dim3(64, h->n_pack_par), dim3(256), 0, st, h->d_pack_par, h->params, h->packed);
-    for (int i = 0; i < 3; i++) {
-        const int nf = h->head[i].oc * h->hw, n = h->head[i].n_out * nf;
-        hipLaunchKernelGGL(k_lc_pack_lin, dim3(cdiv(n, 256)), dim3(256), 0, st, h->params, h->lwT + h->lwT_off[i], h->head[i].lw_off, h->head[i].n_out, nf);
-    }
+    pack_lin(h->head, h->lwT_off, h->hw, h->params, h->lwT, st);
     return hipGetLastError() == hipSuccess ? MZL_OK : MZL_E_HIP;
 }
 
@@ -1671,6 +1677,44 @@ int mzlc_commit(mzlc_learner* h, void* stream, std::string& err) {
     if (pack_all(h, reinterpret_cast<hipStream_t>(stream)) != MZL_OK) { err = "pack kernels failed to launch"; return MZL_E_HIP; }
     h->committed = true;
     return MZL_OK;
+}
+
+// the head block of one update: LchArgs from the handle's geometry (P, hw, A, K, n_max, the heads' shapes and partial-gradient layout) and the
+// buffers of `hb`, then the eight k_lch_* launches.  mzlc_grad passes the handle's buffers, mzlc_debug_heads temporary ones of its own.
+struct HeadBufs {
+    const LchHead* head;     // [3]: shapes as the handle's; the offsets address params / grads / running / nbt of THIS call
+    const int* lwT_off;      // [3]
+    const LchGroup* groups;  // [3 K] device
+    const float* params;
+    float *grads, *running;
+    int64_t* nbt;
+    const float* lwT;
+    float *u, *dzb, *feat, *dlogit, *spart, *spiv, *coef, *save, *lpart, *wpart, *dF_pred, *dF_rew, *loss;
+    float* spart_fwd;        // or null; given (mzlc_debug_heads): the forward partials copied here before k_lch_loss overwrites them with the backward ones
+};
+static void launch_heads(const mzlc_learner* h, const HeadBufs& hb, const LcBatch& bt, hipStream_t st) {
+    const int K = h->K, B = bt.B, ng = 3 * K;
+    LchArgs HA{};
+    for (int i = 0; i < 3; i++) { HA.head[i] = hb.head[i]; HA.lwT_off[i] = hb.lwT_off[i]; }
+    HA.groups = hb.groups; HA.ngroups = ng; HA.K = K; HA.B = B; HA.P = h->P; HA.hw = h->hw; HA.A = h->A;
+    HA.params = hb.params; HA.grads = hb.grads; HA.running = hb.running; HA.nbt = hb.nbt; HA.lwT = hb.lwT;
+    HA.u = hb.u; HA.dzb = hb.dzb; HA.feat = hb.feat; HA.dlogit = hb.dlogit; HA.spart = hb.spart; HA.spiv = hb.spiv; HA.coef = hb.coef; HA.save = hb.save; HA.lpart = hb.lpart;
+    HA.n_max = h->n_max; HA.bt = bt; HA.loss = hb.loss; HA.wpart = hb.wpart; HA.hp_total = h->hp_total;
+    for (int i = 0; i < 3; i++) HA.hp_off[i] = h->hp_off[i];
+    hipLaunchKernelGGL(k_lch_conv, dim3(B, ng), dim3(256), 0, st, HA);
+    hipLaunchKernelGGL(k_lch_bn, dim3(1), dim3(64 * 3 * LCH_MAXOC), 0, st, HA);
+    if (hb.spart_fwd) (void)hipMemcpyAsync(hb.spart_fwd, hb.spart, (size_t)ng * B * LCH_MAXOC * 2 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    {
+        const size_t lds = ((size_t)LCH_MAXOC * h->hw + 3 * (size_t)h->n_max + 32) * sizeof(float);
+        hipLaunchKernelGGL(k_lch_loss, dim3(B, ng), dim3(256), lds, st, HA);
+    }
+    hipLaunchKernelGGL(k_lch_bnb, dim3(1), dim3(64 * (3 * LCH_MAXOC + 1)), 0, st, HA);
+    LchDx dx{};
+    dx.out[0] = hb.dF_pred; dx.out[1] = hb.dF_rew;
+    hipLaunchKernelGGL(k_lch_dx, dim3(B, K, 2), dim3(256), 0, st, HA, dx);
+    hipLaunchKernelGGL(k_lch_dw1, dim3(h->P, 2, K), dim3(256), 0, st, HA);
+    hipLaunchKernelGGL(k_lch_dlin, dim3(cdiv(LCH_MAXOC * h->hw, 256), cdiv(h->n_max, LCH_DLN), 3 * K), dim3(256), 0, st, HA);
+    hipLaunchKernelGGL(k_lch_wsum, dim3(cdiv(h->hp_total, 256)), dim3(256), 0, st, HA);
 }
 
 int mzlc_grad(mzlc_learner* h, const mzl_batch* b, void* stream, std::string& err) {
@@ -1743,26 +1787,11 @@ int mzlc_grad(mzlc_learner* h, const mzl_batch* b, void* stream, std::string& er
         if (hipMemcpy(h->d_groups, h->groups_host.data(), ng * sizeof(LchGroup), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMemcpy"; return MZL_E_HIP; }
         h->groups_dev = h->groups_host;
     }
-    LchArgs HA{};
-    for (int i = 0; i < 3; i++) { HA.head[i] = h->head[i]; HA.lwT_off[i] = h->lwT_off[i]; }
-    HA.groups = h->d_groups; HA.ngroups = ng; HA.K = K; HA.B = B; HA.P = h->P; HA.hw = h->hw; HA.A = h->A;
-    HA.params = h->params; HA.grads = h->grads; HA.running = h->running; HA.nbt = h->nbt; HA.lwT = h->lwT;
-    HA.u = h->hu; HA.dzb = h->hdz; HA.feat = h->hfeat; HA.dlogit = h->hdl; HA.spart = h->hspart; HA.spiv = h->hspiv; HA.coef = h->hcoef; HA.save = h->hsave; HA.lpart = h->hlpart;
-    HA.n_max = h->n_max; HA.bt = bt; HA.loss = b->d_loss; HA.wpart = h->hwpart; HA.hp_total = h->hp_total;
-    for (int i = 0; i < 3; i++) HA.hp_off[i] = h->hp_off[i];
-    hipLaunchKernelGGL(k_lch_conv, dim3(B, ng), dim3(256), 0, st, HA);
-    hipLaunchKernelGGL(k_lch_bn, dim3(1), dim3(64 * 3 * LCH_MAXOC), 0, st, HA);
-    {
-        const size_t lds = ((size_t)LCH_MAXOC * h->hw + 3 * (size_t)h->n_max + 32) * sizeof(float);
-        hipLaunchKernelGGL(k_lch_loss, dim3(B, ng), dim3(256), lds, st, HA);
-    }
-    hipLaunchKernelGGL(k_lch_bnb, dim3(1), dim3(64 * (3 * LCH_MAXOC + 1)), 0, st, HA);
-    LchDx dx{};
-    dx.out[0] = h->dF_pred; dx.out[1] = h->dF_rew;
-    hipLaunchKernelGGL(k_lch_dx, dim3(B, K, 2), dim3(256), 0, st, HA, dx);
-    hipLaunchKernelGGL(k_lch_dw1, dim3(h->P, 2, K), dim3(256), 0, st, HA);
-    hipLaunchKernelGGL(k_lch_dlin, dim3(cdiv(LCH_MAXOC * h->hw, 256), cdiv(h->n_max, LCH_DLN), 3 * K), dim3(256), 0, st, HA);
-    hipLaunchKernelGGL(k_lch_wsum, dim3(cdiv(h->hp_total, 256)), dim3(256), 0, st, HA);
+    HeadBufs hb{};
+    hb.head = h->head; hb.lwT_off = h->lwT_off; hb.groups = h->d_groups; hb.params = h->params; hb.grads = h->grads; hb.running = h->running; hb.nbt = h->nbt; hb.lwT = h->lwT;
+    hb.u = h->hu; hb.dzb = h->hdz; hb.feat = h->hfeat; hb.dlogit = h->hdl; hb.spart = h->hspart; hb.spiv = h->hspiv; hb.coef = h->hcoef; hb.save = h->hsave; hb.lpart = h->hlpart;
+    hb.wpart = h->hwpart; hb.dF_pred = h->dF_pred; hb.dF_rew = h->dF_rew; hb.loss = b->d_loss;
+    launch_heads(h, hb, bt, st);
     // ---- backward ----
     const int eg = entry_groups(h, B);
     const float* gs_next = nullptr;  // gradient wrt s_{t+1}
@@ -2380,4 +2409,89 @@ int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build
     h->debug_name = name;
     *build_name = h->debug_name.c_str();
     return done(MZL_OK, "");
+}
+
+// diagnostic (tests): the head block ALONE -- k_lc_pack_lin through pack_lin, then launch_heads, the function mzlc_grad calls -- on host-supplied tower
+// outputs, head parameters, running statistics, targets, rows and weights.  P, hw, A, K and the support sizes are the handle's.  Every buffer is a
+// temporary one of this call (NULL stream; outputs preset to NaN bits, so an element no kernel wrote shows): the handle's weights, saved tensors,
+// gradients and running statistics are not touched.  Layouts: mz_learn_conv_host.h.
+int mzlc_debug_heads(mzlc_learner* h, const mzl_heads_call* c, std::string& err) {
+    const int B = c->batch, K = h->K, ng = 3 * K, hw = h->hw, P = h->P;
+    if (B < 1 || B > h->maxB) { err = "batch must be in [1, max_batch]"; return MZL_E_INVALID; }
+    if (c->rows < 1 || c->rows > (1 << 24)) { err = "rows (of the target tables) must be in [1, 2^24]"; return MZL_E_INVALID; }
+    if (!c->F_pred || !c->F_rew || !c->params || !c->running || !c->nbt || !c->pi || !c->value || !c->reward || !c->idx || !c->w) {
+        err = "null argument (F_pred, F_rew, params, running, nbt, pi, value, reward, idx, w)";
+        return MZL_E_INVALID;
+    }
+    for (int b = 0; b < B; b++)
+        if (c->idx[b] < 0 || c->idx[b] >= c->rows) { err = "idx out of [0, rows)"; return MZL_E_INVALID; }
+    if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+    // the heads with offsets into this call's compact vectors: per head (reward, policy, value) w1, gamma, beta, lw, lb; running mean, variance
+    LchHead head[3];
+    int lwT_off[3], np = 0, nr = 0, nl = 0;
+    for (int i = 0; i < 3; i++) {
+        LchHead H = h->head[i];
+        const int nf = H.oc * hw;
+        H.w1_off = np; np += H.oc * P;
+        H.gamma_off = np; np += H.oc;
+        H.beta_off = np; np += H.oc;
+        H.lw_off = np; np += H.n_out * nf;
+        H.lb_off = np; np += H.n_out;
+        H.rm_off = nr; nr += H.oc;
+        H.rv_off = nr; nr += H.oc;
+        H.nbt_idx = i;
+        lwT_off[i] = nl; nl += H.n_out * nf;
+        head[i] = H;
+    }
+    std::vector<void*> tmp;
+    auto A = [&](void** p, size_t bytes, int fill) {
+        if (hipMalloc(p, bytes + 256) != hipSuccess) return false;
+        tmp.push_back(*p);
+        return hipMemset(*p, fill, bytes + 256) == hipSuccess;
+    };
+    auto done = [&](int rc, const char* m) {
+        (void)hipDeviceSynchronize();
+        for (void* p : tmp) (void)hipFree(p);
+        if (rc != MZL_OK) { err = m; (void)hipGetLastError(); }
+        return rc;
+    };
+    auto up = [&](void** d, const void* src, size_t bytes) { return A(d, bytes, 0) && hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+    auto out = [&](float** d, size_t n) { return A((void**)d, n * 4, 0xff); };
+    const size_t nF = (size_t)K * B * P * hw, gb = (size_t)ng * B;
+    float *dFp = nullptr, *dFr = nullptr, *d_params = nullptr, *d_running = nullptr, *d_pi = nullptr, *d_value = nullptr, *d_reward = nullptr, *d_w = nullptr, *d_lwT = nullptr;
+    int64_t *d_nbt = nullptr, *d_idx = nullptr;
+    LchGroup* d_groups = nullptr;
+    HeadBufs hb{};
+    float *spart_fwd = nullptr, *d_prio = nullptr;
+    bool ok = up((void**)&dFp, c->F_pred, nF * 4) && up((void**)&dFr, c->F_rew, nF * 4) && up((void**)&d_params, c->params, (size_t)np * 4) &&
+              up((void**)&d_running, c->running, (size_t)nr * 4) && up((void**)&d_nbt, c->nbt, 3 * 8) && up((void**)&d_pi, c->pi, (size_t)c->rows * K * h->A * 4) &&
+              up((void**)&d_value, c->value, (size_t)c->rows * K * 4) && up((void**)&d_reward, c->reward, (size_t)c->rows * K * 4) && up((void**)&d_idx, c->idx, (size_t)B * 8) &&
+              up((void**)&d_w, c->w, (size_t)B * 4) && A((void**)&d_lwT, (size_t)nl * 4, 0) && A((void**)&d_groups, (size_t)ng * sizeof(LchGroup), 0);
+    ok = ok && out(&hb.grads, np) && out(&hb.u, gb * LCH_MAXOC * hw) && out(&hb.dzb, gb * LCH_MAXOC * hw) && out(&hb.feat, gb * LCH_MAXOC * hw) && out(&hb.dlogit, gb * h->n_max) &&
+         out(&hb.spart, gb * LCH_MAXOC * 2) && out(&spart_fwd, gb * LCH_MAXOC * 2) && out(&hb.spiv, gb * LCH_MAXOC) && out(&hb.coef, (size_t)ng * LCH_MAXOC * 5) &&
+         out(&hb.save, (size_t)ng * LCH_MAXOC * 2) && out(&hb.lpart, gb) && out(&hb.wpart, (size_t)K * h->hp_total) && out(&hb.dF_pred, nF) && out(&hb.dF_rew, nF) &&
+         out(&hb.loss, 1) && out(&d_prio, B);
+    if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+    std::vector<LchGroup> groups(ng);
+    for (int t = 0; t < K; t++) {  // (as mzlc_grad orders them)
+        groups[3 * t + 0] = LchGroup{dFr + (size_t)t * B * P * hw, 0, t};
+        groups[3 * t + 1] = LchGroup{dFp + (size_t)t * B * P * hw, 1, t};
+        groups[3 * t + 2] = LchGroup{dFp + (size_t)t * B * P * hw, 2, t};
+    }
+    if (hipMemcpy(d_groups, groups.data(), ng * sizeof(LchGroup), hipMemcpyHostToDevice) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+    hipStream_t st = nullptr;
+    pack_lin(head, lwT_off, hw, d_params, d_lwT, st);
+    hb.head = head; hb.lwT_off = lwT_off; hb.groups = d_groups; hb.params = d_params; hb.running = d_running; hb.nbt = d_nbt; hb.lwT = d_lwT; hb.spart_fwd = spart_fwd;
+    LcBatch bt{};
+    bt.pi = d_pi; bt.value = d_value; bt.reward = d_reward; bt.idx = d_idx; bt.w = d_w; bt.prio = d_prio; bt.B = B; bt.K = K; bt.A = h->A;
+    launch_heads(h, hb, bt, st);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return done(MZL_E_HIP, "the head kernels failed to launch or run");
+    auto dn = [&](void* dst, const void* src, size_t bytes) { return !dst || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    ok = dn(c->u, hb.u, gb * LCH_MAXOC * hw * 4) && dn(c->spart_fwd, spart_fwd, gb * LCH_MAXOC * 2 * 4) && dn(c->spiv, hb.spiv, gb * LCH_MAXOC * 4) &&
+         dn(c->coef, hb.coef, (size_t)ng * LCH_MAXOC * 5 * 4) && dn(c->save, hb.save, (size_t)ng * LCH_MAXOC * 2 * 4) && dn(c->feat, hb.feat, gb * LCH_MAXOC * hw * 4) &&
+         dn(c->dlogit, hb.dlogit, gb * h->n_max * 4) && dn(c->dzb, hb.dzb, gb * LCH_MAXOC * hw * 4) && dn(c->spart_bwd, hb.spart, gb * LCH_MAXOC * 2 * 4) &&
+         dn(c->lpart, hb.lpart, gb * 4) && dn(c->loss, hb.loss, 4) && dn(c->prio, d_prio, (size_t)B * 4) && dn(c->running_out, d_running, (size_t)nr * 4) &&
+         dn(c->nbt_out, d_nbt, 3 * 8) && dn(c->dF_pred, hb.dF_pred, nF * 4) && dn(c->dF_rew, hb.dF_rew, nF * 4) && dn(c->wpart, hb.wpart, (size_t)K * h->hp_total * 4) &&
+         dn(c->grads, hb.grads, (size_t)np * 4);
+    return ok ? done(MZL_OK, "") : done(MZL_E_HIP, "hipMemcpy failed");
 }

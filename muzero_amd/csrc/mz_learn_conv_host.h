@@ -100,3 +100,42 @@ struct mzl_fused_call {
     mzl_fused_conv conv[2];  // [1]: the second job of mode pair
 };
 int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build_name, std::string& err);
+
+// diagnostic (tests): the head block alone (mzl_debug_heads; exported, not part of include/mzlearner.h): the update's own launch code (launch_heads) on
+// temporary buffers.  Host pointers throughout; a null OUTPUT is skipped.  P, hw, A, K, the support sizes: the handle's.  With ng = 3 K groups in the
+// update's order (step t: reward, policy, value), oc = 1, 2, 1 planes and n_out = reward support, A, value support outputs per head:
+//   params / grads: per head (reward, policy, value) w1 [oc][P], gamma [oc], beta [oc], lw [n_out][oc * hw], lb [n_out];
+//   running: per head mean [oc], variance [oc]; nbt: [3].
+// Outputs are preset to NaN bits: a plane the head does not have, a logit beyond its n_out stay so.
+struct mzl_heads_call {
+    int32_t batch, rows;      // images; rows of the target tables (idx addresses them)
+    const float* F_pred;      // [K][B][P][hw] the prediction tower's outputs (policy, value)
+    const float* F_rew;       // [K][B][P][hw] the dynamics tower's raw outputs (reward)
+    const float* params;
+    const float* running;
+    const int64_t* nbt;
+    const float* pi;          // [rows][K][A]
+    const float* value;       // [rows][K]
+    const float* reward;      // [rows][K]
+    const int64_t* idx;       // [B], each in [0, rows)
+    const float* w;           // [B]
+    float* u;                 // [ng][B][2][hw]
+    float* spart_fwd;         // [ng][B][2][2] pivoted forward partials (k_lch_conv)
+    float* spiv;              // [ng][B][2]
+    float* coef;              // [ng][2][5]: a, b, c1, c2, c3
+    float* save;              // [ng][2][2]: mean, invstd
+    float* feat;              // [ng][B][2 hw]
+    float* dlogit;            // [ng][B][n_max]
+    float* dzb;               // [ng][B][2][hw]
+    float* spart_bwd;         // [ng][B][2][2] (sum dz, sum dz u) (k_lch_loss)
+    float* lpart;             // [ng][B]
+    float* loss;              // [1]
+    float* prio;              // [B]
+    float* running_out;
+    int64_t* nbt_out;
+    float* dF_pred;           // [K][B][P][hw]
+    float* dF_rew;
+    float* wpart;             // [K][hp_total], per head: w1, lw, lb
+    float* grads;
+};
+int mzlc_debug_heads(mzlc_learner* h, const mzl_heads_call* c, std::string& err);

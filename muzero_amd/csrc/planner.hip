@@ -408,6 +408,8 @@ extern "C" int mz_planner_create(const mz_config* cfg, int device_id, mz_planner
     if ((!conv && cfg->hidden_dim < 1) || cfg->num_planes < 1 || cfg->num_envs < 1) return fail(MZ_E_INVALID, "bad network/env dimensions");
     if (cfg->value_support_size < 1 || cfg->reward_support_size < 1 || cfg->value_support_size > 1023 || cfg->reward_support_size > 1023)
         return fail(MZ_E_INVALID, "support sizes must be in [1, 1023]");
+    if ((cfg->value_support_size > 1 && cfg->value_support_size % 2 == 0) || (cfg->reward_support_size > 1 && cfg->reward_support_size % 2 == 0))
+        return fail(MZ_E_INVALID, "support sizes must be odd (or 1): the kernels take the expectation over the support with unit spacing, which linspace(-half, half, size) has at odd sizes only");
     if (cfg->is_board_game && cfg->discount != 1.0) return fail(MZ_E_INVALID, "board games require discount == 1.0 (mcts.py:349-350)");
     if (cfg->conv_precision != MZ_CONV_F32 && cfg->conv_precision != MZ_CONV_BF16X3)
         return fail(MZ_E_INVALID, "conv_precision must be MZ_CONV_F32 (0) or MZ_CONV_BF16X3 (1)");

@@ -97,6 +97,16 @@ class MzlFusedCall(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('mode', 'batch', 'h', 'w', 'groups', 'no_side')] + [('count', C.c_float), ('pad_', C.c_int32), ('conv', MzlFusedConv * 2)]
 
 
+_HEADS_IN = ('F_pred', 'F_rew', 'params', 'running', 'nbt', 'pi', 'value', 'reward', 'idx', 'w')
+_HEADS_OUT = ('u', 'spart_fwd', 'spiv', 'coef', 'save', 'feat', 'dlogit', 'dzb', 'spart_bwd', 'lpart', 'loss', 'prio', 'running_out', 'nbt_out', 'dF_pred', 'dF_rew',
+              'wpart', 'grads')
+
+
+class MzlHeadsCall(C.Structure):
+    """mzl_heads_call (csrc/mz_learn_conv_host.h): the host operands of mzl_debug_heads."""
+    _fields_ = [('batch', C.c_int32), ('rows', C.c_int32)] + [(n, C.c_void_p) for n in _HEADS_IN + _HEADS_OUT]
+
+
 FUSED_MODES = {'conv': 0, 'pair': 1, 'finalize': 2, 'apply': 3}
 IN_MODES = {'ident': 0, 'bnrelu': 1, 'bnbwd': 2, 'bnres': 3}
 STAT_MODES = {None: 0, 'none': 0, 'fwd': 1, 'bwd': 2}
@@ -143,6 +153,8 @@ def load_library():
         L.mzl_debug_wgrad.argtypes = [vp, C.POINTER(MzlWgradCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     if hasattr(L, 'mzl_debug_conv_fused'):
         L.mzl_debug_conv_fused.argtypes = [vp, C.POINTER(MzlFusedCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
+    if hasattr(L, 'mzl_debug_heads'):
+        L.mzl_debug_heads.argtypes = [vp, C.POINTER(MzlHeadsCall)]  # diagnostic: exported, not declared
     _lib = L
     return L
 
@@ -266,6 +278,8 @@ class HipLearner:
         if self.wgrad_precision:  # (the default never calls the setter: the handle is what mzl_create made)
             _check(L.mzl_set_wgrad_precision(self._h, self.wgrad_precision))
         self.K, self.A, self.in_dim, self.max_batch = unroll_steps, spec['num_actions'], in_dim, max_batch
+        if self.kind in ('board', 'atari'):  # (debug_heads: planes, positions of the hidden state, reward / value support)
+            self._heads_geom = (spec['num_planes'], bh * bw if self.kind == 'board' else (bh // 16) * (bw // 16), spec['reward_support_size'], spec['value_support_size'])
         self.total = int(L.mzl_num_params(self._h))
         gfl = int(L.mzl_grad_floats(self._h))
         self.flat = torch.zeros(3 * self.total + gfl, dtype=torch.float32, device=self.device)
@@ -689,6 +703,41 @@ class HipLearner:
             if 'num_batches' in r:
                 r['num_batches'] = int(r['num_batches'][0])
         return (tuple(results) if mode == 'pair' else res0), (name.value or b'').decode()
+
+    def debug_heads(self, F_pred, F_rew, params, running, nbt, pi, value, reward, idx, w, skip=()):
+        """Diagnostic (tests): the head block alone through the update's own launch code (mzl_debug_heads), on temporary buffers: the learner's state is
+        not touched.  F_pred, F_rew [K, B, P, hw]; params, running, nbt in the hook's flat layouts (csrc/mz_learn_conv_host.h; tests/heads_cases.py
+        builds them); pi [rows, K, A], value, reward [rows, K], idx [B], w [B].  Returns a dict of every output, shaped (NaN where no kernel wrote);
+        names in `skip` are passed as null pointers and left out."""
+        lib = load_library()
+        if not hasattr(lib, 'mzl_debug_heads'):
+            raise LearnerError('mzl_debug_heads: this library has no such hook')
+        if self.kind not in ('board', 'atari'):
+            call = MzlHeadsCall()
+            _check(lib.mzl_debug_heads(self._h, C.byref(call)))
+        P, hw, Sr, Sv = self._heads_geom
+        K, A = self.K, self.A
+        f32 = np.float32
+        ins = dict(F_pred=np.ascontiguousarray(F_pred, f32), F_rew=np.ascontiguousarray(F_rew, f32), params=np.ascontiguousarray(params, f32),
+                   running=np.ascontiguousarray(running, f32), nbt=np.ascontiguousarray(nbt, np.int64), pi=np.ascontiguousarray(pi, f32),
+                   value=np.ascontiguousarray(value, f32), reward=np.ascontiguousarray(reward, f32), idx=np.ascontiguousarray(idx, np.int64), w=np.ascontiguousarray(w, f32))
+        B, rows = int(ins['idx'].shape[0]), int(ins['value'].shape[0])
+        ng, nmax = 3 * K, max(A, Sr, Sv)
+        npar = sum(oc * P + 2 * oc + n * oc * hw + n for oc, n in ((1, Sr), (2, A), (1, Sv)))
+        want = dict(F_pred=(K, B, P, hw), F_rew=(K, B, P, hw), params=(npar,), running=(8,), nbt=(3,), pi=(rows, K, A), value=(rows, K), reward=(rows, K), idx=(B,), w=(B,))
+        for k, shp in want.items():
+            if tuple(ins[k].shape) != shp:
+                raise LearnerError(f'mzl_debug_heads: {k} {tuple(ins[k].shape)} is not {shp}')
+        shapes = dict(u=(ng, B, 2, hw), spart_fwd=(ng, B, 2, 2), spiv=(ng, B, 2), coef=(ng, 2, 5), save=(ng, 2, 2), feat=(ng, B, 2 * hw), dlogit=(ng, B, nmax),
+                      dzb=(ng, B, 2, hw), spart_bwd=(ng, B, 2, 2), lpart=(ng, B), loss=(1,), prio=(B,), running_out=(8,), nbt_out=(3,), dF_pred=(K, B, P, hw),
+                      dF_rew=(K, B, P, hw), wpart=(K, npar - 4 * 2), grads=(npar,))
+        out = {k: np.zeros(shp, np.int64 if k == 'nbt_out' else f32) for k, shp in shapes.items() if k not in skip}
+        call = MzlHeadsCall()
+        call.batch, call.rows = B, rows
+        for k, a in list(ins.items()) + list(out.items()):
+            setattr(call, k, a.ctypes.data)
+        _check(lib.mzl_debug_heads(self._h, C.byref(call)))
+        return out
 
     def close(self) -> None:
         if self._h:

@@ -220,7 +220,7 @@ def test_batched_search_bit_exact_vs_oracle(oracle, g, B):
 
 @pytest.mark.parametrize('ishape,A,P,vs,rs_,board', [
     ((4, 5), 4, 256, 1, 1, False),      # MSE heads on a tuned shape that is not the ten-action build: shape-generic kernel (scalar_head_tile)
-    ((4, 5), 2, 512, 10, 1, False),     # one categorical, one MSE head (same tile count: a tuned shape)
+    ((4, 5), 2, 512, 11, 1, False),     # one categorical, one MSE head (same tile count: a tuned shape); an odd support: even sizes are refused at create
     ((3, 3, 3), 10, 256, 1, 1, False),  # the ten-action build outside TicTacToe's settings: single player, no known bounds
     ((3, 3, 3), 10, 256, 1, 1, True),
 ], ids=['mse-a4-p256', 'mixed-a2-p512', 'mse-a10-single', 'mse-a10-board'])

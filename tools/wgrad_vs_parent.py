@@ -1,4 +1,4 @@
-"""Is the learner's gradient vector the same bytes as another build's?  The diagnostic hook mzl_debug_wgrad reaches into the update's op builders
+"""Are the learner's gradient vector, loss and priorities the same bytes as another build's?  The diagnostic hook mzl_debug_wgrad reaches into the update's op builders
 (Sched::wgrad_ops, wgrad_ops_steps, AtariRun::wgrad_tiles were given parameters and split for it) and make_geom; the update itself must not move.
 
     python tools/wgrad_vs_parent.py --parent-lib PATH/libmzlearner_hip.so [--out profiles/wgrad_layer/fp32_vs_parent.json]
@@ -52,9 +52,10 @@ def child(case, lib):
                         rs.uniform(-1, 1, (B, K)).astype(np.float32))
     w = rs.uniform(0.3, 1.0, B).astype(np.float32)
     hl = _hip(net, dev, B, K=K)
-    loss, _ = hl.grad(_ring(tr, dev), None, torch.from_numpy(w).to(dev), B)
+    loss, prio = hl.grad(_ring(tr, dev), None, torch.from_numpy(w).to(dev), B)
     g = hl.grad_flat.detach().cpu().numpy()
-    print(json.dumps(dict(case=case, sha256=hashlib.sha256(g.tobytes()).hexdigest(), floats=int(g.size), loss=float(loss))))
+    print(json.dumps(dict(case=case, sha256=hashlib.sha256(g.tobytes()).hexdigest(), floats=int(g.size), loss=float(loss),
+                          loss_bits=loss.detach().cpu().numpy().tobytes().hex(), priorities_sha256=hashlib.sha256(prio.detach().cpu().numpy().tobytes()).hexdigest())))
     hl.close()
 
 
@@ -68,14 +69,16 @@ if __name__ == '__main__':
     if a.child:
         child(a.child, a.lib)
         sys.exit(0)
-    doc = dict(what='sha256 of the gradient vector (grad_flat) after one mzl_grad of a fixed batch: this tree\'s library against the parent commit\'s, same job', cases={})
+    doc = dict(what='sha256 of the gradient vector (grad_flat), the bits of the loss and sha256 of the priorities after one mzl_grad of a fixed batch: this tree\'s library against the parent '
+                    'commit\'s, same job', cases={})
     for case in CASES:
         row = {}
         for who, lib in (('parent', os.path.abspath(a.parent_lib)), ('this', '')):
             out = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', case, '--lib', lib], check=True, timeout=300, capture_output=True, text=True).stdout
             row[who] = json.loads(out.strip().splitlines()[-1])
-        doc['cases'][case] = dict(parent=row['parent']['sha256'], this=row['this']['sha256'], floats=row['this']['floats'],
-                                  identical=row['parent']['sha256'] == row['this']['sha256'] and row['parent']['floats'] == row['this']['floats'])
+        same = all(row['parent'][k] == row['this'][k] for k in ('sha256', 'floats', 'loss_bits', 'priorities_sha256'))
+        doc['cases'][case] = dict(parent=row['parent']['sha256'], this=row['this']['sha256'], floats=row['this']['floats'], loss_bits=[row['parent']['loss_bits'], row['this']['loss_bits']],
+                                  priorities=[row['parent']['priorities_sha256'], row['this']['priorities_sha256']], identical=same)
     doc['identical'] = all(c['identical'] for c in doc['cases'].values())
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, 'w') as f:
