@@ -61,6 +61,8 @@ def main():
     ap.add_argument('--graphed', action='store_true', help='the PyTorch-ROCm update as one HIP graph (learner.GraphedTrainStep)')
     ap.add_argument('--autograd', action='store_true', help='the PyTorch-ROCm update, eager (learner.train_step)')
     ap.add_argument('--out', default='')
+    ap.add_argument('--replay-state', choices=['f32', 'int8'], default='f32',
+                    help='how the replay stores states: float32, or one exact byte per element of the 0 / 1 planes (a quarter of the ring; same run)')
     ap.add_argument('--host-reload', action='store_true',
                     help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--conv-precision', choices=['f32', 'bf16x3'], default='f32',
@@ -106,7 +108,7 @@ def main():
     else:
         opt = torch.optim.Adam(net.parameters(), lr=cfg.lr_init, weight_decay=cfg.weight_decay)
     sched = None if hip is not None else torch.optim.lr_scheduler.MultiStepLR(opt, milestones=cfg.lr_milestones, gamma=cfg.lr_decay_rate)
-    replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda')
+    replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda', state_format=None if args.replay_state == 'f32' else args.replay_state)
     p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed, conv_precision=args.conv_precision), 0)
     net.eval()
     p.reload(hip.planner_weights() if hip is not None else net.state_dict(), host=args.host_reload)

@@ -47,6 +47,8 @@ def main():
     ap.add_argument('--eval-games', type=int, default=50)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--out', default='')
+    ap.add_argument('--replay-state', choices=['f32', 'int8'], default='f32',
+                    help='how the replay stores states: float32, or one exact byte per element of the 0 / 1 planes (a quarter of the ring; same run)')
     ap.add_argument('--host-reload', action='store_true',
                     help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--host-assembly', action='store_true',
@@ -74,7 +76,7 @@ def main():
         sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=cfg.lr_milestones, gamma=cfg.lr_decay_rate)
     else:
         hl = learner.make_hip_learner(cfg, net, dev)
-    replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda')
+    replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda', state_format=None if args.replay_state == 'f32' else args.replay_state)
     p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed), 0)
     net.eval()
     p.reload(hl.planner_weights() if hl is not None else net.state_dict(), host=args.host_reload)

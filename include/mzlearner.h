@@ -66,7 +66,7 @@ typedef struct {
 
 /* One batch of `Transition`s (replay.py:27-32) addressed inside the replay ring's storages. */
 typedef struct {
-    const void* d_state;      /* [capacity][in_dim] float32, or int8 when state_is_int8 (board games) */
+    const void* d_state;      /* [capacity][in_dim] float32, or int8 when state_is_int8 == 1 (board games), or [capacity][state_row_bytes] packed frames (2) */
     const void* d_action;     /* [capacity][K] int8, or int16 when action_bytes == 2 (num_actions > 128) */
     const float* d_pi_prob;   /* [capacity][K][num_actions] */
     const float* d_value;     /* [capacity][K] */
@@ -76,8 +76,15 @@ typedef struct {
     float* d_loss;            /* [1]   out: the reported loss (pipeline.py:594-597) */
     float* d_priorities;      /* [batch] out: |v_0 - z_0| (pipeline.py:603-609) */
     int32_t batch;
-    int32_t state_is_int8;
+    int32_t state_is_int8;    /* the state FORMAT (mzplanner.h MZ_STATE_*): 0 float32, 1 int8, 2 frames_u8 -- conv nets only (the MLP learner returns
+                               * MZL_E_INVALID naming the format): a row is frame_stack * frame_channels * board_h * board_w frame bytes in the observation's
+                               * plane order, then frame_stack action bytes, zero-padded to a multiple of 16; a pixel decodes to (float)b / 255.0f, an action
+                               * plane to (float)((double)(a + 1) / (double)num_actions) */
     int32_t action_bytes;     /* 1 or 2 */
+    /* format 2 only (all zero for 0 and 1): MZL_E_INVALID unless frame_stack * (frame_channels + 1) * board_h * board_w == in_dim, num_actions <= 256 and
+     * state_row_bytes is a multiple of 16 that holds the frame and action bytes */
+    int32_t state_row_bytes;
+    int32_t frame_stack, frame_channels;
 } mzl_batch;
 
 typedef struct mz_learner mz_learner;

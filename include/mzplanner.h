@@ -201,7 +201,7 @@ int mz_selfplay_counters(mz_planner* p, int64_t out[4]);
  * priorities are final.  mz_selfplay_read then returns at most the moves the record ring holds. */
 typedef struct {
     int64_t capacity;     /* ring slots; slot of the i-th item ever added = i % capacity */
-    float* state;         /* [capacity, obs_c*obs_h*obs_w] */
+    void* state;          /* [capacity, obs_c*obs_h*obs_w] float32 -- or the compact rows of `state_format` below */
     void* action;         /* [capacity, unroll_steps] int8 when num_actions <= 128, int16 otherwise (the reference's int8, pipeline.py:753,
                            * cannot hold Gomoku 15x15's 226 actions: numpy 2 raises OverflowError there) */
     float* pi_prob;       /* [capacity, unroll_steps, num_actions] */
@@ -214,7 +214,21 @@ typedef struct {
                            * The caller must not write it while attached. */
     int32_t* origin;      /* optional [capacity]: index of the environment that produced the item, or NULL */
     int32_t acc_seq_length, unroll_steps, td_steps;  /* MuZeroConfig fields (config.py:58-94) */
+    /* How `state` is stored.  MZ_STATE_F32 (0: a zero-initialised field): float32, as ever.  The other formats are EXACT -- every state decodes to
+     * the float32 observation bit for bit -- and are refused (MZ_E_INVALID naming state_format) at mz_selfplay_reset / mz_selfplay_reset_external
+     * for an env whose observations they cannot hold:
+     *   MZ_STATE_I8         [capacity, obs] one signed byte per element, value (float)(int8_t)b.  TicTacToe, Gomoku (0 / 1 planes), and host-stepped
+     *                       envs: there every emitted state is checked (decode(encode(v)) == v bit for bit); on a mismatch the replay count does not
+     *                       advance and mz_selfplay_external_commit returns MZ_E_INVALID naming the smallest such env; mz_selfplay_reset_external next.
+     *   MZ_STATE_FRAMES_U8  host-stepped envs with stack_history = S > 0, is_obs_image, frame_u8 and num_actions <= 256 only.  A row is the
+     *                       S*C*H*W frame bytes in the observation's plane order (plane k*C + c, k = 0 the newest frame), then S action bytes (byte
+     *                       k: the action of plane S*C + k; 0 after a reset), zero-padded to a multiple of 16 bytes: [capacity, row bytes] uint8.
+     *                       A pixel decodes to (float)b / 255.0f, an action plane to (float)((double)(a + 1) / (double)num_actions). */
+    int32_t state_format;
 } mz_replay_ring;
+#define MZ_STATE_F32 0
+#define MZ_STATE_I8 1
+#define MZ_STATE_FRAMES_U8 2
 int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ring);
 
 /* Self-play on host-stepped environments: the reference's actor loop body (pipeline.py:91-113) over whatever env object the

@@ -482,6 +482,9 @@ extern "C" int mzl_grad(mz_learner* h, const mzl_batch* b, void* stream) {
     if (!b->d_state || !b->d_action || !b->d_pi_prob || !b->d_value || !b->d_reward || !b->d_weights || !b->d_loss || !b->d_priorities)
         return fail(MZL_E_INVALID, "null batch pointer");
     if (b->action_bytes != 1 && b->action_bytes != 2) return fail(MZL_E_INVALID, "action_bytes must be 1 or 2");
+    if (b->state_is_int8 != 0 && b->state_is_int8 != 1)
+        return fail(MZL_E_INVALID, "the MLP learner reads float32 (0) and int8 (1) states: mzl_batch.state_is_int8 = " + std::to_string(b->state_is_int8) +
+                                       " (2: frames_u8, packed image frames) is a format of the conv nets");
     {   // every pointer must be memory of this GPU (a host pointer would fault inside a kernel: checked here, once per distinct value)
         const void* ptrs[9] = {b->d_state, b->d_action, b->d_pi_prob, b->d_value, b->d_reward, b->d_index, b->d_weights, b->d_loss, b->d_priorities};
         static const char* names[9] = {"d_state", "d_action", "d_pi_prob", "d_value", "d_reward", "d_index", "d_weights", "d_loss", "d_priorities"};

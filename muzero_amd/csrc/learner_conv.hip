@@ -1727,6 +1727,19 @@ int mzlc_grad(mzlc_learner* h, const mzl_batch* b, void* stream, std::string& er
     }
     if (b->action_bytes != 1 && b->action_bytes != 2) { err = "action_bytes must be 1 or 2"; return MZL_E_INVALID; }
     if (b->action_bytes == 1 && h->A > 128) { err = "num_actions > 128 needs int16 actions"; return MZL_E_INVALID; }
+    if (b->state_is_int8 < 0 || b->state_is_int8 > 2) { err = "mzl_batch.state_is_int8: the state format is 0 (float32), 1 (int8) or 2 (frames_u8)"; return MZL_E_INVALID; }
+    if (b->state_is_int8 == 2) {
+        const long long S = b->frame_stack, C = b->frame_channels, HW = (long long)h->obsH * h->obsW;
+        if (S < 1 || C < 1 || S * (C + 1) * HW != (long long)h->C0 * HW) {
+            err = "mzl_batch state format 2 (frames_u8): frame_stack * (frame_channels + 1) * board_h * board_w != in_dim";
+            return MZL_E_INVALID;
+        }
+        if (h->A > 256) { err = "mzl_batch state format 2 (frames_u8) holds an action in one byte: num_actions > 256"; return MZL_E_INVALID; }
+        if (b->state_row_bytes % 16 != 0 || (long long)b->state_row_bytes < S * C * HW + S) {
+            err = "mzl_batch state format 2 (frames_u8): state_row_bytes must be a multiple of 16 holding frame_stack * frame_channels * board_h * board_w + frame_stack bytes";
+            return MZL_E_INVALID;
+        }
+    }
     {
         const void* ptrs[9] = {b->d_state, b->d_action, b->d_pi_prob, b->d_value, b->d_reward, b->d_index, b->d_weights, b->d_loss, b->d_priorities};
         static const char* names[9] = {"d_state", "d_action", "d_pi_prob", "d_value", "d_reward", "d_index", "d_weights", "d_loss", "d_priorities"};
@@ -1751,6 +1764,7 @@ int mzlc_grad(mzlc_learner* h, const mzl_batch* b, void* stream, std::string& er
     bt.state = b->d_state; bt.action = b->d_action; bt.pi = b->d_pi_prob; bt.value = b->d_value; bt.reward = b->d_reward; bt.idx = b->d_index;
     bt.w = b->d_weights; bt.prio = b->d_priorities; bt.B = B; bt.state_i8 = b->state_is_int8; bt.action_bytes = b->action_bytes; bt.K = K; bt.A = h->A;
     bt.in_dim = h->C0 * h->obsH * h->obsW;
+    if (b->state_is_int8 == 2) { bt.row_bytes = b->state_row_bytes; bt.fS = b->frame_stack; bt.fHW = h->obsH * h->obsW; bt.fP = b->frame_stack * b->frame_channels * bt.fHW; }
     hipLaunchKernelGGL(k_lc_gather, dim3(cdiv(bt.in_dim, 256) > 8 ? 8 : cdiv(bt.in_dim, 256), B), dim3(256), 0, st, bt, h->obs, h->act);
     Sched sr{h, B, 0, false, h->gm, h->P}, s0{h, B, 0, paired, h->gm, h->P}, s1{h, B, 1, paired, h->gm, h->P};
     // ---- forward ----
@@ -1865,7 +1879,8 @@ int mzlc_apply(mzlc_learner* h, double lr, double beta1, double beta2, double ep
 // masks, normalisation arg-min / arg-max -- for a float64 reference that takes the same branches): "feat" the heads' post-ReLU features
 // [3 K groups][B][2 hw]; the Atari representation's plane tensors "a1" / "a2" (post-ReLU conv_1 / conv_2), "s48_h1" / "s48_x" / "s24_h1" / "s24_x"
 // (b = block: the block's inner post-ReLU tensor -- only with MZLC_KEEP_H1=1; else "s48_y1" / "s48_fcoef1" / .., its raw conv output and BatchNorm
-// coefficients as for "y" / "fcoef" -- and the block's output), "hraw" (the pooled 6 x 6 state before normalisation).  *count: floats of the
+// coefficients as for "y" / "fcoef" -- and the block's output), "hraw" (the pooled 6 x 6 state before normalisation); "obs": the gathered,
+// decoded observations [B][C0][H][W] of the last batch (tests/test_gpu_replay_codec.py).  *count: floats of the
 // tensor at the last batch where the shape is known here, else the allocation's.
 int mzlc_debug_tensor(const mzlc_learner* h, const char* what, int a, int b, void** ptr, int64_t* count) {
     const std::string w = what;
@@ -1876,6 +1891,7 @@ int mzlc_debug_tensor(const mzlc_learner* h, const char* what, int a, int b, voi
     else if (a == 2 * h->K + 1 && h->atari) ap = &h->a12;
     *count = (int64_t)h->T;
     if (ap == &h->a12) *count = (int64_t)h->maxB * h->P * (h->obsH / 8) * (h->obsW / 8);  // (the 12 x 12 stage of the Atari representation)
+    if (w == "obs") { *ptr = h->obs; *count = (int64_t)h->lastB * h->C0 * h->obsH * h->obsW; return MZL_OK; }  // k_lc_gather's output [B][C0][H][W]
     if (w == "y" && ap && b >= 0 && b < (int)ap->y.size()) { *ptr = ap->y[b]; return MZL_OK; }
     if (w == "x" && ap && b >= 0 && b < (int)ap->x.size()) { *ptr = ap->x[b]; return MZL_OK; }
     if (w == "fcoef" && ap && b >= 0 && b < (int)ap->fcoef.size()) { *ptr = ap->fcoef[b]; *count = 3 * (int64_t)pad16(h->P); return MZL_OK; }

@@ -12,6 +12,8 @@
 //   Synthetic     : stand-in for the Atari emulator (ale-py is an absent third-party dependency): every step draws a fresh
 //                   U[0,1) observation from Philox, reward 0, episode ends every 1000 steps.
 #pragma once
+#include <climits>
+
 #include "mz_device.h"
 
 namespace mz {
@@ -626,7 +628,7 @@ __global__ void k_env_step(const EnvLaunch L) {  // 16 threads per env
 // ---------------------------------------------------------------------------------------------------------
 struct ReplayRing {
     long long capacity;
-    float* state;         // [capacity][D]
+    void* state;          // [capacity][D] float32, or the compact rows of `state_format` ([capacity][row_bytes], written by k_epi_states)
     signed char* action;  // [capacity][K] int8 -- or, when action16 is set (num_actions > 128), the same buffer as int16
     int action16;
     float* pi_prob;       // [capacity][K][A]
@@ -639,7 +641,12 @@ struct ReplayRing {
     int* origin;          // optional [capacity]: env that produced the item (tests), or null
     int acc, K, td, board;
     double pw[34];        // discount ** i, i = 0..td (host libm pow == Python float pow)
+    int state_format;     // STATE_F32 | STATE_I8 | STATE_FRAMES_U8 (mzplanner.h MZ_STATE_*)
+    int row_bytes;        // compact formats: bytes of one state row (int8: D; frames_u8: fP + fS padded to a multiple of 16)
+    int fS, fC, fHW, fP;  // frames_u8: stacked frames, channels, plane size, frame bytes fS * fC * fHW
+    int* enc_err;         // int8 on host-stepped envs: smallest env with an element int8 cannot hold (INT_MAX: none), else null
 };
+constexpr int STATE_F32 = 0, STATE_I8 = 1, STATE_FRAMES_U8 = 2;
 
 struct EpiLaunch {
     EnvState env;
@@ -674,11 +681,12 @@ __device__ inline void epi_emit(const EpiLaunch& E, int e, long long start, int 
     // `keep_from`: when ONE move emits more items than the ring holds (a small ring, many envs finishing together), the items below it
     // would be overwritten by later items of the same launch -- by another workgroup, in no defined order -- so they are not written at
     // all: the ring ends up with exactly the last `capacity` items in order, run to run the same
-    for (int j = lane; j < n * D; j += 64) {
-        const int t = j / D, i = j - t * D;
-        if (base + t < keep_from) continue;
-        R.state[(size_t)((base + t) % R.capacity) * D + i] = V.r_obs[rec(t) * D + i];
-    }
+    if (R.state_format == STATE_F32)  // (the compact formats' states: k_epi_states)
+        for (int j = lane; j < n * D; j += 64) {
+            const int t = j / D, i = j - t * D;
+            if (base + t < keep_from) continue;
+            static_cast<float*>(R.state)[(size_t)((base + t) % R.capacity) * D + i] = V.r_obs[rec(t) * D + i];
+        }
     for (int j = lane; j < n * K; j += 64) {
         const int t = j / K, k = j - t * K, idx = t + k;
         if (base + t < keep_from) continue;
@@ -761,12 +769,89 @@ __global__ __launch_bounds__(1024) void k_epi_scan(const EpiLaunch E) {
     if (t == 1023) R.ctr[1] = (long long)part[1023];
 }
 
+// The states of a move's items in a compact format (ReplayRing.state_format; the reference of the formats is muzero_amd/replay.py
+// encode_state): between k_epi_scan, which has decided how many items every env emits (off[], ctr[1]), and k_epilogue, which writes
+// everything else and then moves ep_start.  An env's items of one move are consecutive steps of its open trajectory from ep_start[e]
+// (a flush's acc_seq_length items, then -- episode end on the same move -- the rest), in consecutive slots from ctr[0] + off[e], so
+// item g of the move belongs to the last env whose off[] is <= g.  blockIdx.y strides over the move's items, blockIdx.x over 4 KiB
+// chunks of the row; a move without items costs every workgroup one load.  Ring-wrap and keep_from are epi_emit's.
+//   int8      : byte = rint(v); a lane packs four elements into one aligned dword of the ring (rows of D bytes start at any address:
+//               the dwords that straddle a row's ends are written byte by byte).  decode(encode(v)) is compared with v bit for bit
+//               where enc_err is given (host-stepped envs; the device boards' planes are 0 / 1 by construction).
+//   frames_u8 : pixel byte = rint(v * 255), action byte = rint(v * A) - 1 of the action plane's first element; a lane packs sixteen
+//               bytes into one 128-bit store (rows are multiples of 16 bytes: frame bytes, action bytes, zero padding).
+constexpr int EPS_ITEMS = 256;  // gridDim.y
+__device__ __forceinline__ unsigned epi_pixel_byte(float v) { return (unsigned)(int)rintf(v * 255.0f) & 0xffu; }
+__global__ __launch_bounds__(256) void k_epi_states(const EpiLaunch E) {
+    const EnvState& V = E.env;
+    const ReplayRing& R = E.ring;
+    const long long total = R.ctr[1];
+    if (total == 0) return;
+    const long long first = R.ctr[0], keep_from = first + total - R.capacity;
+    const int D = V.D, B = E.B;
+    unsigned char* ring = static_cast<unsigned char*>(R.state);
+    for (long long g = (keep_from > first ? keep_from - first : 0) + blockIdx.y; g < total; g += gridDim.y) {
+        int e = 0, hi = B - 1;
+        while (e < hi) {
+            const int mid = (e + hi + 1) >> 1;
+            if ((long long)R.off[mid] <= g) e = mid;
+            else hi = mid - 1;
+        }
+        const int t = (int)(g - R.off[e]);
+        const float* src = V.r_obs + ((size_t)((V.ep_start[e] + t) % V.ring_len) * B + e) * D;
+        const size_t row0 = (size_t)((first + g) % R.capacity) * R.row_bytes;  // byte offset of the item's row
+        if (R.state_format == STATE_I8) {
+            bool bad = false;
+            for (size_t w = (row0 & ~(size_t)3) + (size_t)(blockIdx.x * 256 + threadIdx.x) * 4; w < row0 + D; w += (size_t)gridDim.x * 1024) {
+                unsigned pack = 0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const long long i = (long long)(w + q) - (long long)row0;
+                    if (i < 0 || i >= D) continue;
+                    const float v = src[i], r = rintf(v);
+                    const int b = r >= -128.0f && r <= 127.0f ? (int)r : 0;
+                    bad |= __float_as_uint((float)b) != __float_as_uint(v);
+                    pack |= ((unsigned)b & 0xffu) << (8 * q);
+                }
+                if (w >= row0 && w + 4 <= row0 + D) *reinterpret_cast<unsigned*>(ring + w) = pack;
+                else
+                    for (int q = 0; q < 4; q++)
+                        if (w + q >= row0 && w + q < row0 + D) ring[w + q] = (unsigned char)(pack >> (8 * q));
+            }
+            if (bad && R.enc_err) atomicMin(R.enc_err, e);
+        } else {
+            const int P = R.fP, S = R.fS, A = V.A;
+            for (int q0 = (blockIdx.x * 256 + threadIdx.x) * 16; q0 < R.row_bytes; q0 += gridDim.x * 4096) {
+                unsigned w[4] = {0, 0, 0, 0};
+                if (q0 + 16 <= P && (D & 3) == 0) {  // sixteen pixels, four aligned 16-byte loads
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const float4 f = *reinterpret_cast<const float4*>(src + q0 + 4 * j);
+                        w[j] = epi_pixel_byte(f.x) | epi_pixel_byte(f.y) << 8 | epi_pixel_byte(f.z) << 16 | epi_pixel_byte(f.w) << 24;
+                    }
+                } else {  // odd rows, and the chunk that holds the action bytes and the padding
+#pragma unroll
+                    for (int j = 0; j < 16; j++) {
+                        const int q = q0 + j;
+                        unsigned b = 0;
+                        if (q < P) b = epi_pixel_byte(src[q]);
+                        else if (q < P + S) b = (unsigned)((int)rintf(src[(size_t)(S * R.fC + (q - P)) * R.fHW] * (float)A) - 1) & 0xffu;
+                        w[j >> 2] |= b << (8 * (j & 3));
+                    }
+                }
+                *reinterpret_cast<uint4*>(ring + row0 + q0) = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
+    }
+}
+
 // Publish: the host (replay.num_added / sample on another stream) may only see a count whose slots are all filled.  Slots are
 // reserved by k_epi_scan (R.off, R.ctr[1]); this one-thread kernel, next on the same stream -- i.e. after every workgroup of the
 // epilogue has finished and its writes are visible -- copies the reserved cursor to the committed counter the host reads.
 // (A last-workgroup-done counter inside k_epilogue did the same with 4096 same-address atomics per move: -9 % on the C2
 // env-steps-into-replay rate, measured.)
 __global__ void k_epi_publish(const ReplayRing R) {
+    if (R.enc_err && *R.enc_err != INT_MAX) return;  // a state the format cannot hold: the count stays (the commit reports the env)
     const long long c = R.ctr[0] + R.ctr[1];
     R.ctr[0] = c;
     *reinterpret_cast<volatile long long*>(R.num_added) = c;

@@ -40,6 +40,7 @@ struct ExtEnv {
     float* reward;  // [B] uploaded rewards
     unsigned char* done;  // [B] uploaded done flags
     int* err;       // [1] smallest env whose open trajectory outgrew the record ring (INT_MAX: none)
+    int* enc_err;   // [1] int8 replay states only: smallest env with an observation element int8 cannot hold (ReplayRing.enc_err), else null
 };
 
 struct ExtLaunch {

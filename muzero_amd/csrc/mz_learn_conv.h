@@ -1409,7 +1409,7 @@ __global__ __launch_bounds__(256) void k_lc_relu_bwd(const float* g, const float
 // Batch plumbing: replay rows -> dense observations and actions (replay.py:27-32 `Transition` storages addressed by row index)
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct LcBatch {
-    const void* state;     // [cap][C0 * hw] float32 or int8
+    const void* state;     // [cap][C0 * hw] float32 or int8, or [cap][row_bytes] packed uint8 frames (state_i8 == 2)
     const void* action;    // [cap][K] int8 or int16
     const float* pi;       // [cap][K][A]
     const float* value;    // [cap][K]
@@ -1418,10 +1418,38 @@ struct LcBatch {
     const float* w;        // [B]
     float* prio;           // [B]
     int B, state_i8, action_bytes, K, A, in_dim;
+    int row_bytes, fS, fP, fHW;  // state_i8 == 2 (frames_u8): bytes per row, stacked frames, frame bytes fS * C * fHW, plane size
 };
+// frames_u8 rows (muzero_amd/replay.py encode_state): fP pixel bytes in the observation's plane order, fS action bytes, padding.  A lane
+// decodes sixteen pixels from one 16-byte load -- (float)b / 255.0f, IEEE division, the expression mz_extenv.h builds the planes with --
+// and the fS constant action planes, (float)((double)(a + 1) / (double)A), are filled plane by plane.
+__device__ inline void lc_gather_frames(const LcBatch& bt, const unsigned char* row, float* o) {
+    const int P = bt.fP;
+    for (int q0 = (blockIdx.x * 256 + threadIdx.x) * 16; q0 < P; q0 += gridDim.x * 4096) {
+        const uint4 w4 = *reinterpret_cast<const uint4*>(row + q0);
+        const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+        if (q0 + 16 <= P && (bt.in_dim & 3) == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                *reinterpret_cast<float4*>(o + q0 + 4 * j) = make_float4((float)(w[j] & 0xffu) / 255.0f, (float)((w[j] >> 8) & 0xffu) / 255.0f,
+                                                                         (float)((w[j] >> 16) & 0xffu) / 255.0f, (float)(w[j] >> 24) / 255.0f);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; j++)
+                if (q0 + j < P) o[q0 + j] = (float)((w[j >> 2] >> (8 * (j & 3))) & 0xffu) / 255.0f;
+        }
+    }
+    for (int k = 0; k < bt.fS; k++) {
+        const float f = (float)((double)((int)row[P + k] + 1) / (double)bt.A);
+        float* pl = o + P + (size_t)k * bt.fHW;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < bt.fHW; i += gridDim.x * 256) pl[i] = f;
+    }
+}
 __global__ __launch_bounds__(256) void k_lc_gather(const LcBatch bt, float* obs, int* act) {
     const int b = blockIdx.y;
     const int64_t row = bt.idx[b];
+    if (bt.state_i8 == 2) lc_gather_frames(bt, reinterpret_cast<const unsigned char*>(bt.state) + (size_t)row * bt.row_bytes, obs + (size_t)b * bt.in_dim);
+    else
     for (int i = blockIdx.x * 256 + threadIdx.x; i < bt.in_dim; i += gridDim.x * 256)
         obs[(size_t)b * bt.in_dim + i] = bt.state_i8 ? (float)reinterpret_cast<const int8_t*>(bt.state)[row * bt.in_dim + i]
                                                     : reinterpret_cast<const float*>(bt.state)[row * bt.in_dim + i];

@@ -1420,6 +1420,10 @@ static int ring_finish_move(mz_planner* p) {
         EpiLaunch E{};
         E.env = p->env; E.ring = p->replay; E.B = p->cfg.num_envs; E.move_abs = p->selfplay_moves;
         hipLaunchKernelGGL(k_epi_scan, dim3(1), dim3(1024), 0, p->stream, E);
+        if (E.ring.state_format != STATE_F32) {  // compact states: before k_epilogue moves ep_start
+            const int per = E.ring.state_format == STATE_I8 ? 1024 : 4096, chunks = (E.ring.row_bytes + 3 + per - 1) / per;
+            hipLaunchKernelGGL(k_epi_states, dim3(chunks < 64 ? chunks : 64, EPS_ITEMS), dim3(256), 0, p->stream, E);
+        }
         hipLaunchKernelGGL(k_epilogue, dim3(p->cfg.num_envs), dim3(64), (size_t)p->ring_len * sizeof(double), p->stream, E);
         hipLaunchKernelGGL(k_epi_publish, dim3(1), dim3(1), 0, p->stream, p->replay);
     }
@@ -1448,6 +1452,13 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         if (h_init_state) return fail(MZ_E_INVALID, "the synthetic env takes no initial state");
     } else {
         return fail(MZ_E_INVALID, "unknown env kind");
+    }
+    if (p->has_replay && p->replay.state_format != STATE_F32) {
+        if (p->replay.state_format != STATE_I8 || (env_kind != MZ_ENV_TICTACTOE && env_kind != MZ_ENV_GOMOKU))
+            return fail(MZ_E_INVALID, "mz_replay_ring.state_format: of the device envs only TicTacToe and Gomoku have exact compact states (MZ_STATE_I8); "
+                                      "CartPole and the synthetic env need MZ_STATE_F32, MZ_STATE_FRAMES_U8 a host-stepped env with uint8 frames");
+        p->replay.row_bytes = obs_dim(c);
+        p->replay.enc_err = nullptr;
     }
     p->env_kind = env_kind;
     p->arena_open = false;
@@ -1507,7 +1518,8 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
 // self-play on host-stepped environments (mz_extenv.h)
 // ---------------------------------------------------------------------------------------------------------
 static void ext_free(mz_planner* p) {
-    void* dbufs[] = {p->ext.frames, p->ext.hist, p->ext.hist_act, p->ext.head, p->ext.reward, p->ext.done, p->ext.err};
+    void* dbufs[] = {p->ext.frames, p->ext.hist, p->ext.hist_act, p->ext.head, p->ext.reward, p->ext.done, p->ext.err, p->ext.enc_err};
+    if (p->ext.enc_err) p->replay.enc_err = nullptr;
     for (void* b : dbufs)
         if (b) (void)hipFree(b);
     void* hbufs[] = {p->h_ext_frames, p->h_ext_mask, p->h_ext_done, p->h_ext_cur, p->h_ext_opp, p->h_ext_action, p->h_ext_err, p->h_ext_reward};
@@ -1545,6 +1557,12 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
         return fail(MZ_E_INVALID, "mz_external_env: the stacked observation has " + std::to_string(stacked) + " values, the network's (obs_c*obs_h*obs_w) " +
                                       std::to_string(obs_dim(c)));
     if (S == 0 && x->frame_u8) return fail(MZ_E_INVALID, "mz_external_env: frame_u8 needs stack_history > 0 (whole observations are float32)");
+    const int fmt = p->has_replay ? p->replay.state_format : STATE_F32;
+    if (fmt == STATE_FRAMES_U8) {
+        if (S == 0 || !x->is_obs_image || !x->frame_u8)
+            return fail(MZ_E_INVALID, "mz_replay_ring.state_format MZ_STATE_FRAMES_U8 needs stack_history > 0, is_obs_image and frame_u8 (float frames are not bytes)");
+        if (c.num_actions > 256) return fail(MZ_E_INVALID, "mz_replay_ring.state_format MZ_STATE_FRAMES_U8 holds an action in one byte: num_actions > 256");
+    }
     ext_free(p);
     p->arena_open = false;
     p->env_kind = MZ_ENV_EXTERNAL;
@@ -1567,6 +1585,16 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
     HIPCHK(hipMalloc(&X.reward, B * sizeof(float)));
     HIPCHK(hipMalloc(&X.done, B));
     HIPCHK(hipMalloc(&X.err, sizeof(int)));
+    if (fmt != STATE_F32) {
+        ReplayRing& R = p->replay;
+        R.fS = S; R.fC = X.C; R.fHW = X.HW; R.fP = S * X.FE;
+        R.row_bytes = fmt == STATE_I8 ? obs_dim(c) : (R.fP + S + 15) / 16 * 16;
+        R.enc_err = nullptr;
+        if (fmt == STATE_I8) {  // whole observations of any env: every emitted state is checked
+            HIPCHK(hipMalloc(&X.enc_err, sizeof(int)));
+            R.enc_err = X.enc_err;
+        }
+    }
     HIPCHK(hipHostMalloc(&p->h_ext_frames, B * fbytes, hipHostMallocDefault));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_mask), B * c.num_actions, hipHostMallocDefault));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_cur), B * sizeof(int), hipHostMallocDefault));
@@ -1577,6 +1605,7 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_err), sizeof(int), hipHostMallocDefault));
     const int none = INT_MAX;
     HIPCHK(hipMemcpyAsync(X.err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
+    if (X.enc_err) HIPCHK(hipMemcpyAsync(X.enc_err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     return MZ_OK;
 }
@@ -1585,7 +1614,7 @@ extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, con
                                         double temperature, int32_t* h_action) {
     if (!p || !h_frames || !h_mask || !h_cur || !h_opp || !h_action) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_act");
     if (p->env_kind != MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "call mz_selfplay_reset_external first");
-    if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory: call mz_selfplay_reset_external");
+    if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory or a state its replay format cannot hold: call mz_selfplay_reset_external");
     if (p->ext_pending) return fail(MZ_E_STATE, "mz_selfplay_external_act twice: commit the last act's outcome first");
     if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
@@ -1628,7 +1657,7 @@ extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, con
 extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done) {
     if (!p || !h_reward || !h_done) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_commit");
     if (p->env_kind != MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "call mz_selfplay_reset_external first");
-    if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory: call mz_selfplay_reset_external");
+    if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory or a state its replay format cannot hold: call mz_selfplay_reset_external");
     if (!p->ext_pending) return fail(MZ_E_STATE, "mz_selfplay_external_commit without an mz_selfplay_external_act");
     HIPCHK(hipSetDevice(p->device));
     const mz_config& c = p->cfg;
@@ -1650,7 +1679,17 @@ extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward,
                                           " moves outgrew the record ring (raise mz_external_env.max_episode_steps); no items written, reset next");
         }
     }
-    return ring_finish_move(p);
+    const int rc = ring_finish_move(p);
+    if (rc == MZ_OK && p->has_replay && p->replay.enc_err) {  // (the encoder has just seen the states this move emitted)
+        HIPCHK(hipMemcpyAsync(p->h_ext_err, p->replay.enc_err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        if (*p->h_ext_err != INT_MAX) {
+            p->ext_broken = true;
+            return fail(MZ_E_INVALID, "env " + std::to_string(*p->h_ext_err) + ": an observation holds a value that mz_replay_ring.state_format MZ_STATE_I8 "
+                                          "cannot hold exactly; the replay count did not advance, reset next");
+        }
+    }
+    return rc;
 }
 
 extern "C" int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ring) {
@@ -1679,7 +1718,10 @@ extern "C" int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ri
             }
         }
     }
+    if (ring->state_format != MZ_STATE_F32 && ring->state_format != MZ_STATE_I8 && ring->state_format != MZ_STATE_FRAMES_U8)
+        return fail(MZ_E_INVALID, "mz_replay_ring.state_format must be MZ_STATE_F32, MZ_STATE_I8 or MZ_STATE_FRAMES_U8");
     ReplayRing& R = p->replay;
+    R.state_format = ring->state_format; R.row_bytes = 0; R.fS = R.fC = R.fHW = R.fP = 0; R.enc_err = nullptr;
     R.capacity = ring->capacity; R.state = ring->state; R.action = reinterpret_cast<signed char*>(ring->action); R.action16 = c.num_actions > 128 ? 1 : 0; R.pi_prob = ring->pi_prob;
     R.value = ring->value; R.reward = ring->reward; R.priority = ring->priority; R.num_added = reinterpret_cast<long long*>(ring->num_added);
     R.origin = ring->origin; R.acc = ring->acc_seq_length; R.K = ring->unroll_steps; R.td = ring->td_steps; R.board = c.is_board_game;

@@ -62,7 +62,8 @@ class MzlReplayDraw(C.Structure):
 class MzlBatch(C.Structure):
     _fields_ = [('d_state', C.c_void_p), ('d_action', C.c_void_p), ('d_pi_prob', C.c_void_p), ('d_value', C.c_void_p), ('d_reward', C.c_void_p),
                 ('d_index', C.c_void_p), ('d_weights', C.c_void_p), ('d_loss', C.c_void_p), ('d_priorities', C.c_void_p), ('batch', C.c_int32),
-                ('state_is_int8', C.c_int32), ('action_bytes', C.c_int32)]
+                ('state_is_int8', C.c_int32), ('action_bytes', C.c_int32),
+                ('state_row_bytes', C.c_int32), ('frame_stack', C.c_int32), ('frame_channels', C.c_int32)]
 
 
 _lib = None
@@ -421,10 +422,12 @@ class HipLearner:
                     base_lrs=[self.lr_init], _last_lr=[self.current_lr()])
 
     # ---- the step ----
-    def grad(self, ring, index: Optional[torch.Tensor], weights: Optional[torch.Tensor], batch: int):
+    def grad(self, ring, index: Optional[torch.Tensor], weights: Optional[torch.Tensor], batch: int, frame_spec=None):
         """Loss and gradient of one batch (pipeline.py:241-244).  `ring`: mapping field -> device tensor [rows, ...] (the replay's
         storages, or a stacked batch with index=None); `index`: int64 device tensor [batch] of rows; `weights`: float32 [batch] or None
-        (uniform replay: ones).  Fills `self.grad_flat`, `self.loss`, `self.priorities[:batch]`; enqueues only."""
+        (uniform replay: ones).  Fills `self.grad_flat`, `self.loss`, `self.priorities[:batch]`; enqueues only.  States may be float32,
+        int8, or the packed uint8 rows of a `PrioritizedReplay(state_format='frames_u8')` (conv nets; the ring's storages carry their
+        `frame_spec`, a plain mapping takes it from the argument): the gather kernel decodes them exactly."""
         if batch < 1 or batch > self.max_batch:
             raise LearnerError(f'batch {batch} outside [1, max_batch = {self.max_batch}]')
         if self._param_versions() != self._seen_versions:
@@ -432,11 +435,23 @@ class HipLearner:
             # in-place edit): the master weights are those tensors, the kernels' operand copies are rebuilt from them
             self.commit()
         st, ac = ring['state'], ring['action']
-        if st.dtype not in (torch.float32, torch.int8) or not st.is_contiguous():
-            raise LearnerError(f'state storage must be contiguous float32 or int8, got {st.dtype}')
+        frame_spec = frame_spec if frame_spec is not None else getattr(ring, 'frame_spec', None)
+        frames = st.dtype == torch.uint8
+        if st.dtype not in (torch.float32, torch.int8, torch.uint8) or not st.is_contiguous():
+            raise LearnerError(f'state storage must be contiguous float32, int8 or packed uint8 frames, got {st.dtype}')
         if ac.dtype not in (torch.int8, torch.int16) or not ac.is_contiguous():
             raise LearnerError(f'action storage must be contiguous int8 or int16, got {ac.dtype}')
-        if int(np.prod(st.shape[1:])) != self.in_dim or tuple(ac.shape[1:]) != (self.K,) or tuple(ring['pi_prob'].shape[1:]) != (self.K, self.A):
+        row_bytes = fs = fc = 0
+        if frames:
+            if frame_spec is None or len(tuple(frame_spec)) != 5:
+                raise LearnerError('uint8 states are state_format frames_u8 rows: frame_spec = (S, C, H, W, A) is required')
+            fs, fc, fh, fw, fa = (int(v) for v in frame_spec)
+            row_bytes = int(np.prod(st.shape[1:]))
+            if fa != self.A or fs * (fc + 1) * fh * fw != self.in_dim or st.dim() != 2:
+                raise LearnerError(f'state_format frames_u8: frame_spec {tuple(frame_spec)} does not match the learner ({self.in_dim} observation elements, {self.A} actions)')
+        elif int(np.prod(st.shape[1:])) != self.in_dim:
+            raise LearnerError('replay item shapes do not match the learner')
+        if tuple(ac.shape[1:]) != (self.K,) or tuple(ring['pi_prob'].shape[1:]) != (self.K, self.A):
             raise LearnerError('replay item shapes do not match the learner')
         for f in ('pi_prob', 'value', 'reward'):
             if ring[f].dtype != torch.float32 or not ring[f].is_contiguous():
@@ -457,7 +472,7 @@ class HipLearner:
             raise LearnerError('weights must be a float32 tensor of `batch` entries')
         b = MzlBatch(st.data_ptr(), ac.data_ptr(), ring['pi_prob'].data_ptr(), ring['value'].data_ptr(), ring['reward'].data_ptr(),
                      index.data_ptr(), w.data_ptr(), self.loss.data_ptr(), self.priorities.data_ptr(), batch,
-                     1 if st.dtype == torch.int8 else 0, ac.element_size())
+                     2 if frames else (1 if st.dtype == torch.int8 else 0), ac.element_size(), row_bytes, fs, fc)
         _check(load_library().mzl_grad(self._h, C.byref(b), self._stream()))
         self._keep = (ring, index, w)  # alive until the next call (the kernels read them asynchronously)
         if self.buffer_views:
@@ -473,10 +488,10 @@ class HipLearner:
                                         self.steps, self._stream()))
         self._bump_epoch()
 
-    def step(self, ring, index, weights, batch: int, allreduce: bool = True):
+    def step(self, ring, index, weights, batch: int, allreduce: bool = True, frame_spec=None):
         """One update.  With an initialised multi-rank process group the flat gradient is averaged over the ranks in ONE all-reduce
         (RCCL; xGMI rings are per-link bound, so one 1-30 MB transfer beats per-tensor collectives) between gradient and update."""
-        loss, prio = self.grad(ring, index, weights, batch)
+        loss, prio = self.grad(ring, index, weights, batch, frame_spec=frame_spec)
         if allreduce:
             import torch.distributed as dist
 
@@ -486,19 +501,22 @@ class HipLearner:
         self.apply()
         return loss, prio
 
-    def step_transitions(self, transitions, weights=None):
-        """One update on a stacked batch (`Transition` of arrays / tensors, as `replay.sample` returns them)."""
+    def step_transitions(self, transitions, weights=None, frame_spec=None):
+        """One update on a stacked batch (`Transition` of arrays / tensors, as `replay.sample` returns them).  uint8 states are packed
+        `frames_u8` rows [B, row bytes] and need their `frame_spec`."""
         def dev(x, dt):
             t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
             return t.to(self.device, dt).contiguous()
 
         st = transitions.state
         st_dt = torch.int8 if (torch.is_tensor(st) and st.dtype == torch.int8) or (not torch.is_tensor(st) and np.asarray(st).dtype == np.int8) else torch.float32
+        if frame_spec is not None and ((torch.is_tensor(st) and st.dtype == torch.uint8) or (not torch.is_tensor(st) and np.asarray(st).dtype == np.uint8)):
+            st_dt = torch.uint8
         B = int(st.shape[0])
         ring = dict(state=dev(st, st_dt).reshape(B, -1), action=dev(transitions.action, torch.int16 if self.A > 128 else torch.int8),
                     pi_prob=dev(transitions.pi_prob, torch.float32), value=dev(transitions.value, torch.float32), reward=dev(transitions.reward, torch.float32))
         w = None if weights is None else dev(weights, torch.float32)
-        return self.step(ring, None, w, B)
+        return self.step(ring, None, w, B, frame_spec=frame_spec if st_dt == torch.uint8 else None)
 
     def debug_conv(self, direction: int, weight, x, action=None, num_actions: int = 0, cin: Optional[int] = None):
         """Diagnostic (tests): ONE 3 x 3 conv through the learner's packers, tiling chooser and dispatcher at this handle's conv_precision

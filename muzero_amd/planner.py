@@ -53,7 +53,7 @@ class MzRngInputs(C.Structure):
 class MzReplayRing(C.Structure):
     _fields_ = [('capacity', C.c_int64), ('state', C.c_void_p), ('action', C.c_void_p), ('pi_prob', C.c_void_p), ('value', C.c_void_p),
                 ('reward', C.c_void_p), ('priority', C.c_void_p), ('num_added', C.c_void_p), ('origin', C.c_void_p),
-                ('acc_seq_length', C.c_int32), ('unroll_steps', C.c_int32), ('td_steps', C.c_int32)]
+                ('acc_seq_length', C.c_int32), ('unroll_steps', C.c_int32), ('td_steps', C.c_int32), ('state_format', C.c_int32)]
 
 
 class MzExternalEnv(C.Structure):
@@ -427,6 +427,13 @@ class Planner:
             c, h, w = fs
         else:
             c, h, w = int(np.prod(fs)), 1, 1
+        keep = getattr(self, '_replay_keepalive', None)
+        ring = None if keep is None else keep[0]._ring
+        if ring is not None and getattr(ring, 'state_format', 'f32') == 'frames_u8' and stack_history > 0 and is_obs_image and \
+                tuple(ring.frame_spec[:4]) != (int(stack_history), c, h, w):  # (an env without stacked image frames: the library refuses it)
+            # (the kernel sizes a row from the env: a ring built for other frames would be written out of bounds)
+            raise PlannerError(f'the attached replay\'s frame_spec {tuple(ring.frame_spec)} is not this env\'s (stack_history, C, H, W) = '
+                               f'{(int(stack_history), c, h, w)}')
         self._ext_frame = (fs, np.uint8 if frame_u8 else np.float32)
         x = MzExternalEnv(int(stack_history), int(bool(is_obs_image)), c, h, w, int(bool(frame_u8)), int(max_episode_steps), int(temp_switch_steps))
         _chk(self.lib.mz_selfplay_reset_external(self.h, C.byref(x)))
@@ -472,8 +479,11 @@ class Planner:
         -- a `muzero_amd.replay.PrioritizedReplay(device='cuda')` -- on the GPU, with the reference's target / unroll-window
         arithmetic (pipeline.py:118-165, 632-767); the host only reads `replay.num_added`.  `config` supplies acc_seq_length,
         unroll_steps, td_steps.  Call before `selfplay_reset`.  `with_origin`: also record which env produced each item
-        (returned tensor; tests)."""
+        (returned tensor; tests).  A replay built with `state_format='int8'` / `'frames_u8'` gets its states in that exact compact form
+        (mzplanner.h MZ_STATE_*); the env's reset refuses a format its observations do not fit."""
         import torch
+
+        from muzero_amd.replay import STATE_FORMATS, state_row_bytes
 
         K, A = int(config.unroll_steps), self.A
         shp = tuple(obs_shape) if obs_shape is not None else (self.obs_dim,)
@@ -481,15 +491,25 @@ class Planner:
         if replay._ring is None:
             replay.allocate(dict(state=shp, action=(K,), pi_prob=(K, A), value=(K,), reward=(K,)), dict(action=adt))
         ring = replay._ring
-        if ring['state'].device.type != 'cuda' or ring['state'].dtype != torch.float32 or ring['action'].dtype != adt:
-            raise PlannerError(f'attach_replay needs a replay on the GPU with float32 states and {adt} actions ({A} actions)')
-        if int(np.prod(ring['state'].shape[1:])) != self.obs_dim or tuple(ring['pi_prob'].shape[1:]) != (K, A):
+        fmt = getattr(ring, 'state_format', 'f32')
+        sdt = {'f32': torch.float32, 'int8': torch.int8, 'frames_u8': torch.uint8}[fmt]
+        if ring['state'].device.type != 'cuda' or ring['state'].dtype != sdt or ring['action'].dtype != adt:
+            raise PlannerError(f'attach_replay needs a replay on the GPU with float32 states and {adt} actions ({A} actions)' if fmt == 'f32' else
+                               f'attach_replay needs a replay on the GPU; state_format {fmt!r} stores {sdt} states and {adt} actions ({A} actions)')
+        if fmt == 'frames_u8':
+            S, Cf, H, W, Af = ring.frame_spec
+            if Af != A or S * (Cf + 1) * H * W != self.obs_dim:
+                raise PlannerError(f'replay frame_spec {ring.frame_spec} does not match the planner ({self.obs_dim} observation elements, {A} actions)')
+            state_elems = self.obs_dim if tuple(ring['state'].shape[1:]) == (state_row_bytes(fmt, (self.obs_dim,), ring.frame_spec),) else -1
+        else:
+            state_elems = int(np.prod(ring['state'].shape[1:]))
+        if state_elems != self.obs_dim or tuple(ring['pi_prob'].shape[1:]) != (K, A):
             raise PlannerError('replay item shapes do not match the planner (observation size, unroll_steps, num_actions)')
         prio, count = replay.attach_device_writer()
         origin = torch.full((replay.capacity,), -1, dtype=torch.int32, device=ring['state'].device) if with_origin else None
         r = MzReplayRing(replay.capacity, ring['state'].data_ptr(), ring['action'].data_ptr(), ring['pi_prob'].data_ptr(), ring['value'].data_ptr(),
                          ring['reward'].data_ptr(), prio.data_ptr(), count.data_ptr(), origin.data_ptr() if with_origin else None,
-                         int(config.acc_seq_length), K, int(config.td_steps))
+                         int(config.acc_seq_length), K, int(config.td_steps), STATE_FORMATS[fmt])
         torch.cuda.synchronize()
         _chk(self.lib.mz_selfplay_attach_replay(self.h, C.byref(r)))
         self._replay_keepalive = (replay, prio, count, origin)

@@ -7,8 +7,10 @@ Storage is one preallocated tensor per `Transition` field (`state [cap, *shape]`
 ring lives in HBM, `sample_tensors` hands the learner device tensors without a host round trip, and the planner's
 device epilogue (`Planner.attach_replay`) writes finished transitions straight into it.  States are stored in the dtype
 of the first item unless `state_dtype` says otherwise: float32 Atari-sized states (8x96x96) cost 295 KB each, so 10^6 of
-them do NOT fit even 288 GB -- pass `state_dtype=torch.float16` / `torch.uint8` for image states (converted back to
-float32 in `sample_tensors`); the constructor-time size check refuses a ring that exceeds the free memory of its device
+them do NOT fit even 288 GB -- pass `state_format='frames_u8'` with the frames' `frame_spec` (stacked uint8 image frames) or
+`state_format='int8'` (board planes): EXACT compact rows, encoded by `add` / `add_batch` and by the planner's epilogue, decoded by `get` /
+`sample` / `sample_tensors` and by the HIP learner's gather (see `encode_state`); or a lossy `state_dtype=torch.float16` / `torch.uint8`
+(host path only, converted back to float32 in `sample_tensors`); the constructor-time size check refuses a ring that exceeds the free memory of its device
 instead of letting the process die.  With the default `device='cpu'` it is a drop-in for the reference class.
 
 Thread safety: the collector thread adds while the learner thread samples (pipeline.py:491-538 vs :238-255).  The
@@ -43,15 +45,131 @@ class Transition(NamedTuple):
 TransitionStructure = Transition(state=None, action=None, pi_prob=None, value=None, reward=None)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Compact, EXACT state formats: what the ring stores instead of float32 observations.  These two numpy functions are the
+# reference of the format; the planner's k_epi_states writes it and the learner's k_lc_gather reads it (include/mzplanner.h
+# MZ_STATE_*, include/mzlearner.h mzl_batch.state_is_int8).
+#   'int8'      one signed byte per element; valid when float32(int8(v)) == v bit for bit (the 0 / 1 planes of the board games).
+#   'frames_u8' observations of StackFrameAndAction(S, is_obs_image=True) over uint8 frames [C, H, W] scaled by 1 / 255
+#               (games.py:145-206): the S*C*H*W frame bytes in the observation's plane order (plane k*C + c, k = 0 the newest frame),
+#               then S action bytes (byte k: the action whose plane is plane S*C + k), zero-padded to a multiple of 16 bytes.
+#               A pixel decodes to float32(b) / float32(255), an action plane to float32(float64(a + 1) / float64(A)).
+# ---------------------------------------------------------------------------------------------------------------------
+STATE_FORMATS = {'f32': 0, 'int8': 1, 'frames_u8': 2}
+
+
+def _frame_geometry(frame_spec):
+    if frame_spec is None or len(tuple(frame_spec)) != 5:
+        raise ValueError(f'state_format frames_u8 needs frame_spec = (S, C, H, W, A), got {frame_spec}')
+    S, C, H, W, A = (int(v) for v in frame_spec)
+    if min(S, C, H, W, A) < 1:
+        raise ValueError(f'frame_spec (S, C, H, W, A) = {(S, C, H, W, A)}: every entry must be >= 1')
+    if A > 256:
+        raise ValueError(f'state_format frames_u8 holds an action in one byte: frame_spec A = {A} > 256')
+    P = S * C * H * W
+    return S, C, H, W, A, P, (P + S + 15) // 16 * 16
+
+
+def state_row_bytes(state_format, item_shape, frame_spec=None) -> int:
+    """Bytes one state takes in the ring."""
+    D = int(np.prod(item_shape, dtype=np.int64))
+    if state_format == 'frames_u8':
+        S, C, H, W, _, _, row = _frame_geometry(frame_spec)
+        if S * (C + 1) * H * W != D:
+            raise ValueError(f'frame_spec {tuple(frame_spec)} describes {S * (C + 1) * H * W} observation elements, the state has {D}')
+        return row
+    return D if state_format == 'int8' else 4 * D
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def encode_state(x, state_format, frame_spec=None) -> np.ndarray:
+    """float32 observation(s) -> the compact form: int8 of x's shape, or uint8 [..., row bytes] for x of shape [..., S*(C+1), H, W]
+    (any number of leading axes).  Raises ValueError naming the first element the format cannot hold exactly."""
+    x = np.ascontiguousarray(x, np.float32)
+    if state_format == 'int8':
+        q = np.clip(np.nan_to_num(np.rint(x), nan=0.0), -128, 127).astype(np.int8)
+        bad = _bits(q.astype(np.float32)) != _bits(x)
+        if bad.any():
+            i = np.unravel_index(int(np.argmax(bad)), x.shape)
+            raise ValueError(f'state_format int8: element {tuple(int(v) for v in i)} = {x[i]!r} is not an int8 value')
+        return q
+    if state_format != 'frames_u8':
+        raise ValueError(f'unknown state_format {state_format!r}')
+    S, C, H, W, A, P, row = _frame_geometry(frame_spec)
+    HW = H * W
+    if x.ndim < 3 or tuple(x.shape[-3:]) != (S * (C + 1), H, W):
+        raise ValueError(f'frame_spec {tuple(frame_spec)} describes observations [{S * (C + 1)}, {H}, {W}], got shape {x.shape}')
+    lead = x.shape[:-3]
+    v = x.reshape(-1, S * (C + 1), HW)
+    pix = v[:, :S * C]
+    b = np.clip(np.nan_to_num(np.rint(pix * np.float32(255.0)), nan=0.0), 0, 255).astype(np.uint8)
+    bad = _bits(b.astype(np.float32) / np.float32(255.0)) != _bits(pix)
+    if bad.any():
+        n, p, i = (int(t) for t in np.unravel_index(int(np.argmax(bad)), bad.shape))
+        raise ValueError(f'state_format frames_u8: element (item {n}, plane {p}, pixel {i}) = {pix[n, p, i]!r} is not b / 255 for a byte b')
+    act = v[:, S * C:]
+    a1 = np.clip(np.nan_to_num(np.rint(act[:, :, 0].astype(np.float64) * A), nan=0.0), 1, A)
+    bad = _bits(np.broadcast_to((a1 / float(A)).astype(np.float32)[:, :, None], act.shape)) != _bits(act)
+    if bad.any():
+        n, k, i = (int(t) for t in np.unravel_index(int(np.argmax(bad)), bad.shape))
+        why = 'differs from the plane\'s first element: an action plane is constant' if _bits(act[n, k, i]) != _bits(act[n, k, 0]) \
+            else f'is not (a + 1) / {A} for an action a'
+        raise ValueError(f'state_format frames_u8: element (item {n}, plane {S * C + k}, pixel {i}) = {act[n, k, i]!r} {why}')
+    out = np.zeros((v.shape[0], row), np.uint8)
+    out[:, :P] = b.reshape(-1, P)
+    out[:, P:P + S] = (a1 - 1).astype(np.uint8)
+    return out.reshape(lead + (row,))
+
+
+def decode_state(row, state_format, frame_spec=None) -> np.ndarray:
+    """The inverse of `encode_state`: float32, bit-equal to what was encoded."""
+    row = np.asarray(row)
+    if state_format == 'int8':
+        return row.astype(np.int8).astype(np.float32)
+    if state_format != 'frames_u8':
+        raise ValueError(f'unknown state_format {state_format!r}')
+    S, C, H, W, A, P, nbytes = _frame_geometry(frame_spec)
+    if row.shape[-1] != nbytes:
+        raise ValueError(f'frame_spec {tuple(frame_spec)} describes rows of {nbytes} bytes, got {row.shape[-1]}')
+    lead = row.shape[:-1]
+    r = row.reshape(-1, nbytes).astype(np.uint8)
+    out = np.empty((r.shape[0], S * (C + 1), H * W), np.float32)
+    out[:, :S * C] = (r[:, :P].astype(np.float32) / np.float32(255.0)).reshape(-1, S * C, H * W)
+    out[:, S * C:] = ((r[:, P:P + S].astype(np.float64) + 1.0) / float(A)).astype(np.float32)[:, :, None]
+    return out.reshape(lead + (S * (C + 1), H, W))
+
+
+class RingStorage(dict):
+    """field -> tensor [capacity, ...], plus how `state` is stored (what hip_learner.HipLearner.grad and Planner.attach_replay read)."""
+
+    state_format = 'f32'
+    frame_spec = None
+
+
 class PrioritizedReplay:
     """replay.py:39-142 with array storage.  `priority_exponent == 0` is uniform replay (all launchers' default)."""
 
     FIELDS = Transition._fields
 
     def __init__(self, capacity: int, priority_exponent: float, importance_sampling_exponent: float, random_state: np.random.RandomState,
-                 device='cpu', state_dtype: Optional[torch.dtype] = None):
+                 device='cpu', state_dtype: Optional[torch.dtype] = None, state_format: Optional[Text] = None,
+                 frame_spec: Optional[Sequence[int]] = None):
         if capacity <= 0:
             raise ValueError(f'Expect capacity to be a positive integer, got {capacity}')
+        state_format = state_format or 'f32'
+        if state_format not in STATE_FORMATS:
+            raise ValueError(f'state_format must be None, \'int8\' or \'frames_u8\', got {state_format!r}')
+        if state_format != 'f32' and state_dtype is not None:
+            raise ValueError('state_format and state_dtype exclude each other (an exact format, or a lossy narrow dtype)')
+        if state_format == 'frames_u8':
+            _frame_geometry(frame_spec)
+        elif frame_spec is not None:
+            raise ValueError(f'frame_spec belongs to state_format \'frames_u8\', not {state_format!r}')
+        self._fmt, self._frame_spec = state_format, (None if frame_spec is None else tuple(int(v) for v in frame_spec))
+        self._state_shape = None  # per-item shape of the float32 state (compact formats: the ring holds another shape)
         self.structure = TransitionStructure
         self._cap, self._count = int(capacity), 0
         self._rng = random_state
@@ -77,6 +195,15 @@ class PrioritizedReplay:
         defaults.update(dtypes or {})
         if self._state_dtype is not None:
             defaults['state'] = self._state_dtype
+        self._state_shape = tuple(int(d) for d in shapes['state'])
+        if self._fmt != 'f32':  # the size check below counts the compact row
+            shapes = dict(shapes)
+            if self._fmt == 'frames_u8':
+                shapes['state'] = (state_row_bytes(self._fmt, self._state_shape, self._frame_spec),)
+                S, C, H, W = self._frame_spec[:4]
+                if len(self._state_shape) > 1 and self._state_shape != (S * (C + 1), H, W):
+                    raise ValueError(f'frame_spec {self._frame_spec} describes observations {(S * (C + 1), H, W)}, the state has shape {self._state_shape}')
+            defaults['state'] = torch.int8 if self._fmt == 'int8' else torch.uint8
         need = sum(int(np.prod(shapes[f], dtype=np.int64)) * torch.empty(0, dtype=defaults[f]).element_size() for f in self.FIELDS) * self._cap
         if self._dev.type == 'cuda':
             free = torch.cuda.mem_get_info(self._dev)[0]
@@ -91,8 +218,37 @@ class PrioritizedReplay:
                 free = float('inf')
         if need > 0.9 * free:
             raise MemoryError(f'replay of {self._cap} items needs {need / 2**30:.1f} GiB on {self._dev} but only {free / 2**30:.1f} GiB are free: '
-                              f'lower the capacity or store states in a narrower dtype (state_dtype=torch.float16 / torch.uint8)')
-        self._ring = {f: torch.zeros((self._cap,) + tuple(shapes[f]), dtype=defaults[f], device=self._dev) for f in self.FIELDS}
+                              f'lower the capacity or store states compactly (state_format=\'int8\' / \'frames_u8\', or a lossy state_dtype)')
+        self._ring = self._storage({f: torch.zeros((self._cap,) + tuple(shapes[f]), dtype=defaults[f], device=self._dev) for f in self.FIELDS})
+
+    def _storage(self, tensors) -> RingStorage:
+        ring = RingStorage(tensors)
+        ring.state_format, ring.frame_spec = self._fmt, self._frame_spec
+        return ring
+
+    def _encode(self, state) -> np.ndarray:
+        """float32 state(s) -> what the ring holds (compact formats only)"""
+        if torch.is_tensor(state):
+            state = state.detach().cpu().numpy()
+        state = np.ascontiguousarray(state, np.float32)
+        if self._fmt == 'frames_u8' and state.ndim < 3:  # (flattened observations)
+            S, C, H, W = self._frame_spec[:4]
+            state = state.reshape(state.shape[:-1] + (S * (C + 1), H, W))
+        return encode_state(state, self._fmt, self._frame_spec)
+
+    def _decode_tensor(self, st: torch.Tensor) -> torch.Tensor:
+        """ring rows [n, ...] -> float32 states [n, *state shape] on the rows' device, bit-equal to what was added"""
+        n = st.shape[0]
+        if self._fmt == 'int8':
+            return st.to(torch.float32)
+        # table look-ups, so that the values are numpy's (IEEE division) whatever the device's division does
+        S, C, H, W, A, P, _ = _frame_geometry(self._frame_spec)
+        if getattr(self, '_lut', None) is None or self._lut[0].device != st.device:
+            self._lut = (torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(st.device),
+                         torch.from_numpy(((np.arange(A, dtype=np.float64) + 1.0) / float(A)).astype(np.float32)).to(st.device))
+        pix = torch.index_select(self._lut[0], 0, st[:, :P].reshape(-1).to(torch.int32)).reshape(n, S * C, H, W)
+        act = torch.index_select(self._lut[1], 0, st[:, P:P + S].reshape(-1).to(torch.int32)).reshape(n, S, 1, 1).expand(n, S, H, W)
+        return torch.cat([pix, act], dim=1).reshape((n,) + self._state_shape)
 
     def _allocate(self, item: Transition) -> None:
         arrs = [np.asarray(x) for x in item]
@@ -101,8 +257,9 @@ class PrioritizedReplay:
 
     def _check_shapes(self, item_shapes) -> None:
         for f, shp in zip(self.FIELDS, item_shapes):
-            if tuple(shp) != tuple(self._ring[f].shape[1:]):
-                raise ValueError(f'Transition.{f} has shape {tuple(shp)}, the replay holds {tuple(self._ring[f].shape[1:])}')
+            held = self._state_shape if f == 'state' and self._fmt != 'f32' else tuple(self._ring[f].shape[1:])
+            if tuple(shp) != tuple(held):
+                raise ValueError(f'Transition.{f} has shape {tuple(shp)}, the replay holds {tuple(held)}')
 
     def _host_writer_only(self, what: str) -> None:
         if self._attached is not None:
@@ -118,6 +275,8 @@ class PrioritizedReplay:
                 self._allocate(item)
             arrs = [np.ascontiguousarray(x) for x in item]
             self._check_shapes([a.shape for a in arrs])
+            if self._fmt != 'f32':
+                arrs[0] = self._encode(arrs[0])
             slot = self._count % self._cap
             for name, a in zip(self.FIELDS, arrs):
                 self._ring[name][slot] = torch.from_numpy(a).to(self._ring[name].dtype)
@@ -133,6 +292,8 @@ class PrioritizedReplay:
             if self._ring is None:
                 self._allocate(Transition(*[np.asarray(x)[0] for x in items]))
             self._check_shapes([tuple(x.shape[1:]) for x in items])
+            if self._fmt != 'f32':
+                items = Transition(self._encode(items[0]), *items[1:])
             slots = (self._count + np.arange(n)) % self._cap
             tslots = torch.from_numpy(slots).to(self._dev)
             for name, x in zip(self.FIELDS, items):
@@ -145,7 +306,10 @@ class PrioritizedReplay:
         """Items by index (replay.py:77-79)."""
         with self._lock:
             self._sync_attached()
-            return [Transition(*[self._ring[f][int(i)].cpu().numpy() for f in self.FIELDS]) for i in indices]
+            items = [Transition(*[self._ring[f][int(i)].cpu().numpy() for f in self.FIELDS]) for i in indices]
+        if self._fmt != 'f32':
+            items = [it._replace(state=decode_state(it.state, self._fmt, self._frame_spec).reshape(self._state_shape)) for it in items]
+        return items
 
     # ---- device epilogue (Planner.attach_replay): the planner writes items and priorities, this class only counts ----
     def attach_device_writer(self):
@@ -208,6 +372,8 @@ class PrioritizedReplay:
             batch = [self._ring[f].index_select(0, tpicks) for f in self.FIELDS]
         if batch[0].dtype != torch.float32 and self._state_dtype is not None:
             batch[0] = batch[0].to(torch.float32)
+        if self._fmt != 'f32':
+            batch[0] = self._decode_tensor(batch[0])
         return Transition(*batch), picks, is_w
 
     def sample_indices(self, batch_size: int):
@@ -269,12 +435,21 @@ class PrioritizedReplay:
     def get_state(self) -> Mapping[Text, Any]:
         self._sync_attached()
         ring = None if self._ring is None else {k: v.cpu() for k, v in self._ring.items()}
-        return {'num_added': self._count, 'storage': ring, 'priorities': self._prio}
+        state = {'num_added': self._count, 'storage': ring, 'priorities': self._prio}
+        if self._fmt != 'f32':  # (a float32 replay's state stays what it was)
+            state.update(state_format=self._fmt, frame_spec=self._frame_spec, state_shape=self._state_shape)
+        return state
 
     def set_state(self, state: Mapping[Text, Any]) -> None:
         self._host_writer_only('set_state')  # (while attached the next read of the device counter would overwrite the restored state)
+        fmt = state.get('state_format', 'f32')
+        spec = state.get('frame_spec')
+        if fmt != self._fmt or (None if spec is None else tuple(spec)) != self._frame_spec:
+            raise ValueError(f'set_state: the saved replay stores states as {fmt!r} (frame_spec {spec}), this one as {self._fmt!r} (frame_spec {self._frame_spec})')
         self._count = state['num_added']
-        self._ring = None if state['storage'] is None else {k: v.to(self._dev) for k, v in state['storage'].items()}
+        self._ring = None if state['storage'] is None else self._storage({k: v.to(self._dev) for k, v in state['storage'].items()})
+        if self._fmt != 'f32':
+            self._state_shape = None if state.get('state_shape') is None else tuple(state['state_shape'])
         self._prio = state['priorities']
 
 
