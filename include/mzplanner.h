@@ -181,13 +181,21 @@ int mz_planner_search_scripted(mz_planner* p, int32_t batch, const float* h_pi0,
 int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* h_init_state);
 int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_moves);
 /* Copy out the records of the last `n_moves` moves (newest last): arrays [n_moves, B, ...]; any pointer may be NULL.
- * The records live in a ring of R moves (R = 64; 16 when one move of observations exceeds 64 MiB; at least an open
+ * The records live in a ring of R moves (R = 64; 16 when one move of observation records exceeds 64 MiB; at least an open
  * trajectory when a replay is attached): mz_selfplay_step may play more than R moves between reads -- older records are
- * overwritten -- and mz_selfplay_read returns MZ_E_INVALID when asked for more moves than the ring holds. */
+ * overwritten -- and mz_selfplay_read returns MZ_E_INVALID when asked for more moves than the ring holds.
+ * With compact records (mz_external_env.record_format = MZ_RECORD_FRAMES_U8) the ring is R + stack_history moves long and h_obs is
+ * rebuilt on the device, move by move, bit for bit the float32 records' observations; as many moves as ever (R) can be read.  A read whose
+ * oldest move's observation reaches back past what the ring still holds is refused (MZ_E_INVALID naming record_format) when it asks for
+ * h_obs; the same read without h_obs succeeds. */
 int mz_selfplay_read(mz_planner* p, int32_t n_moves, float* h_obs, int32_t* h_action, float* h_reward, double* h_pi,
                      double* h_root_value, int32_t* h_player, uint8_t* h_done);
 /* counters since reset: [0] env steps, [1] simulations, [2] finished episodes, [3] sum of finished episode lengths */
 int mz_selfplay_counters(mz_planner* p, int64_t out[4]);
+/* The record ring as the last reset sized it: [0] MZ_RECORD_* format, [1] ring length in moves, [2] bytes of one move's observation records
+ * (float32: num_envs * obs * 4; compact: num_envs * frame bytes rounded up to 16), [3] bytes of all record arrays (observations or frames,
+ * action, reward, pi, root value, player, done, and the compact ring's per-record step count).  No device work. */
+int mz_selfplay_record_info(mz_planner* p, int64_t out[4]);
 
 /* Device epilogue of run_self_play: what the reference does per episode on the host -- compute_n_step_target /
  * compute_mc_return_target (pipeline.py:632-707), priorities (:129,156), make_unroll_sequence (:710-767), including the
@@ -254,7 +262,20 @@ typedef struct {
     int32_t max_episode_steps; /* sizes the record ring when a replay is attached (0: acc + unroll + td window) */
     int32_t temp_switch_steps; /* temperature < 0: 1.0 for the first temp_switch_steps moves of an episode, then 0.1 (config.py:236-249:
                                   6 TicTacToe, 30 Gomoku); 0: 6 when num_actions <= 10, else 30 */
+    /* What the record ring keeps of a move's observation.  MZ_RECORD_F32 (0: a zero-initialised field): the float32 stacked observation,
+     * as ever.  MZ_RECORD_FRAMES_U8 (1): only the uint8 frame the host uploaded for the move, at a 16-byte-aligned stride (frame bytes
+     * rounded up to 16) -- S - 1 of an observation's S frames are earlier moves' records and the action planes are the recorded actions.
+     * Nothing a reader gets changes: mz_selfplay_read's h_obs and every MZ_STATE_FRAMES_U8 replay row are bit for bit the float32 ring's.
+     * Record m of an env is the frame of act m; with first(m) the start of m's episode, the observation of move m has frame block k
+     * (0 = newest, k < S) = record max(m - k, first(m)) and action plane k = the action of move m - k - 1 if m - k > first(m), else action 0
+     * (decoded as MZ_STATE_FRAMES_U8 rows are).  The ring keeps S moves more than the float32 ring would, and its 64 -> 16 rule counts frame
+     * bytes.  Refused (MZ_E_INVALID naming record_format) by mz_selfplay_reset_external: without stack_history > 0, is_obs_image and
+     * frame_u8; with num_actions > 256; with an attached replay whose state_format is not MZ_STATE_FRAMES_U8; any other value.
+     * mz_selfplay_reset (device envs) always keeps float32 records. */
+    int32_t record_format;
 } mz_external_env;
+#define MZ_RECORD_F32 0
+#define MZ_RECORD_FRAMES_U8 1
 
 int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* env);
 /* Search the current observations of all num_envs envs and return the sampled actions.

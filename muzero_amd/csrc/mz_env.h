@@ -71,7 +71,8 @@ inline void env_free(EnvState& e) {
     e = EnvState{};
 }
 
-inline hipError_t env_alloc(EnvState& e, int kind, int B, int A, int D, int ring_len, int board_n = 3, int num_to_win = 3) {
+// with_obs = false: no float32 observation records (r_obs stays null): the compact record ring of mz_extenv.h holds the frames instead
+inline hipError_t env_alloc(EnvState& e, int kind, int B, int A, int D, int ring_len, int board_n = 3, int num_to_win = 3, bool with_obs = true) {
     env_free(e);
     e.kind = kind; e.B = B; e.A = A; e.D = D; e.ring_len = ring_len;
     e.bn = board_n; e.nn = board_n * board_n; e.win = num_to_win;
@@ -86,7 +87,7 @@ inline hipError_t env_alloc(EnvState& e, int kind, int B, int A, int D, int ring
     MZ_ALLOC(e.board, (size_t)B * e.nn);
     MZ_ALLOC(e.planes, (size_t)B * 8 * e.nn);
     MZ_ALLOC(e.player, (size_t)B * sizeof(int));
-    MZ_ALLOC(e.r_obs, (size_t)ring_len * B * D * sizeof(float));
+    if (with_obs) { MZ_ALLOC(e.r_obs, (size_t)ring_len * B * D * sizeof(float)); }
     MZ_ALLOC(e.r_action, (size_t)ring_len * B * sizeof(int));
     MZ_ALLOC(e.r_reward, (size_t)ring_len * B * sizeof(float));
     MZ_ALLOC(e.r_pi, (size_t)ring_len * B * A * sizeof(double));
@@ -648,11 +649,27 @@ struct ReplayRing {
 };
 constexpr int STATE_F32 = 0, STATE_I8 = 1, STATE_FRAMES_U8 = 2;
 
+// Compact record ring of host-stepped envs with stacked uint8 image frames (mzplanner.h MZ_RECORD_FRAMES_U8): instead of a float32
+// observation (EnvState::r_obs, not allocated then) the record of move m holds the ONE frame the host uploaded for it, and how many
+// moves of the env's episode came before it.  The window rule gives the observation back: with age = m - first(m), frame block k
+// (0 = newest, k < S) of move m is the frame of record m - min(k, age), action plane k is r_action[m - k - 1] where k < age, else
+// action 0 (StackFrameAndAction after a reset: every slot the reset frame, every action plane 1 / A).  A move reads records back to
+// m - S, so the ring keeps `extra` = S moves more than an open trajectory needs.  Carried in ExtLaunch / EpiLaunch, not in EnvState:
+// the fused search kernels take EnvState by value.
+struct RecRing {
+    unsigned char* frames;  // [ring][B][stride] uploaded frame bytes; null: float32 records
+    int* age;               // [ring][B] m - first(m): the env's step count when move m was searched
+    int stride;             // frame bytes rounded up to 16: every frame starts 16-byte aligned
+    int FE;                 // frame bytes C * H * W
+    int extra;              // moves the ring keeps beyond an open trajectory (S; 0 for float32 records)
+};
+
 struct EpiLaunch {
     EnvState env;
     ReplayRing ring;
     int B;
     long long move_abs;   // absolute index (since mz_selfplay_reset) of the move that has just been recorded
+    RecRing rr;
 };
 
 // z[t], t in [0, T): target value of every step of the open trajectory (compute_n_step_target :632-673 /
@@ -780,8 +797,45 @@ __global__ __launch_bounds__(1024) void k_epi_scan(const EpiLaunch E) {
 //               where enc_err is given (host-stepped envs; the device boards' planes are 0 / 1 by construction).
 //   frames_u8 : pixel byte = rint(v * 255), action byte = rint(v * A) - 1 of the action plane's first element; a lane packs sixteen
 //               bytes into one 128-bit store (rows are multiples of 16 bytes: frame bytes, action bytes, zero padding).
+//   REC       : frames_u8 rows from the compact record ring (RecRing): the row of move m is the S frames the window rule names, then
+//               the S action bytes straight from r_action -- no float on the way.  Frames of a multiple of 16 bytes: a lane copies
+//               sixteen bytes with one 128-bit load and one 128-bit store; other frames, and the chunk with the action bytes and the
+//               padding, byte by byte.
 constexpr int EPS_ITEMS = 256;  // gridDim.y
 __device__ __forceinline__ unsigned epi_pixel_byte(float v) { return (unsigned)(int)rintf(v * 255.0f) & 0xffu; }
+
+__device__ __forceinline__ void epi_row_from_records(const EpiLaunch& E, int e, long long m, unsigned char* row) {
+    const EnvState& V = E.env;
+    const ReplayRing& R = E.ring;
+    const RecRing& Q = E.rr;
+    const int B = E.B, P = R.fP, S = R.fS, FE = Q.FE;
+    const int age = Q.age[(size_t)(m % V.ring_len) * B + e];
+    auto frame = [&](int k) { return Q.frames + ((size_t)((m - (k < age ? k : age)) % V.ring_len) * B + e) * Q.stride; };
+    for (int q0 = (blockIdx.x * 256 + threadIdx.x) * 16; q0 < R.row_bytes; q0 += gridDim.x * 4096) {
+        if (q0 + 16 <= P && (FE & 15) == 0) {  // sixteen bytes of one frame
+            const int k = q0 / FE;
+            *reinterpret_cast<uint4*>(row + q0) = *reinterpret_cast<const uint4*>(frame(k) + (q0 - k * FE));
+        } else {
+            unsigned w[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const int q = q0 + j;
+                unsigned b = 0;
+                if (q < P) {
+                    const int k = q / FE;
+                    b = frame(k)[q - k * FE];
+                } else if (q < P + S) {
+                    const int k = q - P;
+                    if (k < age) b = (unsigned)V.r_action[(size_t)((m - k - 1) % V.ring_len) * B + e] & 0xffu;
+                }
+                w[j >> 2] |= b << (8 * (j & 3));
+            }
+            *reinterpret_cast<uint4*>(row + q0) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+}
+
+template <bool REC>
 __global__ __launch_bounds__(256) void k_epi_states(const EpiLaunch E) {
     const EnvState& V = E.env;
     const ReplayRing& R = E.ring;
@@ -798,8 +852,12 @@ __global__ __launch_bounds__(256) void k_epi_states(const EpiLaunch E) {
             else hi = mid - 1;
         }
         const int t = (int)(g - R.off[e]);
-        const float* src = V.r_obs + ((size_t)((V.ep_start[e] + t) % V.ring_len) * B + e) * D;
         const size_t row0 = (size_t)((first + g) % R.capacity) * R.row_bytes;  // byte offset of the item's row
+        if constexpr (REC) {
+            epi_row_from_records(E, e, V.ep_start[e] + t, ring + row0);
+            continue;
+        }
+        const float* src = V.r_obs + ((size_t)((V.ep_start[e] + t) % V.ring_len) * B + e) * D;
         if (R.state_format == STATE_I8) {
             bool bad = false;
             for (size_t w = (row0 & ~(size_t)3) + (size_t)(blockIdx.x * 256 + threadIdx.x) * 4; w < row0 + D; w += (size_t)gridDim.x * 1024) {

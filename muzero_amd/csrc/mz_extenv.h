@@ -15,6 +15,9 @@
 // shifts: output plane k (0 = newest) of a frame is history slot head - (k - 1) (k >= 1) or the uploaded frame (k = 0),
 // and the uploaded frame is written to slot head + 1, which no reader of this launch touches.  The head is kept twice,
 // indexed by the move's parity: a launch reads one copy and writes the other, so no workgroup sees another's update.
+// Compact records (ExtLaunch::rr, RecRing in mz_env.h; stacked uint8 image frames): k_ext_ingest<VEC, true> writes the search input only and
+// stores the uploaded frame's bytes as the move's record (C4: 151 MB of float32 records less per move, 4.7 MB of frame bytes more);
+// k_rec_decode rebuilds a recorded move's float32 observations for mz_selfplay_read.
 // uint8 frames: (float)b / 255.0f is IEEE division (no fast-math in muzero_amd/build.py FLAGS; hipcc's default
 // -fhip-fp32-correctly-rounded-divide-sqrt), the float32 value numpy's astype(np.float32) / 255.0 gives.
 #pragma once
@@ -60,6 +63,7 @@ struct ExtLaunch {
     const int* action;
     const double* pi;
     const double* root;
+    RecRing rr;          // compact record ring (rr.frames set): the uploaded frame is the move's record, r_obs does not exist
 };
 
 __device__ __forceinline__ float ext_frame_value(const ExtLaunch& L, const void* base, size_t i) {
@@ -106,13 +110,16 @@ __device__ __forceinline__ void ext_source(const ExtLaunch& L, int j, int& k, in
 
 // One group of VEC consecutive output floats of env e starting at j0 (VEC = 1: any shape; VEC = 4: image frames whose plane size is a
 // multiple of 4, so the group lies in one plane and reads one run of its source frame).
-template <int VEC>
+// REC (compact record ring: stacked uint8 image frames): no float32 record; the group that files the newest frame in the history also
+// stores its bytes to the move's record slot.
+template <int VEC, bool REC>
 __device__ __forceinline__ void ext_ingest_group(const ExtLaunch& L, int e, int j0, bool reset, int a, int h, int hnew) {
     const ExtEnv& X = L.x;
     int k, src;
     ext_source(L, j0, k, src);
     float* o1 = L.obs + (size_t)e * L.OD + j0;
-    float* o2 = L.env.r_obs + ((size_t)L.slot * L.B + e) * L.OD + j0;
+    float* o2 = nullptr;
+    if constexpr (!REC) o2 = L.env.r_obs + ((size_t)L.slot * L.B + e) * L.OD + j0;
     float v[VEC];
     if (src < 0) {  // action plane: (a + 1) / A of the action that led to frame k; 0 for every plane after a reset
         const float f = ext_action_value(reset ? 0 : (k == 0 ? a : X.hist_act[(size_t)e * X.S + ((h - (k - 1)) % X.S + X.S) % X.S]), L.A);
@@ -131,10 +138,14 @@ __device__ __forceinline__ void ext_ingest_group(const ExtLaunch& L, int e, int 
                 for (int q = 0; q < 4; q++) v[q] = (float)((w >> (8 * q)) & 0xffu) / 255.0f;
                 if (file)
                     for (int t = t0; t < t1; t++) *reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(X.hist) + ((size_t)e * X.S + t) * X.FE + src) = w;
+                if constexpr (REC)
+                    if (file) *reinterpret_cast<uint32_t*>(L.rr.frames + ((size_t)L.slot * L.B + e) * L.rr.stride + src) = w;
             } else {
                 v[0] = (float)s[0] / 255.0f;
                 if (file)
                     for (int t = t0; t < t1; t++) static_cast<unsigned char*>(X.hist)[((size_t)e * X.S + t) * X.FE + src] = s[0];
+                if constexpr (REC)
+                    if (file) L.rr.frames[((size_t)L.slot * L.B + e) * L.rr.stride + src] = s[0];
             }
         } else {
             const float* s = static_cast<const float*>(fresh ? X.frames : X.hist) + off;
@@ -153,10 +164,10 @@ __device__ __forceinline__ void ext_ingest_group(const ExtLaunch& L, int e, int 
     if constexpr (VEC == 4) {
         const float4 w = make_float4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<float4*>(o1) = w;
-        *reinterpret_cast<float4*>(o2) = w;
+        if constexpr (!REC) *reinterpret_cast<float4*>(o2) = w;
     } else {
         *o1 = v[0];
-        *o2 = v[0];
+        if constexpr (!REC) *o2 = v[0];
     }
 }
 
@@ -165,21 +176,55 @@ __device__ __forceinline__ void ext_ingest_group(const ExtLaunch& L, int e, int 
 // lane: float32 frames load 16 bytes per lane too, uint8 frames 4).  VEC = 1: one float per thread (vector frames, odd planes).
 constexpr int EXT_ITER = 4;
 
-template <int VEC>
+template <int VEC, bool REC = false>
 __global__ __launch_bounds__(256) void k_ext_ingest(const ExtLaunch L) {
     const ExtEnv& X = L.x;
     const int e = blockIdx.y;
     const size_t prev = (size_t)L.prev_slot * L.B + e;
     const bool reset = L.first || L.env.r_done[prev] != 0;
     const int a = reset ? 0 : L.env.r_action[prev];
-    if (blockIdx.x == 0 && threadIdx.x == 0) ext_ingest_env(L, e, reset, a);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if constexpr (REC) L.rr.age[(size_t)L.slot * L.B + e] = reset ? 0 : L.env.steps[e];  // (before ext_ingest_env: same thread, no race)
+        ext_ingest_env(L, e, reset, a);
+    }
     const int h = X.S > 0 && !reset ? X.head[(size_t)L.parity * L.B + e] : 0;
     const int hnew = reset || X.S == 0 ? 0 : (h + 1) % X.S;
     constexpr int iters = VEC == 4 ? EXT_ITER : 1;
 #pragma unroll
     for (int it = 0; it < iters; it++) {
         const int j0 = ((blockIdx.x * iters + it) * blockDim.x + threadIdx.x) * VEC;
-        if (j0 < L.OD) ext_ingest_group<VEC>(L, e, j0, reset, a, h, hnew);
+        if (j0 < L.OD) ext_ingest_group<VEC, REC>(L, e, j0, reset, a, h, hnew);
+    }
+}
+
+// mz_selfplay_read on a compact record ring: the float32 observations [B][OD] of the move in slot L.slot, rebuilt by the window rule
+// (RecRing, mz_env.h) into L.obs -- k_ext_ingest's geometry (ext_source) and values (ext_frame_value, ext_action_value), so what a
+// reader gets is what the search saw.  Grid and VEC as k_ext_ingest: VEC = 4 stores 16 bytes per lane.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_rec_decode(const ExtLaunch L) {
+    const RecRing& Q = L.rr;
+    const int e = blockIdx.y, R = L.env.ring_len;
+    const int age = Q.age[(size_t)L.slot * L.B + e];
+    constexpr int iters = VEC == 4 ? EXT_ITER : 1;
+#pragma unroll
+    for (int it = 0; it < iters; it++) {
+        const int j0 = ((blockIdx.x * iters + it) * blockDim.x + threadIdx.x) * VEC;
+        if (j0 >= L.OD) continue;
+        int k, src;
+        ext_source(L, j0, k, src);
+        float v[VEC];
+        if (src < 0) {
+            const float f = ext_action_value(k < age ? L.env.r_action[(size_t)((L.slot + R - k - 1) % R) * L.B + e] : 0, L.A);
+#pragma unroll
+            for (int q = 0; q < VEC; q++) v[q] = f;
+        } else {
+            const unsigned char* s = Q.frames + ((size_t)((L.slot + R - (k < age ? k : age)) % R) * L.B + e) * Q.stride;
+#pragma unroll
+            for (int q = 0; q < VEC; q++) v[q] = ext_frame_value(L, s, (size_t)src + q);
+        }
+        float* o = L.obs + (size_t)e * L.OD + j0;
+        if constexpr (VEC == 4) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+        else *o = v[0];
     }
 }
 
@@ -219,7 +264,8 @@ __global__ void k_ext_commit(const ExtLaunch L) {
         atomicAdd(&L.env.counters[1], (unsigned long long)L.B * (unsigned long long)L.sims);
     }
     // the epilogue reads positions ep_start .. move_abs of the env's open trajectory from the record ring: all of them must still be there
-    if (L.check && L.move_abs + 1 - L.env.ep_start[e] > (long long)L.env.ring_len) atomicMin(L.x.err, e);
+    // (compact records: and the rr.extra = S moves before ep_start that the first position's window reaches back to)
+    if (L.check && L.move_abs + 1 - L.env.ep_start[e] > (long long)(L.env.ring_len - L.rr.extra)) atomicMin(L.x.err, e);
 }
 
 }  // namespace mz

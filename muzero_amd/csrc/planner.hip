@@ -210,6 +210,9 @@ struct mz_planner {
     unsigned char *h_ext_mask = nullptr, *h_ext_done = nullptr;
     int *h_ext_cur = nullptr, *h_ext_opp = nullptr, *h_ext_action = nullptr, *h_ext_err = nullptr;
     float* h_ext_reward = nullptr;
+    RecRing rr{};                  // compact record ring (MZ_RECORD_FRAMES_U8; rr.frames null: float32 records in env.r_obs)
+    int rec_S = 0;                 // its stack_history
+    float* d_rec_stage = nullptr;  // [B][obs] one move of decoded observations (mz_selfplay_read, allocated by the first read)
 
     // arena (mz_arena.h): evaluation games in lock-step on this handle's env state
     ArenaState arena{};
@@ -1397,9 +1400,22 @@ extern "C" int mz_planner_search_scripted(mz_planner* p, int32_t batch, const fl
 // env's open trajectory -- a whole board game, or the acc + unroll + td window (pipeline.py:118-121), but never longer than an episode can
 // get when its step limit is known (max_steps > 0): the classic configs set acc_seq_length = 9999 ("never flush mid-episode",
 // config.py:198), and 10 014 slots x 4096 envs of CartPole records would be ~5 GB.
-static void ring_start(mz_planner* p, int max_steps) {
+// Compact records (mz_selfplay_reset_external, MZ_RECORD_FRAMES_U8): `obs_bytes` is one env's record of a move (its padded frame) and the
+// ring keeps `extra` = S moves more, which the window of the oldest move reaches back to (RecRing, mz_env.h).  The compact ring is
+// host-stepped env state: ext_free is the one place that calls rec_free, and every reset of another mode starts with ext_free.
+static void rec_free(mz_planner* p) {
+    if (p->rr.frames) (void)hipFree(p->rr.frames);
+    if (p->rr.age) (void)hipFree(p->rr.age);
+    if (p->d_rec_stage) (void)hipFree(p->d_rec_stage);
+    p->rr = RecRing{};
+    p->rec_S = 0;
+    p->d_rec_stage = nullptr;
+}
+
+static void ring_start(mz_planner* p, int max_steps, size_t obs_bytes = 0, int extra = 0) {
     const mz_config& c = p->cfg;
-    p->ring_len = (size_t)c.num_envs * obs_dim(c) * sizeof(float) * 64 > ((size_t)4 << 30) ? 16 : 64;
+    if (obs_bytes == 0) obs_bytes = (size_t)obs_dim(c) * sizeof(float);
+    p->ring_len = (size_t)c.num_envs * obs_bytes * 64 > ((size_t)4 << 30) ? 16 : 64;
     if (p->has_replay) {
         const int window = p->replay.acc + p->replay.K + p->replay.td;
         int need = c.is_board_game ? c.num_actions + 1 : window;
@@ -1409,6 +1425,7 @@ static void ring_start(mz_planner* p, int max_steps) {
         }
         if (need > p->ring_len) p->ring_len = (need + 7) & ~7;
     }
+    p->ring_len += extra;
     p->selfplay_moves = 0;
     p->ring_pos = 0;
     p->ring_count = 0;
@@ -1418,11 +1435,14 @@ static void ring_start(mz_planner* p, int max_steps) {
 static int ring_finish_move(mz_planner* p) {
     if (p->has_replay) {
         EpiLaunch E{};
-        E.env = p->env; E.ring = p->replay; E.B = p->cfg.num_envs; E.move_abs = p->selfplay_moves;
+        E.env = p->env; E.ring = p->replay; E.B = p->cfg.num_envs; E.move_abs = p->selfplay_moves; E.rr = p->rr;
         hipLaunchKernelGGL(k_epi_scan, dim3(1), dim3(1024), 0, p->stream, E);
         if (E.ring.state_format != STATE_F32) {  // compact states: before k_epilogue moves ep_start
             const int per = E.ring.state_format == STATE_I8 ? 1024 : 4096, chunks = (E.ring.row_bytes + 3 + per - 1) / per;
-            hipLaunchKernelGGL(k_epi_states, dim3(chunks < 64 ? chunks : 64, EPS_ITEMS), dim3(256), 0, p->stream, E);
+            if (p->rr.frames)  // (compact records: the reset admitted them with frames_u8 states only)
+                hipLaunchKernelGGL(k_epi_states<true>, dim3(chunks < 64 ? chunks : 64, EPS_ITEMS), dim3(256), 0, p->stream, E);
+            else
+                hipLaunchKernelGGL(k_epi_states<false>, dim3(chunks < 64 ? chunks : 64, EPS_ITEMS), dim3(256), 0, p->stream, E);
         }
         hipLaunchKernelGGL(k_epilogue, dim3(p->cfg.num_envs), dim3(64), (size_t)p->ring_len * sizeof(double), p->stream, E);
         hipLaunchKernelGGL(k_epi_publish, dim3(1), dim3(1), 0, p->stream, p->replay);
@@ -1460,6 +1480,7 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         p->replay.row_bytes = obs_dim(c);
         p->replay.enc_err = nullptr;
     }
+    ext_free(p);  // (leaves host-stepped self-play: its buffers and a compact record ring end here)
     p->env_kind = env_kind;
     p->arena_open = false;
     // gym's TimeLimit ends CartPole after 500 steps, the synthetic frames env after 1000; a board game's ring holds the whole game
@@ -1526,6 +1547,7 @@ static void ext_free(mz_planner* p) {
     for (void* b : hbufs)
         if (b) (void)hipHostFree(b);
     p->ext = ExtEnv{};
+    rec_free(p);
     p->h_ext_frames = nullptr; p->h_ext_mask = p->h_ext_done = nullptr;
     p->h_ext_cur = p->h_ext_opp = p->h_ext_action = p->h_ext_err = nullptr;
     p->h_ext_reward = nullptr;
@@ -1538,7 +1560,7 @@ static ExtLaunch ext_launch(mz_planner* p, double temperature) {
     L.slot = p->ring_pos; L.prev_slot = (p->ring_pos + p->ring_len - 1) % p->ring_len; L.first = p->selfplay_moves == 0;
     L.parity = (int)(p->selfplay_moves & 1); L.sims = c.num_simulations; L.check = p->has_replay ? 1 : 0; L.move_abs = p->selfplay_moves;
     L.temperature = temperature; L.obs = p->d_obs; L.cur = p->d_cur; L.temp_out = p->d_temp;
-    L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root;
+    L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root; L.rr = p->rr;
     return L;
 }
 
@@ -1563,13 +1585,41 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
             return fail(MZ_E_INVALID, "mz_replay_ring.state_format MZ_STATE_FRAMES_U8 needs stack_history > 0, is_obs_image and frame_u8 (float frames are not bytes)");
         if (c.num_actions > 256) return fail(MZ_E_INVALID, "mz_replay_ring.state_format MZ_STATE_FRAMES_U8 holds an action in one byte: num_actions > 256");
     }
+    if (x->record_format != MZ_RECORD_F32 && x->record_format != MZ_RECORD_FRAMES_U8)
+        return fail(MZ_E_INVALID, "mz_external_env.record_format must be MZ_RECORD_F32 or MZ_RECORD_FRAMES_U8");
+    const bool rec = x->record_format == MZ_RECORD_FRAMES_U8;
+    if (rec) {
+        if (S == 0 || !x->is_obs_image || !x->frame_u8)
+            return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8 needs stack_history > 0, is_obs_image and frame_u8 (a record is one uint8 frame)");
+        if (c.num_actions > 256) return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8 rebuilds one-byte actions: num_actions > 256");
+        if (p->has_replay && fmt != STATE_FRAMES_U8)
+            return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8 feeds a replay of mz_replay_ring.state_format MZ_STATE_FRAMES_U8 only");
+    }
     ext_free(p);
     p->arena_open = false;
     p->env_kind = MZ_ENV_EXTERNAL;
     p->ext_pending = p->ext_broken = false;
-    ring_start(p, x->max_episode_steps);
-    hipError_t e = env_alloc(p->env, ENV_EXTERNAL, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, 3, 3);
+    const size_t rec_stride = ((size_t)FE + 15) / 16 * 16;
+    if (rec) ring_start(p, x->max_episode_steps, rec_stride, S);
+    else ring_start(p, x->max_episode_steps);
+    hipError_t e = env_alloc(p->env, ENV_EXTERNAL, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, 3, 3, !rec);
     if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    if (rec) {
+        RecRing& Q = p->rr;
+        const size_t slots = (size_t)p->ring_len * c.num_envs;
+        Q.stride = (int)rec_stride; Q.FE = (int)FE; Q.extra = S;
+        p->rec_S = S;
+        hipError_t r = hipMalloc(reinterpret_cast<void**>(&Q.frames), slots * rec_stride);
+        if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void**>(&Q.age), slots * sizeof(int));
+        if (r == hipSuccess) r = hipMemsetAsync(Q.frames, 0, slots * rec_stride, p->stream);
+        if (r == hipSuccess) r = hipMemsetAsync(Q.age, 0, slots * sizeof(int), p->stream);
+        if (r != hipSuccess) {  // no half-built ring: the handle is left without an env, as before its first reset
+            (void)hipGetLastError();
+            ext_free(p);
+            p->env_kind = MZ_ENV_NONE;
+            return fail(MZ_E_HIP, std::string("compact record ring: ") + hipGetErrorString(r));
+        }
+    }
     ExtEnv& X = p->ext;
     X.S = S; X.image = x->is_obs_image ? 1 : 0; X.C = x->frame_c; X.HW = x->frame_h * x->frame_w; X.FE = (int)FE; X.u8 = x->frame_u8 ? 1 : 0;
     X.temp_steps = x->temp_switch_steps > 0 ? x->temp_switch_steps : (c.num_actions <= 10 ? 6 : 30);
@@ -1631,10 +1681,15 @@ extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, con
     HIPCHK(hipMemcpyAsync(p->d_opp, p->h_ext_opp, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
     const ExtLaunch L = ext_launch(p, temperature);
     const int OD = p->ext_od;
-    if ((p->ext.S > 0 && p->ext.image && p->ext.HW % 4 == 0) || (p->ext.S == 0 && OD % 4 == 0))  // (four floats of one plane / run per group)
-        hipLaunchKernelGGL(k_ext_ingest<4>, dim3((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), c.num_envs), dim3(256), 0, p->stream, L);
+    const bool vec4 = (p->ext.S > 0 && p->ext.image && p->ext.HW % 4 == 0) || (p->ext.S == 0 && OD % 4 == 0);  // (four floats of one plane / run per group)
+    const dim3 grid4((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), c.num_envs), grid1((OD + 63) / 64, c.num_envs);
+    if (p->rr.frames) {  // compact records: the same pass without the float32 record
+        if (vec4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_ingest<4, true>), grid4, dim3(256), 0, p->stream, L);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_ingest<1, true>), grid1, dim3(64), 0, p->stream, L);
+    } else if (vec4)
+        hipLaunchKernelGGL(k_ext_ingest<4>, grid4, dim3(256), 0, p->stream, L);
     else
-        hipLaunchKernelGGL(k_ext_ingest<1>, dim3((OD + 63) / 64, c.num_envs), dim3(64), 0, p->stream, L);
+        hipLaunchKernelGGL(k_ext_ingest<1>, grid1, dim3(64), 0, p->stream, L);
     HIPCHK(hipGetLastError());
     int rc = launch_search(p, c.num_envs, 0, true, false, false);  // (move_counter keys the Philox draws as in mz_selfplay_step)
     if (rc) return rc;
@@ -1675,7 +1730,7 @@ extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward,
         HIPCHK(hipStreamSynchronize(p->stream));
         if (*p->h_ext_err != INT_MAX) {
             p->ext_broken = true;
-            return fail(MZ_E_INVALID, "env " + std::to_string(*p->h_ext_err) + ": open trajectory of more than " + std::to_string(p->ring_len) +
+            return fail(MZ_E_INVALID, "env " + std::to_string(*p->h_ext_err) + ": open trajectory of more than " + std::to_string(p->ring_len - p->rr.extra) +
                                           " moves outgrew the record ring (raise mz_external_env.max_episode_steps); no items written, reset next");
         }
     }
@@ -1750,6 +1805,28 @@ extern "C" int mz_selfplay_read(mz_planner* p, int32_t n_moves, float* h_obs, in
     // copies per call, not 7 per move
     const int first = ((p->ring_pos - n_moves) % p->ring_len + p->ring_len) % p->ring_len;
     const int n1 = n_moves < p->ring_len - first ? n_moves : p->ring_len - first;  // moves before the ring wraps
+    if (h_obs && p->rr.frames) {
+        // compact records: the oldest requested move's window reaches back S more moves (fewer at the start of the run), and an act
+        // that waits for its commit has already written its frame over the oldest slot of a full ring
+        const long long before = p->selfplay_moves - n_moves;
+        const int back = before < p->rec_S ? (int)before : p->rec_S;
+        const int held = p->ring_count - (p->ext_pending && p->ring_count == p->ring_len ? 1 : 0);
+        if (n_moves + back > held)
+            return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8: the record ring no longer holds the " + std::to_string(back) +
+                                          " moves before the oldest requested one that its observation is rebuilt from (read fewer moves, or without h_obs)");
+        if (!p->d_rec_stage) HIPCHK(hipMalloc(reinterpret_cast<void**>(&p->d_rec_stage), B * D * sizeof(float)));
+        ExtLaunch L = ext_launch(p, 0.0);
+        L.obs = p->d_rec_stage;
+        const int OD = p->ext_od;
+        for (int i = 0; i < n_moves; i++) {  // move by move through the staging buffer, in stream order
+            L.slot = (first + i) % p->ring_len;
+            if (p->ext.HW % 4 == 0) hipLaunchKernelGGL(k_rec_decode<4>, dim3((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), (unsigned)B), dim3(256), 0, p->stream, L);
+            else hipLaunchKernelGGL(k_rec_decode<1>, dim3((OD + 63) / 64, (unsigned)B), dim3(64), 0, p->stream, L);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(h_obs + (size_t)i * B * D, p->d_rec_stage, B * D * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+        }
+        h_obs = nullptr;  // (done; the other fields as ever)
+    }
     for (int part = 0; part < 2; part++) {
         const size_t slot = part == 0 ? (size_t)first : 0, cnt = part == 0 ? (size_t)n1 : (size_t)(n_moves - n1), done_moves = part == 0 ? 0 : (size_t)n1;
         if (cnt == 0) continue;
@@ -1762,6 +1839,19 @@ extern "C" int mz_selfplay_read(mz_planner* p, int32_t n_moves, float* h_obs, in
         if (h_done) HIPCHK(hipMemcpyAsync(h_done + done_moves * B, p->env.r_done + slot * B, cnt * B, hipMemcpyDeviceToHost, p->stream));
     }
     HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_record_info(mz_planner* p, int64_t out[4]) {
+    if (!p || !out) return fail(MZ_E_INVALID, "null argument");
+    if (p->env_kind == MZ_ENV_NONE || p->arena_open) return fail(MZ_E_STATE, "call mz_selfplay_reset first");
+    const int64_t B = p->cfg.num_envs, A = p->cfg.num_actions, D = obs_dim(p->cfg);
+    const bool rec = p->rr.frames != nullptr;
+    out[0] = rec ? MZ_RECORD_FRAMES_U8 : MZ_RECORD_F32;
+    out[1] = p->ring_len;
+    out[2] = rec ? B * p->rr.stride : B * D * (int64_t)sizeof(float);
+    // r_action, r_reward, r_pi, r_root, r_player, r_done (EnvState) and the compact ring's step counts
+    out[3] = out[1] * (out[2] + B * (int64_t)(sizeof(int) + sizeof(float) + A * sizeof(double) + sizeof(double) + sizeof(int) + 1 + (rec ? sizeof(int) : 0)));
     return MZ_OK;
 }
 
@@ -1846,6 +1936,7 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
         HIPCHK(hipEventCreateWithFlags(&p->ev_arena_q, hipEventDisableTiming));
     }
     p->env_kind = env_kind;
+    ext_free(p);  // (the arena keeps its own one-ply float32 record, ArenaState::r_obs: a compact self-play ring ends here)
     p->ring_len = 1; p->ring_pos = 0; p->ring_count = 0;  // no self-play records in this mode (mz_selfplay_read: MZ_E_INVALID)
     p->selfplay_moves = 0;
     hipError_t e = env_alloc(p->env, env_kind, c.num_envs, c.num_actions, obs_dim(c), 1, board_n, num_to_win);

@@ -282,7 +282,8 @@ def board_temperature_switch(config, train_steps: int = 0) -> int:
 
 
 def run_self_play(config, rank, network, device, env, data_queue, train_steps_counter, stop_event, tag: str = None,
-                  moves_per_drain: int = 16, max_moves: Optional[int] = None, device_stack: bool = True, env_threads: int = 1) -> int:
+                  moves_per_drain: int = 16, max_moves: Optional[int] = None, device_stack: bool = True, env_threads: int = 1,
+                  record_format: str = 'f32') -> int:
     """Self-play until `stop_event` is set (pipeline.py:41-167).  `env` names a device environment ('CartPole-v1',
     'TicTacToe', 'Gomoku', or 'Synthetic-Atari': random frames standing in for the absent emulator); `config.num_envs` of
     them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
@@ -298,11 +299,13 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     is reset on the host.  Envs that are `games.StackFrameAndAction` (directly or inside `games.PlayerIdAndActionMaskWrapper`)
     have their stacking done on the device from the newest frame (`device_stack=False`: on the host).  The actor owns the env
     objects while it runs: it may step an inner env of a wrapper, leaving the wrapper's own state stale.  `env_threads` (1 to 16)
-    host threads step the envs."""
+    host threads step the envs.  `record_format` 'frames_u8' (host-stepped envs whose uint8 image frames the device stacks; device envs
+    ignore it): the planner's record ring keeps one uint8 frame per move instead of the float32 observation
+    (`Planner.selfplay_reset_external`); what reaches `data_queue` is the same."""
     kind, target = resolve_self_play_envs(env, int(getattr(config, 'num_envs', 1)))
     if kind == 'host':
         return _run_self_play_host(config, rank, network, device, target, data_queue, train_steps_counter, stop_event, tag, moves_per_drain,
-                                   max_moves, device_stack, env_threads)
+                                   max_moves, device_stack, env_threads, record_format)
     from muzero_amd import planner as pl
 
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU, 'Synthetic-Atari': pl.ENV_SYNTHETIC}
@@ -348,7 +351,7 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
 
 
 def _run_self_play_host(config, rank, network, device, envs, data_queue, train_steps_counter, stop_event, tag, moves_per_drain, max_moves,
-                        device_stack, env_threads) -> int:
+                        device_stack, env_threads, record_format='f32') -> int:
     """run_self_play over host-stepped env objects (see there): the reference's loop body (pipeline.py:83-113) for all envs at once."""
     from muzero_amd import metrics as mzm
     from muzero_amd import planner as pl
@@ -357,6 +360,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
     env_threads = int(env_threads)
     if not 1 <= env_threads <= MAX_ENV_THREADS:
         raise ValueError(f'env_threads must be 1 to {MAX_ENV_THREADS}, got {env_threads}')
+    pl._record_format(record_format)  # (an unknown name: before any GPU work)
     B = len(envs)
     parts = [device_stack_parts(e) for e in envs] if device_stack else [None] * B
     stacked = all(pt is not None for pt in parts)
@@ -379,7 +383,8 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
     max_steps = int(getattr(spec, 'max_episode_steps', None) or getattr(envs[0], 'max_episode_steps', None) or 0)
     board = bool(config.is_board_game)
     p.selfplay_reset_external(stack_history=S, is_obs_image=image, frame_shape=frame_shape, frame_u8=u8, max_episode_steps=max_steps,
-                              temp_switch_steps=board_temperature_switch(config, train_steps_counter.value) if board else 0)
+                              temp_switch_steps=board_temperature_switch(config, train_steps_counter.value) if board else 0,
+                              record_format=record_format)
     asm = EpisodeAssembler(config, B, obs_shape)
     tracker = mzm.ActorMetrics(mzm.run_file(config, f'actor{rank}', tag), B)
     ones = np.ones((B, p.A), np.uint8)

@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     'mz_planner_bind_param_device', 'mz_planner_refresh_params',
     'mz_planner_initial_inference', 'mz_planner_recurrent_inference', 'mz_planner_hidden_size', 'mz_planner_search',
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
+    'mz_selfplay_record_info',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
     'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
@@ -58,7 +59,7 @@ class MzReplayRing(C.Structure):
 
 class MzExternalEnv(C.Structure):
     _fields_ = [('stack_history', C.c_int32), ('is_obs_image', C.c_int32), ('frame_c', C.c_int32), ('frame_h', C.c_int32), ('frame_w', C.c_int32),
-                ('frame_u8', C.c_int32), ('max_episode_steps', C.c_int32), ('temp_switch_steps', C.c_int32)]
+                ('frame_u8', C.c_int32), ('max_episode_steps', C.c_int32), ('temp_switch_steps', C.c_int32), ('record_format', C.c_int32)]
 
 
 _lib = None
@@ -99,6 +100,7 @@ def load_library():
     L.mz_selfplay_step.argtypes = [vp, C.c_double, i32]
     L.mz_selfplay_read.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mz_selfplay_counters.argtypes = [vp, i64p]
+    L.mz_selfplay_record_info.argtypes = [vp, i64p]
     L.mz_selfplay_attach_replay.argtypes = [vp, C.POINTER(MzReplayRing)]
     L.mz_selfplay_reset_external.argtypes = [vp, C.POINTER(MzExternalEnv)]
     L.mz_selfplay_external_act.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp]
@@ -136,6 +138,15 @@ def _conv_precision(v):
     if not isinstance(v, (str, bool)) and v in (0, 1):
         return int(v)
     raise ValueError(f"conv_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
+
+
+RECORD_FORMATS = {'f32': 0, 'frames_u8': 1}  # MZ_RECORD_F32 / MZ_RECORD_FRAMES_U8 (include/mzplanner.h)
+
+
+def _record_format(v):
+    if isinstance(v, str) and v in RECORD_FORMATS:
+        return RECORD_FORMATS[v]
+    raise ValueError(f"record_format must be 'f32' or 'frames_u8', not {v!r}")
 
 
 def make_mz_config(spec, config=None, num_envs=1, max_ties=0, seed=1, **search_overrides):
@@ -412,12 +423,15 @@ class Planner:
 
     # ---- self-play on host-stepped environments (mz_selfplay_reset_external / _act / _commit) ----
     def selfplay_reset_external(self, stack_history=0, is_obs_image=False, frame_shape=None, frame_u8=False, max_episode_steps=0,
-                                temp_switch_steps=0):
+                                temp_switch_steps=0, record_format='f32'):
         """Start self-play on `num_envs` envs stepped by the caller.  `stack_history` 0: `external_act` gets whole observations (float32);
         S > 0: it gets the newest unstacked frame of shape `frame_shape` ([C, H, W] images, [D] vectors) and the device applies
         StackFrameAndAction(S, is_obs_image) (gym_env.py:271-353); `frame_u8`: uint8 frames scaled by 1 / 255 on the device
         (ScaledFloatFrame, gym_env.py:214-224).  `max_episode_steps` bounds the record ring when a replay is attached; `temp_switch_steps`
-        is the board schedule's switch from temperature 1.0 to 0.1 (used when `external_act` gets temperature < 0)."""
+        is the board schedule's switch from temperature 1.0 to 0.1 (used when `external_act` gets temperature < 0).  `record_format`
+        'frames_u8': the record ring keeps one uint8 frame per move instead of the float32 stacked observation (mzplanner.h
+        MZ_RECORD_FRAMES_U8: stacked uint8 image frames only); `selfplay_read` and the attached `frames_u8` replay get the same bytes."""
+        rfmt = _record_format(record_format)
         if frame_shape is None:
             frame_shape = (self.obs_dim,)
         fs = tuple(int(d) for d in frame_shape)
@@ -435,7 +449,7 @@ class Planner:
             raise PlannerError(f'the attached replay\'s frame_spec {tuple(ring.frame_spec)} is not this env\'s (stack_history, C, H, W) = '
                                f'{(int(stack_history), c, h, w)}')
         self._ext_frame = (fs, np.uint8 if frame_u8 else np.float32)
-        x = MzExternalEnv(int(stack_history), int(bool(is_obs_image)), c, h, w, int(bool(frame_u8)), int(max_episode_steps), int(temp_switch_steps))
+        x = MzExternalEnv(int(stack_history), int(bool(is_obs_image)), c, h, w, int(bool(frame_u8)), int(max_episode_steps), int(temp_switch_steps), rfmt)
         _chk(self.lib.mz_selfplay_reset_external(self.h, C.byref(x)))
 
     def external_act(self, frames, mask, cur, opp, temperature):
@@ -564,6 +578,13 @@ class Planner:
         _chk(self.lib.mz_arena_result(self.h, _p(winner), _p(length), _p(ret), totals, C.cast(C.byref(live), C.c_void_p)))
         return dict(winner=winner, length=length, ret=ret, challenger_wins=int(totals[0]), opponent_wins=int(totals[1]), draws=int(totals[2]),
                     finished_plies=int(totals[3]), live=int(live.value))
+
+    def record_info(self):
+        """The record ring as the last reset sized it (mz_selfplay_record_info): dict(format ('f32' / 'frames_u8'), ring_len (moves),
+        bytes_per_move (one move's observation or frame records), bytes (all record arrays))."""
+        c = (C.c_int64 * 4)()
+        _chk(self.lib.mz_selfplay_record_info(self.h, c))
+        return dict(format={v: k for k, v in RECORD_FORMATS.items()}[int(c[0])], ring_len=int(c[1]), bytes_per_move=int(c[2]), bytes=int(c[3]))
 
     def selfplay_counters(self):
         c = (C.c_int64 * 4)()
