@@ -67,6 +67,9 @@ def main():
                     help='hand the weights to the planner through the host (Planner.load_state_dict) instead of packing them on the GPU (Planner.reload): A/B runs')
     ap.add_argument('--conv-precision', choices=['f32', 'bf16x3'], default='f32',
                     help="the planner's conv arithmetic (mz_config.conv_precision): f32 is bit-equal to the oracle, bf16x3 the split-bf16 path; the learner has its own switch, --learner-conv-precision")
+    ap.add_argument('--tower-precision', choices=['f32', 'bf16x3'], default='f32',
+                    help="the planner's fused residual towers (mz_planner_set_tower_precision): bf16x3 runs them on the split-bf16 tower kernel while the "
+                         "rest of the net stays as --conv-precision says; boards up to 9 x 9 (96 points) have a fused tower, larger ones are refused")
     ap.add_argument('--learner-conv-precision', choices=['f32', 'bf16x3'], default='f32',
                     help="the HIP learner's conv arithmetic (mzl_config.conv_precision): bf16x3 runs the towers' forward and data-gradient convs as split-bf16 MFMAs; "
                          "BatchNorm, the heads and Adam stay float32 either way; the weight gradient has its own switch, --learner-wgrad-precision")
@@ -109,7 +112,7 @@ def main():
         opt = torch.optim.Adam(net.parameters(), lr=cfg.lr_init, weight_decay=cfg.weight_decay)
     sched = None if hip is not None else torch.optim.lr_scheduler.MultiStepLR(opt, milestones=cfg.lr_milestones, gamma=cfg.lr_decay_rate)
     replay = PrioritizedReplay(20000, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda', state_format=None if args.replay_state == 'f32' else args.replay_state)
-    p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed, conv_precision=args.conv_precision), 0)
+    p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed, conv_precision=args.conv_precision), 0, tower_precision=args.tower_precision)
     net.eval()
     p.reload(hip.planner_weights() if hip is not None else net.state_dict(), host=args.host_reload)
     if not args.host_assembly:

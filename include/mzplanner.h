@@ -118,6 +118,20 @@ const char* mz_planner_describe(mz_planner* p);
 int mz_planner_create(const mz_config* cfg, int device_id, mz_planner** out);
 int mz_planner_destroy(mz_planner* p);
 
+/* Arithmetic of a conv net's FUSED residual towers (one persistent kernel per tower, activations in LDS).  MZ_TOWER_F32 (0,
+ * default): k_res_tower, float32 MFMA, bit-equal to the oracle.  MZ_TOWER_BF16X3 (1): k_res_tower_bf16x3 -- the split-bf16 arithmetic of
+ * MZ_CONV_BF16X3 in its one summation order, so a tower equals the chain of split per-conv launches bit for bit; NOT bit-equal to the
+ * oracle.  MZ_NET_ATARI: the dynamics and prediction towers at 6 x 6 (32 of a simulation's 33 convs); the representation net, the dynamics
+ * net's first conv, the heads and the normalisation stay float32.  MZ_NET_BOARD: all three towers (a board net with
+ * conv_precision MZ_CONV_BF16X3 takes the fused split towers without this call: the results are those of its per-conv launches).
+ * Legal after mz_planner_create and before the handle's first mz_planner_commit_params / mz_planner_refresh_params; MZ_E_STATE later.
+ * MZ_E_INVALID, the handle unchanged, for any other value, for MZ_NET_MLP, for a net without a fused-tower geometry (num_planes no
+ * multiple of 16 or above 128, a hidden state too large for the LDS) and where MZ_TOWER=0 is set.  mz_arena_reset refuses two planners
+ * that differ in it. */
+#define MZ_TOWER_F32 0
+#define MZ_TOWER_BF16X3 1
+int mz_planner_set_tower_precision(mz_planner* p, int32_t precision);
+
 /* Weights.  `name` is a state_dict key of the reference module (SURVEY 8b lists them; e.g.
  * "dynamics_net.transition_net.0.weight"); data is a host float32 tensor in torch layout; it is copied.
  * Replaces: actor_network.load_state_dict (pipeline.py:266).  Call mz_planner_commit_params after the last tensor:

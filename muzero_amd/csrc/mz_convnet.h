@@ -17,6 +17,7 @@
 #include "mz_pack.h"
 #include "mz_search.h"
 #include "mz_tower.h"
+#include "mz_tower_split.h"
 
 namespace mz {
 
@@ -42,12 +43,16 @@ struct HeadDev {
 
 struct ConvNetDev {
     int kind = 0;  // MZ_NET_BOARD (1) / MZ_NET_ATARI (2)
-    int split = 0; // mz_config.conv_precision == MZ_CONV_BF16X3: every conv also gets its split-bf16 weight copy, no fused towers
+    int split = 0; // mz_config.conv_precision == MZ_CONV_BF16X3: every conv also gets its split-bf16 weight copy
+    int tower_split = 0;  // mz_planner_set_tower_precision(MZ_TOWER_BF16X3): the fused towers' convs (and only those) get a w3 copy and run on k_res_tower_bf16x3
     int in_c = 0, in_h = 0, in_w = 0, A = 0, R = 0, P = 0, Sv = 1, Sr = 1, hh = 0, hw = 0;
     ConvLayerDev rep_conv, rep_conv2;
     std::vector<ResBlockDev> rep_res, dyn_res, pred_res;
     // fused-tower copies (mz_tower.h): the packed weights / biases of a tower's 2 * blocks convs back to back
     const float *tw_rep = nullptr, *tb_rep = nullptr, *tw_dyn = nullptr, *tb_dyn = nullptr, *tw_pred = nullptr, *tb_pred = nullptr;
+    // split fused towers (mz_tower_split.h): per tower a device table of 2 * blocks w3 pointers followed by 2 * blocks bias pointers --
+    // every conv is read through its own w3 / b buffer, no second copy (so nothing here is a packed buffer of its own)
+    const void* const *ts_rep = nullptr, *const *ts_dyn = nullptr, *const *ts_pred = nullptr;
     ConvLayerDev dyn_conv;
     // board games (gcd(h*w, A) == 1, planes % 16 == 0): the dynamics conv split into its real-channel part (dense MFMA kernel)
     // and the action channels' folded weights [cout][A][9] for k_action_sparse; dyn_inv_hw == 0: not available
@@ -204,7 +209,13 @@ inline int build_conv(ConvNetDev& n, const ParamMap& pm, const std::string& conv
     return 0;
 }
 
-inline int build_res(ConvNetDev& n, const ParamMap& pm, const std::string& prefix, int planes, ResBlockDev* r, std::string* err) {
+// want_w3: this block belongs to a tower that mz_planner_set_tower_precision put on the split kernel (build_conv packs w3 where n.split is set)
+inline int build_res(ConvNetDev& n, const ParamMap& pm, const std::string& prefix, int planes, ResBlockDev* r, std::string* err, bool want_w3 = false) {
+    struct SplitScope {
+        int& s; int keep;
+        SplitScope(int& ref, bool on) : s(ref), keep(ref) { if (on) s = 1; }
+        ~SplitScope() { s = keep; }
+    } scope(n.split, want_w3);
     int rc = build_conv(n, pm, prefix + ".conv_block1.0.weight", prefix + ".conv_block1.1", planes, planes, planes, 3, 1, &r->c1, err);
     if (rc) return rc;
     return build_conv(n, pm, prefix + ".conv_block2.0.weight", prefix + ".conv_block2.1", planes, planes, planes, 3, 1, &r->c2, err);
@@ -238,6 +249,27 @@ inline int build_head(ConvNetDev& n, const ParamMap& pm, const std::string& pref
     return 0;
 }
 
+// The pointer table of a split fused tower (ConvNetDev::ts_*): [2 * blocks] w3 streams, then [2 * blocks] biases.  *out stays null where
+// the tower cannot run fused (planes, a layer without w3, MZ_TOWER=0): tower_run then launches conv by conv.
+inline int split_tower_table(ConvNetDev& n, const std::vector<ResBlockDev>& blocks, const void* const** out) {
+    const int P = blocks.empty() ? 0 : blocks[0].c1.cout;
+    if (blocks.empty() || P > 128 || (P & 15) || conv_switches().tower == 0) return 0;
+    std::vector<const void*> t(4 * blocks.size());
+    size_t i = 0;
+    for (const ResBlockDev& r : blocks)
+        for (const ConvLayerDev* c : {&r.c1, &r.c2}) {
+            if (c->cin != P || c->cout != P || c->stride != 1 || !c->w3) return 0;
+            t[i] = c->w3; t[2 * blocks.size() + i] = c->b;
+            i++;
+        }
+    void* d = nullptr;
+    if (hipMalloc(&d, t.size() * sizeof(void*)) != hipSuccess) return -2;
+    n.allocs.push_back(d);
+    if (hipMemcpy(d, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice) != hipSuccess) return -2;
+    *out = static_cast<const void* const*>(d);
+    return 0;
+}
+
 inline void convnet_free(ConvNetDev& n) {
     for (void* p : n.allocs) (void)hipFree(p);
     n.allocs.clear();
@@ -251,12 +283,14 @@ inline void convnet_free(ConvNetDev& n) {
 inline int convnet_build(ConvNetDev& n, const ParamMap& pm, std::string* err) {
     int rc;
     const int P = n.P, R = n.R;
+    n.ts_rep = n.ts_dyn = n.ts_pred = nullptr;
+    const bool tsp = n.tower_split != 0;
     if (n.kind == 1) {  // MuZeroBoardGameNet, network.py:540-574
         n.hh = n.in_h; n.hw = n.in_w;
         if ((rc = build_conv(n, pm, "represent_net.conv_block.0.weight", "represent_net.conv_block.1", n.in_c, n.in_c, P, 3, 1, &n.rep_conv, err))) return rc;
         n.rep_res.resize(R);
         for (int i = 0; i < R; i++)
-            if ((rc = build_res(n, pm, "represent_net.res_blocks." + std::to_string(i), P, &n.rep_res[i], err))) return rc;
+            if ((rc = build_res(n, pm, "represent_net.res_blocks." + std::to_string(i), P, &n.rep_res[i], err, tsp))) return rc;
     } else {  // MuZeroAtariNet, network.py:501-537: conv_1 always has 128 output channels (network.py:324)
         n.hh = 6; n.hw = 6;
         if ((rc = build_conv(n, pm, "represent_net.conv_1.weight", "", n.in_c, n.in_c, 128, 3, 2, &n.rep_conv, err))) return rc;
@@ -311,8 +345,8 @@ inline int convnet_build(ConvNetDev& n, const ParamMap& pm, std::string* err) {
     n.dyn_res.resize(R);
     n.pred_res.resize(R);
     for (int i = 0; i < R; i++) {
-        if ((rc = build_res(n, pm, "dynamics_net.res_blocks." + std::to_string(i), P, &n.dyn_res[i], err))) return rc;
-        if ((rc = build_res(n, pm, "prediction_net.res_blocks." + std::to_string(i), P, &n.pred_res[i], err))) return rc;
+        if ((rc = build_res(n, pm, "dynamics_net.res_blocks." + std::to_string(i), P, &n.dyn_res[i], err, tsp))) return rc;
+        if ((rc = build_res(n, pm, "prediction_net.res_blocks." + std::to_string(i), P, &n.pred_res[i], err, tsp))) return rc;
     }
     if ((rc = build_head(n, pm, "dynamics_net.reward_head", P, 1, hw, n.Sr, &n.reward, err))) return rc;
     if ((rc = build_head(n, pm, "prediction_net.policy_net", P, 2, hw, n.A, &n.policy, err))) return rc;
@@ -336,6 +370,10 @@ inline int convnet_build(ConvNetDev& n, const ParamMap& pm, std::string* err) {
     };
     if (n.kind == 1 && table(n.rep_res, &n.tw_rep, &n.tb_rep)) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
     if (table(n.dyn_res, &n.tw_dyn, &n.tb_dyn) || table(n.pred_res, &n.tw_pred, &n.tb_pred)) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
+    if (n.split || n.tower_split) {  // split fused towers: whether a launch takes them is split_tower_geometry's decision (tower_run)
+        if (n.kind == 1 && split_tower_table(n, n.rep_res, &n.ts_rep)) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
+        if (split_tower_table(n, n.dyn_res, &n.ts_dyn) || split_tower_table(n, n.pred_res, &n.ts_pred)) { *err = "hipMalloc/hipMemcpy failed"; return -2; }
+    }
     return 0;
 }
 
@@ -639,6 +677,41 @@ inline TowerGeom tower_geometry(int B, int P, int h, int w) {
     return best;
 }
 
+// The split fused tower (mz_tower_split.h): the same G / NPT scoring, its own LDS bound -- two buffers of three bf16 term planes,
+// channels padded to 32: 2 * P32 * nposp * 6 bytes within the CU's 160 KB
+inline TowerGeom split_tower_geometry(int B, int P, int h, int w) {
+    TowerGeom best{0, 0, 0, 0};
+    if (P > 128 || (P & 15) || conv_switches().tower == 0) return best;
+    const int hw = h * w;
+    double best_score = -1.0;
+    for (int G = 1; G <= 16 && G <= B; G++) {
+        const int npt = (G * hw + 15) / 16;
+        if (npt > 6) break;
+        const int nposp = npt * 16 + ((G * hw) % 16 == 0 ? 16 : 0);  // at least one padding position (it stays zero: the halo reads)
+        const size_t lds = split_tower_lds_bytes(P, nposp);
+        if (lds > 160 * 1024) break;
+        const long wgs = (B + G - 1) / G;
+        double score = (double)(G * hw) / (16.0 * npt);
+        if (wgs < 256) score *= (double)wgs / 256.0;
+        if (score > best_score + 1e-9) { best_score = score; best = TowerGeom{G, npt, nposp, lds}; }
+    }
+    return best;
+}
+
+inline std::string split_tower_name(const TowerGeom& g) {
+    return "k_res_tower_bf16x3<NPT=" + std::to_string(g.npt) + ">, G=" + std::to_string(g.G);
+}
+
+template <int NPT>
+inline void split_tower_launch_npt(hipStream_t st, const SplitTowerLaunch& L, int wgs, size_t lds) {
+    static bool attr_set = false;  // one planner thread per process configures this instantiation once
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_res_tower_bf16x3<NPT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(k_res_tower_bf16x3<NPT>, dim3(wgs), dim3(512), lds, st, L);
+}
+
 template <int NPT>
 inline void tower_launch_npt(hipStream_t st, const TowerLaunch& L, int wgs, size_t lds) {
     static bool attr_set = false;  // one planner thread per process configures this instantiation once
@@ -652,7 +725,29 @@ inline void tower_launch_npt(hipStream_t st, const TowerLaunch& L, int wgs, size
 // residual tower on x (dense), t1/t2 scratch; returns the buffer holding the result.  Small images take the fused
 // LDS-resident kernel (tables tw / tb: per-conv weight / bias pointers of `blocks`), the rest one k_conv3x3 launch per conv.
 inline float* tower_run(hipStream_t st, const std::vector<ResBlockDev>& blocks, int first, int count, int B, float* x, float* t1, float* t2, int h, int w,
-                        const float* tw = nullptr, const float* tb = nullptr) {
+                        const float* tw = nullptr, const float* tb = nullptr, const void* const* ts = nullptr) {
+    if (count > 0 && ts) {  // split fused tower (ts: split_tower_table of `blocks`); bit-identical to the per-conv split launches below
+        const int Pc = blocks[first].c1.cout;
+        const TowerGeom g = split_tower_geometry(B, Pc, h, w);
+        if (g.npt) {
+            SplitTowerLaunch L{};
+            const size_t nc = 2 * blocks.size();
+            L.in = x; L.out = t1; L.n_convs = 2 * count;
+            L.w3 = reinterpret_cast<const conv_u32x4* const*>(ts) + 2 * first;
+            L.bias = reinterpret_cast<const float* const*>(ts) + nc + 2 * first;
+            L.P = Pc; L.h = h; L.w_img = w; L.G = g.G; L.B = B; L.nposp = g.nposp;
+            const int wgs = (B + g.G - 1) / g.G;
+            switch (g.npt) {
+                case 1: split_tower_launch_npt<1>(st, L, wgs, g.lds); break;
+                case 2: split_tower_launch_npt<2>(st, L, wgs, g.lds); break;
+                case 3: split_tower_launch_npt<3>(st, L, wgs, g.lds); break;
+                case 4: split_tower_launch_npt<4>(st, L, wgs, g.lds); break;
+                case 5: split_tower_launch_npt<5>(st, L, wgs, g.lds); break;
+                default: split_tower_launch_npt<6>(st, L, wgs, g.lds); break;
+            }
+            return t1;
+        }
+    }
     if (count > 0 && tw && tb) {
         const TowerGeom g = tower_geometry(B, blocks[first].c1.cout, h, w);
         if (g.npt) {
@@ -723,7 +818,7 @@ inline void convnet_tail(hipStream_t st, ConvNetDev& n, int B, float* x, float* 
         else if (cpt <= 32) hipLaunchKernelGGL(k_normalize_planes<32>, grid, block, 0, st, x, dst_ptrs, dst_dense, nrm, B, n.P, hw);
         else hipLaunchKernelGGL(k_normalize_planes<64>, grid, block, 0, st, x, dst_ptrs, dst_dense, nrm, B, n.P, hw);
     }
-    float* f = tower_run(st, n.pred_res, 0, n.R, B, nrm, x, t2, n.hh, n.hw, n.tw_pred, n.tb_pred);
+    float* f = tower_run(st, n.pred_res, 0, n.R, B, nrm, x, t2, n.hh, n.hw, n.tw_pred, n.tb_pred, n.ts_pred);
     if (pi) head_run(st, n.policy, B, f, nullptr, hw, 1, nullptr, pi);
     head_run(st, n.value, B, f, nullptr, hw, 0, value, nullptr);
 }
@@ -736,7 +831,7 @@ inline void convnet_initial(hipStream_t st, ConvNetDev& n, int B, const float* o
     float* x;
     conv_run(st, n.rep_conv, B, obs, nullptr, nullptr, 0, h, w, nullptr, a, true);  // board: conv+BN+ReLU (:389); Atari: conv_1+ReLU (:346)
     if (n.kind == 1) {
-        x = tower_run(st, n.rep_res, 0, n.R, B, a, b, c, h, w, n.tw_rep, n.tb_rep);
+        x = tower_run(st, n.rep_res, 0, n.R, B, a, b, c, h, w, n.tw_rep, n.tb_rep, n.ts_rep);
     } else {
         h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1;
         x = tower_run(st, n.rep_res, 0, 2, B, a, b, c, h, w);
@@ -777,7 +872,7 @@ inline void convnet_recurrent(hipStream_t st, ConvNetDev& n, int B, const float*
     } else {
         conv_run(st, n.dyn_conv, B, src_dense, src_ptrs, action, n.A, h, w, nullptr, n.bufA, true, store_base, store_floats);
     }
-    float* x = tower_run(st, n.dyn_res, 0, n.R, B, n.bufA, n.bufB, n.bufC, h, w, n.tw_dyn, n.tb_dyn);
+    float* x = tower_run(st, n.dyn_res, 0, n.R, B, n.bufA, n.bufB, n.bufC, h, w, n.tw_dyn, n.tb_dyn, n.ts_dyn);
     head_run(st, n.reward, B, x, nullptr, hw, 0, reward, nullptr);  // the reward head reads the un-normalised state (:447-448)
     convnet_tail(st, n, B, x, dst_ptrs, dst_dense, pi, value);
 }

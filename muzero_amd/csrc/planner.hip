@@ -223,6 +223,7 @@ struct mz_planner {
 
     // weights bound in device memory (mz_planner_bind_param_device / mz_planner_refresh_params; mz_pack.h)
     struct PackState* pk = nullptr;
+    bool params_touched = false;  // a commit or refresh was called: mz_planner_set_tower_precision is no longer legal
 
     // profiling
     bool profiling = false;
@@ -251,7 +252,29 @@ extern "C" const char* mz_planner_describe(mz_planner* p) {
     if (p->conv && p->cnet.split)  // the build conv_run_split dispatches this net's tower convs to (the same chooser)
         g_describe += std::string(" | conv_precision=bf16x3: ") + split_geometry(p->cnet.hh, p->cnet.hw, p->cnet.P).name + ", one launch per conv";
     else if (p->conv) g_describe += " | conv_precision=f32";
+    if (p->conv && (p->cnet.split || p->cnet.tower_split)) {  // the fused split tower a num_envs-wide launch takes (tower_run's chooser)
+        const TowerGeom g = split_tower_geometry(p->cfg.num_envs, p->cnet.P, p->cnet.hh, p->cnet.hw);
+        g_describe += std::string(p->cnet.tower_split ? " | tower_precision=bf16x3: " : " | tower: ") +
+                      (g.npt ? split_tower_name(g) + ", fused" : std::string("no fused split build (MZ_TOWER=0 or no geometry), one launch per conv"));
+    } else if (p->conv) {
+        g_describe += " | tower_precision=f32";
+    }
     return g_describe.c_str();
+}
+
+// mzplanner.h: the fused towers of a conv net on k_res_tower_bf16x3 (mz_tower_split.h); everything else of the net stays as conv_precision says
+extern "C" int mz_planner_set_tower_precision(mz_planner* p, int32_t precision) {
+    if (!p) return fail(MZ_E_INVALID, "null planner");
+    if (precision != MZ_TOWER_F32 && precision != MZ_TOWER_BF16X3) return fail(MZ_E_INVALID, "tower_precision must be MZ_TOWER_F32 (0) or MZ_TOWER_BF16X3 (1)");
+    if (!p->conv) return fail(MZ_E_INVALID, "tower_precision needs a conv net: MZ_NET_MLP has no residual towers");
+    if (p->params_touched) return fail(MZ_E_STATE, "tower_precision is set after mz_planner_create and before the first mz_planner_commit_params / mz_planner_refresh_params");
+    if (precision == MZ_TOWER_BF16X3) {
+        if (conv_switches().tower == 0) return fail(MZ_E_INVALID, "tower_precision MZ_TOWER_BF16X3 needs the fused towers: MZ_TOWER=0 is set");
+        if (!split_tower_geometry(1, p->cnet.P, p->cnet.hh, p->cnet.hw).npt)
+            return fail(MZ_E_INVALID, "tower_precision MZ_TOWER_BF16X3: this net has no fused-tower geometry (num_planes a multiple of 16 and <= 128, a hidden state of at most 96 pixels that fits the LDS)");
+    }
+    p->cnet.tower_split = precision == MZ_TOWER_BF16X3 ? 1 : 0;
+    return MZ_OK;
 }
 
 static void compute_layout(mz_planner* p) {
@@ -641,6 +664,7 @@ static int packed_k(const MlpNet& n, int l, int g, int q, int s) {
 
 extern "C" int mz_planner_commit_params(mz_planner* p) {
     if (!p) return fail(MZ_E_INVALID, "null planner");
+    p->params_touched = true;
     HIPCHK(hipSetDevice(p->device));
     if (p->conv) {
         HIPCHK(hipStreamSynchronize(p->stream));
@@ -924,6 +948,7 @@ static int pack_build_maps(mz_planner* p) {
 
 extern "C" int mz_planner_refresh_params(mz_planner* p, void* producer_stream) {
     if (!p) return fail(MZ_E_INVALID, "null planner");
+    p->params_touched = true;
     if (!p->pk || p->pk->bound.empty()) return fail(MZ_E_STATE, "no tensor bound: call mz_planner_bind_param_device for every tensor first");
     HIPCHK(hipSetDevice(p->device));
     PackState& k = *p->pk;
@@ -1070,14 +1095,18 @@ extern "C" int mz_debug_conv3x3(mz_planner* p, int32_t batch, int32_t cin_real, 
     if (h_rows) {
         for (int b = 0; b < batch; b++) ptrs.push_back(d_in + (size_t)h_rows[b] * cin_real * hw);
         HIPCHK(s.alloc(reinterpret_cast<void**>(&d_ptrs), (size_t)batch * sizeof(float*)));
+        HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpyAsync(d_ptrs, ptrs.data(), (size_t)batch * sizeof(float*), hipMemcpyHostToDevice, p->stream));
     }
     if (h_action) {
         HIPCHK(s.alloc(reinterpret_cast<void**>(&d_act), (size_t)batch * sizeof(int)));
+        HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpyAsync(d_act, h_action, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, p->stream));
     }
     if (h_residual) {
         HIPCHK(s.alloc(reinterpret_cast<void**>(&d_res), out_floats * sizeof(float)));
+        HIPCHK(hipDeviceSynchronize());  // (alloc's memset runs on the null stream, which the planner's non-blocking stream does not wait for: unsynchronised it can
+                                         // land after the copy below and zero the head of a large residual)
         HIPCHK(hipMemcpyAsync(d_res, h_residual, out_floats * sizeof(float), hipMemcpyHostToDevice, p->stream));
     }
     static thread_local std::string g_build;
@@ -1093,6 +1122,93 @@ extern "C" int mz_debug_conv3x3(mz_planner* p, int32_t batch, int32_t cin_real, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_out, d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+// mz_debug_res_tower: ONE residual tower of n_convs = 2 * blocks convs through the production code -- build_conv per layer (no BatchNorm) in
+// a temporary ConvNetDev in the handle's precision (split where conv_precision or tower_precision is bf16x3), the tower tables, tower_run on
+// the handle's stream.  h_weight [n_convs][P][P][3][3], h_bias [n_convs][P], h_in / h_out [batch][P][h][w].  *build_name: the build that ran,
+// with G and NPT; *tower_ms (may be NULL): the tower's launches between two HIP events on the handle's stream.  Everything lives in allocations of this call: the handle's weights and buffers are not touched.
+extern "C" int mz_debug_res_tower(mz_planner* p, int32_t batch, int32_t planes, int32_t h, int32_t w, int32_t n_convs, const float* h_weight,
+                                  const float* h_bias, const float* h_in, float* h_out, const char** build_name, float* tower_ms) {
+    if (!p || !h_weight || !h_bias || !h_in || !h_out) return fail(MZ_E_INVALID, "null argument to mz_debug_res_tower");
+    if (!p->conv) return fail(MZ_E_INVALID, "mz_debug_res_tower needs a conv net: MZ_NET_MLP has no residual towers");
+    if (batch < 1 || batch > 4096) return fail(MZ_E_INVALID, "mz_debug_res_tower: batch must be in [1, 4096]");
+    if (planes < 1 || planes > 512) return fail(MZ_E_INVALID, "mz_debug_res_tower: planes must be in [1, 512]");
+    if (h < 3 || h > 19 || w < 3 || w > 19) return fail(MZ_E_INVALID, "mz_debug_res_tower: h and w must be in [3, 19]");
+    if (n_convs < 2 || n_convs > 64 || (n_convs & 1)) return fail(MZ_E_INVALID, "mz_debug_res_tower: n_convs must be even and in [2, 64]");
+    HIPCHK(hipSetDevice(p->device));
+    struct Scratch {
+        ConvNetDev n;
+        ~Scratch() {
+            for (void* b : n.allocs) (void)hipFree(b);
+        }
+        hipError_t alloc(void** d, size_t bytes) {
+            hipError_t e = hipMalloc(d, bytes + 256);  // + slack: the f32 kernels read the last pixel quad of a channel as 16 bytes
+            if (e != hipSuccess) return e;
+            n.allocs.push_back(*d);
+            return hipMemset(*d, 0, bytes + 256);
+        }
+    } s;
+    const bool split = p->cnet.split || p->cnet.tower_split;
+    s.n.kind = MZ_NET_BOARD;
+    s.n.split = split ? 1 : 0;
+    s.n.P = planes;
+    std::vector<ResBlockDev> blocks(n_convs / 2);
+    const size_t wn = (size_t)planes * planes * 9;
+    std::string err;
+    for (int i = 0; i < n_convs; i++) {
+        ParamMap pm;
+        pm["w"] = HostTensorRef{h_weight + (size_t)i * wn, {planes, planes, 3, 3}};
+        ConvLayerDev* layer = (i & 1) ? &blocks[i / 2].c2 : &blocks[i / 2].c1;
+        const int rc = build_conv(s.n, pm, "w", "", planes, planes, planes, 3, 1, layer, &err);
+        if (rc) return fail(rc == -2 ? MZ_E_HIP : MZ_E_INVALID, "mz_debug_res_tower: " + err);
+        HIPCHK(hipMemcpy(layer->b, h_bias + (size_t)i * planes, (size_t)planes * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const void* const* ts = nullptr;
+    float *tw = nullptr, *tb = nullptr;
+    if (split) {
+        if (split_tower_table(s.n, blocks, &ts)) return fail(MZ_E_HIP, "mz_debug_res_tower: hipMalloc/hipMemcpy failed");
+    } else if (planes <= 128 && (planes & 15) == 0) {  // the float32 tower's back-to-back tables, as convnet_build lays them out
+        const size_t pw = (size_t)(planes / 16) * (planes / 16) * 9 * 256;
+        HIPCHK(s.alloc(reinterpret_cast<void**>(&tw), n_convs * pw * sizeof(float)));
+        HIPCHK(s.alloc(reinterpret_cast<void**>(&tb), (size_t)n_convs * planes * sizeof(float)));
+        HIPCHK(hipDeviceSynchronize());
+        for (int i = 0; i < n_convs; i++) {
+            const ConvLayerDev& c = (i & 1) ? blocks[i / 2].c2 : blocks[i / 2].c1;
+            HIPCHK(hipMemcpy(tw + i * pw, c.w, pw * sizeof(float), hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(tb + (size_t)i * planes, c.b, (size_t)planes * sizeof(float), hipMemcpyDeviceToDevice));
+        }
+    }
+    const size_t floats = (size_t)batch * planes * h * w;
+    float* d[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++) HIPCHK(s.alloc(reinterpret_cast<void**>(&d[i]), floats * sizeof(float)));
+    HIPCHK(hipDeviceSynchronize());  // (the memsets above run on the null stream)
+    HIPCHK(hipMemcpyAsync(d[0], h_in, floats * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    static thread_local std::string g_build;
+    const TowerGeom gs = ts ? split_tower_geometry(batch, planes, h, w) : TowerGeom{0, 0, 0, 0};
+    const TowerGeom gf = (tw && tb) ? tower_geometry(batch, planes, h, w) : TowerGeom{0, 0, 0, 0};
+    if (gs.npt) g_build = split_tower_name(gs);
+    else if (split) g_build = std::string("per conv: ") + split_geometry(h, w, planes).name;
+    else if (gf.npt) g_build = "k_res_tower<NPT=" + std::to_string(gf.npt) + ">, G=" + std::to_string(gf.G);
+    else g_build = "per conv: k_conv3x3 f32";
+    if (build_name) *build_name = g_build.c_str();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (tower_ms) {
+        HIPCHK(hipEventCreate(&ev[0]));
+        HIPCHK(hipEventCreate(&ev[1]));
+        HIPCHK(hipEventRecord(ev[0], p->stream));
+    }
+    const float* out = tower_run(p->stream, blocks, 0, n_convs / 2, batch, d[0], d[1], d[2], h, w, tw, tb, ts);
+    if (tower_ms) HIPCHK(hipEventRecord(ev[1], p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out, out, floats * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (tower_ms) {
+        HIPCHK(hipEventElapsedTime(tower_ms, ev[0], ev[1]));
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+    }
     return MZ_OK;
 }
 
@@ -1924,6 +2040,7 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
         if (!q || q == p) return fail(MZ_E_INVALID, "MZ_ARENA_PLANNER needs a second planner");
         if (q->device != p->device) return fail(MZ_E_INVALID, "the opponent planner must be on the challenger's device");
         if (!arena_same_config(p->cfg, q->cfg)) return fail(MZ_E_INVALID, "the opponent planner's mz_config must equal the challenger's (apart from the seed)");
+        if (p->conv && p->cnet.tower_split != q->cnet.tower_split) return fail(MZ_E_INVALID, "the opponent planner's tower_precision must equal the challenger's");
         if (!q->committed) return fail(MZ_E_STATE, "the opponent planner's weights are not committed");
     } else if (q) {
         return fail(MZ_E_INVALID, "an opponent planner is given but the opponent kind is not MZ_ARENA_PLANNER");

@@ -280,7 +280,7 @@ def _planner_for(network, config, num_envs, device):
         idx = device.index if getattr(device, 'index', None) is not None else 0
         if getattr(device, 'type', 'cuda') != 'cuda':
             raise _pl.PlannerError(f'uct_search runs on the HIP planner only; got device {device} (no CPU fallback)')
-        pl = _pl.Planner(_pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=getattr(config, 'planner_seed', 1)), idx)
+        pl = _pl.Planner(_pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=getattr(config, 'planner_seed', 1)), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
         entry = [pl, None]
         cache[key] = entry
     if entry[1] != version:

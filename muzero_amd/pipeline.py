@@ -312,7 +312,7 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     name = target
     num_envs = int(getattr(config, 'num_envs', 1))
     idx = device.index if getattr(device, 'index', None) is not None else 0
-    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx)
+    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
     p.reload(network.state_dict())
     from muzero_amd.replay import PrioritizedReplay
 
@@ -373,7 +373,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
     frame_dtype = np.uint8 if u8 else np.float32
 
     idx = device.index if getattr(device, 'index', None) is not None else 0
-    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=B, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx)
+    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=B, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
     p.reload(network.state_dict())
     on_device = isinstance(data_queue, PrioritizedReplay)
     obs_shape = getattr(network, 'input_shape', None)
@@ -560,12 +560,12 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU}
     idx = device.index if getattr(device, 'index', None) is not None else 0
     seed = int(getattr(config, 'planner_seed', 1))
-    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729), idx)
+    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
     q = None
     try:
         p.reload(challenger_network.state_dict())
         if is_net:
-            q = pl.Planner(pl.make_mz_config(opponent.planner_spec(), config, num_envs=num_games, seed=seed + 130003), idx)
+            q = pl.Planner(pl.make_mz_config(opponent.planner_spec(), config, num_envs=num_games, seed=seed + 130003), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
             q.reload(opponent.state_dict())
         p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
         cap = 500 if not two else p.A - 1  # the env's own cap: CartPole's TimeLimit, a board's point count

@@ -20,7 +20,7 @@ ARENA_UNFINISHED, ARENA_WIN_CHALLENGER, ARENA_WIN_OPPONENT, ARENA_DRAW = 0, 1, 2
 
 # every symbol include/mzplanner.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
-    'mz_last_error', 'mz_version', 'mz_planner_describe', 'mz_planner_create', 'mz_planner_destroy', 'mz_planner_set_param', 'mz_planner_commit_params',
+    'mz_last_error', 'mz_version', 'mz_planner_describe', 'mz_planner_create', 'mz_planner_destroy', 'mz_planner_set_tower_precision', 'mz_planner_set_param', 'mz_planner_commit_params',
     'mz_planner_bind_param_device', 'mz_planner_refresh_params',
     'mz_planner_initial_inference', 'mz_planner_recurrent_inference', 'mz_planner_hidden_size', 'mz_planner_search',
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
@@ -83,6 +83,7 @@ def load_library():
     L.mz_planner_describe.argtypes = [C.c_void_p]
     L.mz_planner_create.argtypes = [C.POINTER(MzConfig), C.c_int, C.POINTER(vp)]
     L.mz_planner_destroy.argtypes = [vp]
+    L.mz_planner_set_tower_precision.argtypes = [vp, i32]
     L.mz_planner_set_param.argtypes = [vp, C.c_char_p, vp, i64p, i32]
     L.mz_planner_commit_params.argtypes = [vp]
     L.mz_planner_bind_param_device.argtypes = [vp, C.c_char_p, vp, i64p, i32]
@@ -90,6 +91,7 @@ def load_library():
     L.mz_debug_read_packed.argtypes = [vp, i32, vp, i64p, C.POINTER(C.c_char_p)]
     L.mz_debug_packed_info.argtypes = [vp, i32, i64p]
     L.mz_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, C.POINTER(C.c_char_p)]
+    L.mz_debug_res_tower.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float)]
     L.mz_planner_initial_inference.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mz_planner_recurrent_inference.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.mz_planner_hidden_size.argtypes = [vp]
@@ -138,6 +140,17 @@ def _conv_precision(v):
     if not isinstance(v, (str, bool)) and v in (0, 1):
         return int(v)
     raise ValueError(f"conv_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
+
+
+TOWER_PRECISIONS = {'f32': 0, 'bf16x3': 1}  # MZ_TOWER_F32 / MZ_TOWER_BF16X3 (include/mzplanner.h)
+
+
+def _tower_precision(v):
+    if isinstance(v, str) and v in TOWER_PRECISIONS:
+        return TOWER_PRECISIONS[v]
+    if not isinstance(v, (str, bool)) and v in (0, 1):
+        return int(v)
+    raise ValueError(f"tower_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
 
 
 RECORD_FORMATS = {'f32': 0, 'frames_u8': 1}  # MZ_RECORD_F32 / MZ_RECORD_FRAMES_U8 (include/mzplanner.h)
@@ -215,12 +228,22 @@ def can_bind(state_dict, device_index):
 class Planner:
     """One planner handle on one GPU (mz_planner*)."""
 
-    def __init__(self, mz_config, device_id=0):
+    def __init__(self, mz_config, device_id=0, tower_precision='f32'):
+        """`tower_precision` 'bf16x3': the fused residual towers on the split-bf16 kernel (mz_planner_set_tower_precision)."""
+        tp = _tower_precision(tower_precision)
         self.lib = load_library()
         self.cfg = mz_config
         h = C.c_void_p()
         _chk(self.lib.mz_planner_create(C.byref(mz_config), int(device_id), C.byref(h)))
         self.h = h
+        self.tower_precision = tp
+        if tp:
+            try:
+                self.set_tower_precision(tp)
+            except PlannerError:
+                self.lib.mz_planner_destroy(self.h)
+                self.h = None
+                raise
         self.device_id = int(device_id)
         self.A = mz_config.num_actions
         self.S = mz_config.num_simulations
@@ -244,6 +267,12 @@ class Planner:
             self.close()
         except Exception:
             pass
+
+    def set_tower_precision(self, precision):
+        """mz_planner_set_tower_precision: legal before the first load_state_dict / refresh_weights of the handle."""
+        tp = _tower_precision(precision)
+        _chk(self.lib.mz_planner_set_tower_precision(self.h, tp))
+        self.tower_precision = tp
 
     # ---- weights ----
     def load_state_dict(self, state_dict):
@@ -328,6 +357,23 @@ class Planner:
         _chk(self.lib.mz_debug_conv3x3(self.h, B, cin_real, cin, cout, h, w, _p(weight), _p(bias), _p(x), _p(rows), _p(action), int(num_actions),
                                        _p(residual), int(bool(relu)), _p(out), C.byref(name)))
         return out, name.value.decode()
+
+    def debug_res_tower(self, x, weights, biases, timed=False):
+        """Test hook (mz_debug_res_tower): one residual tower through the planner's own packers and `tower_run`, in this handle's precision
+        (split-bf16 where conv_precision or tower_precision is 'bf16x3').  x [B, P, h, w], weights [n_convs, P, P, 3, 3], biases
+        [n_convs, P], n_convs even.  Returns (out [B, P, h, w] float32, name of the build that ran, with G and NPT); timed=True adds the
+        tower's launches in ms, between two HIP events on the planner's stream (tools/split_tower_bench.py)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        biases = np.ascontiguousarray(biases, dtype=np.float32)
+        B, P, h, w = x.shape
+        n = weights.shape[0]
+        if weights.shape != (n, P, P, 3, 3) or biases.shape != (n, P):
+            raise ValueError('debug_res_tower: mis-shaped argument')
+        out, name = np.empty((B, P, h, w), np.float32), C.c_char_p()
+        ms = C.c_float()
+        _chk(self.lib.mz_debug_res_tower(self.h, B, P, h, w, n, _p(weights), _p(biases), _p(x), _p(out), C.byref(name), C.byref(ms) if timed else None))
+        return (out, name.value.decode(), float(ms.value)) if timed else (out, name.value.decode())
 
     def pack_stats(self):
         """Test / measurement hook: dict(launches, bytes_read, bytes_written) of one refresh."""
