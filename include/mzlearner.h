@@ -32,7 +32,7 @@ extern "C" {
 #define MZL_NET_ATARI 2  /* MuZeroAtariNet (network.py:501-537): the same kernels; the 96 x 96 representation (network.py:312-353) on 12 x 12 / 12 x 16 tiles */
 
 #define MZL_CONV_F32 0     /* the conv nets' 3x3 convs on the f32-input MFMA (default) */
-#define MZL_CONV_BF16X3 1  /* MZL_NET_BOARD only: the towers' forward and data-gradient convs as split-bf16 MFMAs -- every float32 operand the exact sum of
+#define MZL_CONV_BF16X3 1  /* mzl_config.conv_precision: MZL_NET_BOARD only (an Atari net's switches: mzl_set_atari_precision): the towers' forward and data-gradient convs as split-bf16 MFMAs -- every float32 operand the exact sum of
                             * three bf16 values, six products per step accumulated in float32 (muzero_amd/csrc/mz_learn_conv_split.h).  Staging transforms,
                             * saved tensors, masks, BatchNorm, the heads and Adam stay float32, and so does the weight gradient by default (switchable on
                             * its own: mzl_set_wgrad_precision).  Float32-grade, not bit-equal to MZL_CONV_F32. */
@@ -61,7 +61,8 @@ typedef struct {
     int32_t in_channels;          /* planes of the observation (network.py:549 / :508 input_shape[0]) */
     int32_t board_h, board_w;     /* MZL_NET_BOARD: the board, board_h * board_w <= 240; MZL_NET_ATARI: the frame, 96 x 96 (hidden state 6 x 6) */
     int32_t num_res_blocks;       /* residual blocks of each of the three towers (network.py:546) */
-    int32_t conv_precision;       /* MZL_CONV_F32 (0: a zero-initialised config) | MZL_CONV_BF16X3 (MZL_NET_BOARD only; mzl_create refuses it for the other nets) */
+    int32_t conv_precision;       /* MZL_CONV_F32 (0: a zero-initialised config) | MZL_CONV_BF16X3 (MZL_NET_BOARD only; mzl_create refuses it for the other nets:
+                                   * an Atari net is switched per group of layers by mzl_set_atari_precision) */
 } mzl_config;
 
 /* One batch of `Transition`s (replay.py:27-32) addressed inside the replay ring's storages. */
@@ -139,6 +140,15 @@ int mzl_bind_buffers(mz_learner* h, float* d_running, int64_t* d_num_batches);
  * planes do not fit the LDS; the handle then stays as it was.  Independent of mzl_config.conv_precision: all four combinations are valid for
  * MZL_NET_BOARD.  Redoes the weight-gradient geometry mzl_create derived (images per staging round, pitch, steps, LDS). */
 int mzl_set_wgrad_precision(mz_learner* h, int32_t precision);
+
+/* MZL_NET_ATARI only: the arithmetic of the forward convs and data gradients of two groups of layers, MZL_CONV_F32 (default) | MZL_CONV_BF16X3 each,
+ * independent of each other (all four combinations run).  tower_precision: the whole-image towers -- represent_net.res_blocks_3 (12 x 12), dynamics_net's
+ * and prediction_net's towers (6 x 6, all unroll steps).  stage_precision: the tile path's stride-1 convs -- represent_net.res_blocks_1 (48 x 48, 128
+ * channels) and res_blocks_2 (24 x 24).  Float32 whatever the switches: the stride-2 conv_1 / conv_2, every weight gradient, BatchNorm, heads,
+ * normalisation and Adam.  Split operand copies exist, and are repacked by mzl_commit and mzl_apply, for the split layers only.  Legal after mzl_create and
+ * before mzl_bind (MZL_E_STATE later).  MZL_E_INVALID for an unknown value and for MLP and board nets (a board net's switch is mzl_config.conv_precision);
+ * the handle then stays as it was.  Never calling it, or passing MZL_CONV_F32 twice, is the float32 update bit for bit. */
+int mzl_set_atari_precision(mz_learner* h, int32_t tower_precision, int32_t stage_precision);
 
 /* Caller-owned flat device buffers: master weights, gradients, Adam's exp_avg / exp_avg_sq (torch.optim.Adam state), all float32.
  * Replaces: network.parameters() / optimizer.state (pipeline.py:224-230).  The caller keeps them alive while bound. */

@@ -376,6 +376,22 @@ extern "C" int mzl_debug_conv(mz_learner* h, int32_t direction, int32_t batch, i
     return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv: " + err);
 }
 
+// diagnostic (tests; exported, NOT part of include/mzlearner.h): ONE stride-1 conv of the Atari net's tile path through the update's gather, op builders
+// and dispatcher, at the precision of the call (learner_conv.hip mzlc_debug_conv_tile; the argument block is mz_learn_conv_host.h's); host pointers
+extern "C" int mzl_debug_conv_tile(mz_learner* h, mzl_tile_call* call, const char** build_name) {
+    if (!h || !h->conv) return fail(MZL_E_INVALID, "mzl_debug_conv_tile: needs a conv-net learner (MZL_NET_ATARI)");
+    if (!call) return fail(MZL_E_INVALID, "mzl_debug_conv_tile: null argument");
+    std::string err;
+    const int rc = mzlc_debug_conv_tile(h->conv, call, build_name, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv_tile: " + err);
+}
+// diagnostic (tests): the Atari handle's switches as the handle holds them: [0] tower_precision, [1] stage_precision, [2] wgrad_precision
+extern "C" int mzl_debug_precisions(const mz_learner* h, int32_t* out3) {
+    if (!h || !h->conv || !out3) return fail(MZL_E_INVALID, "mzl_debug_precisions: needs a conv-net learner");
+    out3[0] = mzlc_tower_precision(h->conv); out3[1] = mzlc_stage_precision(h->conv); out3[2] = mzlc_wgrad_precision(h->conv);
+    return MZL_OK;
+}
+
 // diagnostic (tests): ONE layer's weight gradient through the conv learner's op builders, geometry chooser and dispatcher (learner_conv.hip
 // mzlc_debug_wgrad; the argument block is mz_learn_conv_host.h's); host pointers
 extern "C" int mzl_debug_wgrad(mz_learner* h, const mzl_wgrad_call* call, const char** build_name) {
@@ -428,6 +444,17 @@ extern "C" int mzl_set_wgrad_precision(mz_learner* h, int32_t precision) {
     if (!h->conv) return fail(MZL_E_INVALID, "wgrad_precision needs net_kind MZL_NET_BOARD: MZL_NET_MLP has no convolutions");
     std::string err;
     const int rc = mzlc_set_wgrad_precision(h->conv, precision, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, err);
+}
+
+extern "C" int mzl_set_atari_precision(mz_learner* h, int32_t tower_precision, int32_t stage_precision) {
+    if (!h) return fail(MZL_E_INVALID, "null learner");
+    for (const int32_t v : {tower_precision, stage_precision})
+        if (v != MZL_CONV_F32 && v != MZL_CONV_BF16X3)
+            return fail(MZL_E_INVALID, "atari precision: tower_precision and stage_precision must be MZL_CONV_F32 (0) or MZL_CONV_BF16X3 (1), not " + std::to_string(v));
+    if (!h->conv) return fail(MZL_E_INVALID, "mzl_set_atari_precision needs net_kind MZL_NET_ATARI: MZL_NET_MLP has no convolutions (a board net's switch is mzl_config.conv_precision)");
+    std::string err;
+    const int rc = mzlc_set_atari_precision(h->conv, tower_precision, stage_precision, err);
     return rc == MZL_OK ? MZL_OK : fail(rc, err);
 }
 

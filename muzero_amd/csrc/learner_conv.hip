@@ -1,6 +1,6 @@
 // learner_conv.hip -- host side of the conv-net learner step (MuZeroBoardGameNet): layer tables, saved-tensor plan, the launch schedule of one update
 // over the kernels of mz_learn_conv.h.  Called by learner.hip for net_kind == MZL_NET_BOARD; same rules as the MLP path: one handle == one GPU,
-// every call only enqueues on the caller's stream, no allocation after create, no CPU fallback.
+// every call only enqueues on the caller's stream, no allocation after create (but mzlc_set_atari_precision's split copies, before mzlc_bind), no CPU fallback.
 //
 // Schedule of mzl_grad (reference: pipeline.py:575-592 unroll, :594-609 loss / priorities; network.py:273-299, 356-498):
 //   forward   representation tower -> normalize -> for t < K: [dynamics tower_t || prediction tower_t] (independent: launched PAIRED, two jobs per
@@ -37,6 +37,8 @@ struct LayerInfo {
     int f_off = 0, d_off = 0, n_cb = 0, co_tiles = 0, n_cb_d = 0, co_tiles_d = 0;
     long long f3_off = 0, d3_off = 0;  // conv_precision bf16x3: the split operand copies (16-byte words of packed3), 32-channel blocks
     int n_cb3 = 0, n_cb3_d = 0;
+    bool split3 = false;  // this layer's forward and data-gradient convs run k_lc_conv_bf16x3 on the split copies: every layer of a conv_precision bf16x3 board
+                          // handle, the layers mzlc_set_atari_precision names on an Atari handle
     BnInfo bn;
 };
 struct TowerInfo {
@@ -65,6 +67,7 @@ enum OpKind { OP_CONV, OP_WGRAD, OP_WREDUCE, OP_BNFWD, OP_BNBWD, OP_APPLY, OP_WG
 struct Op {
     int kind;
     int npt = 15, side15 = 0;  // OP_CONV: which build
+    bool split = false;        // OP_CONV: the split-bf16 build (conv.w is the layer's split copy, conv.n_cb counts 32-channel blocks)
     LcConv conv;
     LcWgrad wg;
     LcWreduce wr;
@@ -208,11 +211,14 @@ struct mzlc_learner {
     int64_t total = 0, nrunning = 0;
     bool wsplit = false;     // mzlc_set_wgrad_precision(MZL_WGRAD_BF16X3): the towers' weight gradients run k_lc_wgrad_bf16x3 (mz_learn_conv_split_wgrad.h), gm's
                              // weight-gradient fields are make_geom_wsplit's
-    bool split = false;      // mzl_config.conv_precision == MZL_CONV_BF16X3: the towers' convs run k_lc_conv_bf16x3 (mz_learn_conv_split.h)
+    bool split = false;      // mzl_config.conv_precision == MZL_CONV_BF16X3 (board nets): EVERY layer is a split layer (LayerInfo::split3) and only the split copies are packed
     bool allow_side = true;  // the 15 x 15 conv builds (MZLC_NO_SIDE=1 at create: the generic ones)
-    u32x4* packed3 = nullptr;  // split: three bf16 fragment streams per (output-channel tile, 32-channel block, tap), both orientations
+    u32x4* packed3 = nullptr;  // the split layers' copies: three bf16 fragment streams per (output-channel tile, 32-channel block, tap), both orientations
     size_t packed3_words = 0;
     LcPackSplitJob* d_pack3 = nullptr;
+    int n_pack3 = 0;           // pack jobs of the split copies: every layer (split), the layers mzlc_set_atari_precision made split, or none
+    bool tower_split = false;  // mzlc_set_atari_precision: res_blocks_3 and the dynamics / prediction towers (whole images) are split layers
+    bool stage_split = false;  //                           res_blocks_1 / res_blocks_2 (the tile path's stride-1 convs) are split layers
     std::string debug_name;  // mzlc_debug_conv: the build it ran
     int dbg_wgrad_remap = 0;                // launch_ops: the last weight-gradient launch's XCD remap and kernel build (mzlc_debug_wgrad's name)
     const char* dbg_wgrad_build = "";
@@ -335,6 +341,7 @@ int add_conv(mzlc_learner* h, const std::string& conv_name, const std::string& b
     L.d_off = (int)h->packed_floats;
     h->packed_floats += (size_t)L.co_tiles_d * L.n_cb_d * 9 * 256;
     L.n_cb3 = cdiv(L.cin, 32); L.n_cb3_d = cdiv(cout, 32);
+    L.split3 = h->split;
     L.f3_off = (long long)h->packed3_words;
     h->packed3_words += (size_t)L.co_tiles * L.n_cb3 * 9 * 192;
     L.d3_off = (long long)h->packed3_words;
@@ -409,7 +416,7 @@ struct Sched {
             c.cin_real = L.cout; c.cin = L.cout; c.n_cb = L.n_cb_d; c.cout = L.cin_d; c.co_tiles = L.co_tiles_d;
             c.w = h->packed + L.d_off;
         }
-        if (h->split) {  // (k_lc_conv_bf16x3: w is the split copy, n_cb counts 32-channel blocks)
+        if (L.split3) {  // (k_lc_conv_bf16x3: w is the split copy, n_cb counts 32-channel blocks)
             c.n_cb = dgrad ? L.n_cb3_d : L.n_cb3;
             c.w = reinterpret_cast<const float*>(h->packed3 + (dgrad ? L.d3_off : L.f3_off));
         }
@@ -417,7 +424,8 @@ struct Sched {
         c.num_actions = h->A;
         return c;
     }
-    Op op_conv(const LcConv& c) const { Op o{}; o.kind = OP_CONV; o.conv = c; o.npt = g.npt; o.side15 = g.side15 ? 1 : 0; return o; }
+    // `split`: the layer's LayerInfo::split3 (conv_base chose the operand copy by it; the dispatcher chooses the kernel by this)
+    Op op_conv(const LcConv& c, bool split) const { Op o{}; o.kind = OP_CONV; o.conv = c; o.npt = g.npt; o.side15 = g.side15 ? 1 : 0; o.split = split; return o; }
     Op op_bnfwd(const LayerInfo& L, float* fcoef, float* save) const {
         Op o{};
         o.kind = OP_BNFWD;
@@ -494,7 +502,7 @@ struct Sched {
             const LayerInfo& L = h->layers[t.layers[0]];
             LcConv c = conv_base(L, false);
             c.in0 = cur; c.in_mode = IN_IDENT; c.action = action; c.out = a.y[0]; c.stat_mode = ST_FWD; c.stat_part = h->stat[lane];
-            ops.push_back(op_conv(c));
+            ops.push_back(op_conv(c, L.split3));
             ops.push_back(op_bnfwd(L, a.fcoef[0], a.save[0]));
             ops.push_back(op_apply(a.y[0], nullptr, a.fcoef[0], a.x[0]));
             cur = a.x[0];
@@ -519,11 +527,11 @@ struct Sched {
                 c.in0 = cur; c.in_mode = IN_IDENT;
             }
             c.out = a.y[l1]; c.stat_mode = ST_FWD; c.stat_part = h->stat[lane];
-            ops.push_back(op_conv(c));
+            ops.push_back(op_conv(c, L1.split3));
             ops.push_back(op_bnfwd(L1, a.fcoef[l1], a.save[l1]));
             LcConv d = conv_base(L2, false);
             d.in0 = a.y[l1]; d.in_mode = IN_BNRELU; d.coef = a.fcoef[l1]; d.out = a.y[l2]; d.stat_mode = ST_FWD; d.stat_part = h->stat[lane];
-            ops.push_back(op_conv(d));
+            ops.push_back(op_conv(d, L2.split3));
             ops.push_back(op_bnfwd(L2, a.fcoef[l2], a.save[l2]));
             if (h->fuse_apply && r + 1 < t.R) {
                 pend_y = a.y[l2]; pend_coef = a.fcoef[l2]; pend_res = cur; pend_out = a.x[xi + r];
@@ -582,7 +590,7 @@ struct Sched {
             LcConv c = conv_base(L2, true);
             c.in0 = Da; c.in1 = a.y[l2]; c.coef = a.bcoef[l2]; c.in_mode = IN_BNBWD; c.out = Db;
             c.mask = a.y[l1]; c.mcoef = a.fcoef[l1]; c.partner = a.y[l1]; c.stat_mode = ST_BWD; c.stat_part = h->stat[lane];
-            ops.push_back(op_conv(c));
+            ops.push_back(op_conv(c, L2.split3));
             ng = groups();
             ops.push_back(op_bnbwd(L1, a.save[l1], a.bcoef[l1], ng, accumulate));
             if (!defer) wgrad_ops(ops, L1, Db, a.y[l1], a.bcoef[l1], xin_blk, IN_IDENT, nullptr, nullptr, accumulate);
@@ -598,7 +606,7 @@ struct Sched {
                     // not reached: the prediction tower never carries a final_skip; kept for clarity
                 }
             }
-            ops.push_back(op_conv(d));
+            ops.push_back(op_conv(d, L1.split3));
             ng = groups();
             float* tmp = Da; Da = Dc; Dc = tmp;
         }
@@ -609,7 +617,7 @@ struct Sched {
             if (final_out) {
                 LcConv c = conv_base(L0, true);
                 c.in0 = Da; c.in1 = a.y[0]; c.coef = a.bcoef[0]; c.in_mode = IN_BNBWD; c.skip = final_skip; c.out = final_out; c.stat_mode = ST_NONE;
-                ops.push_back(op_conv(c));
+                ops.push_back(op_conv(c, L0.split3));
             }
         }
     }
@@ -694,7 +702,7 @@ hipError_t conv_attr() {
 int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
     switch (a->kind) {
         case OP_CONV: {
-            if (b && (b->conv.in_mode != a->conv.in_mode || b->npt != a->npt || b->side15 != a->side15)) {  // (never the case for the zipped towers; kept correct anyway)
+            if (b && (b->conv.in_mode != a->conv.in_mode || b->npt != a->npt || b->side15 != a->side15 || b->split != a->split)) {  // (never the case for the zipped towers; kept correct anyway)
                 launch_ops(h, a, nullptr, st);
                 return launch_ops(h, b, nullptr, st);
             }
@@ -713,9 +721,21 @@ int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
             const dim3 grid(1, ga + gb, z);
             const size_t lds = conv_lds(a->conv.qstride, cp);
             const int mode = a->conv.in_mode;
-            if (h->split) {  // the towers' convs of a board net: whole images, nine taps, the tilings make_geom picks for a board
-                if ((a->conv.tapmask && a->conv.tapmask != 0x1ff) || a->conv.out_plane || a->conv.halo_in) { h->bad_dispatch = true; return MZL_E_INVALID; }
+            if (a->split) {  // a split layer: the towers' whole images (nine taps, the tilings make_geom picks) or the Atari net's stride-1 tile path
+                if (a->conv.tapmask && a->conv.tapmask != 0x1ff) { h->bad_dispatch = true; return MZL_E_INVALID; }
                 const size_t slds = conv_split_lds(a->conv.G, a->conv.h, a->conv.w_img, cp);
+                if (a->conv.halo_in) {  // the inner 12 x 16 / 12 x 12 of a haloed tile, into planes (out_plane) or inner-only tiles: the float32 dispatcher's conditions
+                    if (mode != IN_IDENT || b || a->side15 || (a->npt != 9 && a->npt != 12) || a->conv.G != 1 || a->conv.action) { h->bad_dispatch = true; return MZL_E_INVALID; }
+                    if (a->conv.out_plane && a->npt == 12) hipLaunchKernelGGL((k_lc_conv_bf16x3<12, IN_IDENT, 0, true, true>), grid, dim3(256), slds, st, pj);
+                    else if (a->conv.out_plane) hipLaunchKernelGGL((k_lc_conv_bf16x3<9, IN_IDENT, 0, true, true>), grid, dim3(256), slds, st, pj);
+                    else if (a->npt == 12) hipLaunchKernelGGL((k_lc_conv_bf16x3<12, IN_IDENT, 0, true, false>), grid, dim3(256), slds, st, pj);
+                    else hipLaunchKernelGGL((k_lc_conv_bf16x3<9, IN_IDENT, 0, true, false>), grid, dim3(256), slds, st, pj);
+                } else
+                if (a->conv.out_plane) { h->bad_dispatch = true; return MZL_E_INVALID; }
+                else if (a->npt == 16) {  // a gathered wide tile as a whole 14 x 18 image (identity staging)
+                    if (mode != IN_IDENT) { h->bad_dispatch = true; return MZL_E_INVALID; }
+                    hipLaunchKernelGGL((k_lc_conv_bf16x3<16, IN_IDENT, 0>), grid, dim3(256), slds, st, pj);
+                } else
                 if (a->npt == 15 && a->side15) launch_conv_split<15, 15>(mode, pj, grid, slds, st);
                 else if (a->npt == 15) launch_conv_split<15, 0>(mode, pj, grid, slds, st);
                 else if (a->npt == 13) launch_conv_split<13, 0>(mode, pj, grid, slds, st);
@@ -935,18 +955,20 @@ struct AtariRun {
     // (round 6: halo_in -- the tile WITH its halo is the staged slab, only the inner 12 x 12 / 12 x 16 outputs are computed: 9 / 12 pixel tiles
     // per workgroup instead of 13 / 16, written as inner-only tiles [tiles][C][Ty Tx]; MZLC_NO_HALO_IN=1 at create: the first form)
     bool halo_in() const { return h->halo_in; }
-    void conv_tiles(const LayerInfo& L, bool dgrad, int H, int W, const float* in, float* out) const {
+    void conv_tiles(const LayerInfo& L, bool dgrad, int H, int W, const float* in, float* out) const { run(conv_tiles_op(L, dgrad, H, W, in, out)); }
+    // (the op alone: also built by mzlc_debug_conv_tile, which points it at operand copies of its own)
+    Op conv_tiles_op(const LayerInfo& L, bool dgrad, int H, int W, const float* in, float* out) const {
         const Sched s = tiles(dgrad ? L.cout : L.cin_real, H, W);
         LcConv c = s.conv_base(L, dgrad);
         c.in0 = in; c.in_mode = IN_IDENT; c.out = out; c.stat_mode = ST_NONE;
-        Op o = s.op_conv(c);
+        Op o = s.op_conv(c, L.split3);
         if (halo_in()) {
             const int tw = tile_w(W);
             o.conv.halo_in = 1; o.conv.G = 1; o.conv.h = TILE; o.conv.w_img = tw; o.conv.qstride = (4 * (TILE + 2) * (tw + 2) + 63) & ~63;
             o.npt = (TILE * tw) / 16;  // 9 (12 x 12) or 12 (12 x 16)
             o.side15 = 0;
         }
-        run(o);
+        return o;
     }
     // (round 6: out_plane) the same conv with the scatter folded into its epilogue: the tile's inner outputs go straight to their place in `plane`
     // [B][C][H][W] (+ `skip`, a plane of the same shape), and with `stat_part` the BatchNorm forward partial sums are taken per tile (pivoted, the
@@ -957,19 +979,23 @@ struct AtariRun {
     // layer below leaves the conv directly (before: a gradient plane, then k_lc_entry_plain over it).
     int conv_tiles_plane(const LayerInfo& L, bool dgrad, int H, int W, const float* in, float* plane, const float* skip, float* stat_part,
                          const float* mask = nullptr, const float* partner = nullptr, const float* mcoef = nullptr) const {
+        run(conv_tiles_plane_op(L, dgrad, H, W, in, plane, skip, stat_part, mask, partner, mcoef));
+        return B * ntiles(H, W);
+    }
+    Op conv_tiles_plane_op(const LayerInfo& L, bool dgrad, int H, int W, const float* in, float* plane, const float* skip, float* stat_part, const float* mask,
+                           const float* partner, const float* mcoef) const {
         const Sched s = tiles(dgrad ? L.cout : L.cin_real, H, W);
         LcConv c = s.conv_base(L, dgrad);
         c.in0 = in; c.in_mode = IN_IDENT; c.out = plane; c.skip = skip;
         c.stat_mode = stat_part ? (mask ? ST_BWD : ST_FWD) : ST_NONE; c.stat_part = stat_part;
         c.mask = mask; c.mcoef = mcoef; c.partner = partner;  // (mcoef: the mask is where a mask + b > 0 -- a ReLU that was never materialised)
-        Op o = s.op_conv(c);
+        Op o = s.op_conv(c, L.split3);
         const int tw = tile_w(W);
         o.conv.halo_in = 1; o.conv.G = 1; o.conv.h = TILE; o.conv.w_img = tw; o.conv.qstride = (4 * (TILE + 2) * (tw + 2) + 63) & ~63;
         o.conv.out_plane = 1; o.conv.pl_h = H; o.conv.pl_w = W; o.conv.pl_nty = H / TILE; o.conv.pl_ntx = W / tw;
         o.npt = (TILE * tw) / 16;
         o.side15 = 0;
-        run(o);
-        return B * ntiles(H, W);
+        return o;
     }
     // one parity plane's share of a stride-2 conv: the packed copy at `w_off`; accumulate: out += (the earlier planes' sum rides in `skip`)
     void conv_par(int w_off, int cin, int cout, int H, int W, const float* in, float* out, bool accumulate, int tapmask) const {
@@ -981,7 +1007,7 @@ struct AtariRun {
         c.cpad_in = pad16(cin); c.cpad_out = pad16(cout); c.num_actions = h->A;
         c.in0 = in; c.in_mode = IN_IDENT; c.out = out; c.skip = accumulate ? out : nullptr; c.stat_mode = ST_NONE;
         c.tapmask = h->par_compact ? tapmask : 0;
-        run(s.op_conv(c));
+        run(s.op_conv(c, false));  // (the parity planes' tap-set builds are float32 only)
     }
     void bn_fwd(const LayerInfo& L, float* fcoef, float* save, int groups, float count) const {
         const Sched s = plain(L.cout);
@@ -1385,6 +1411,7 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
             j.n_cb = L.n_cb3; j.co_tiles = L.co_tiles; j.n_cb_d = L.n_cb3_d; j.co_tiles_d = L.co_tiles_d;
             jobs.push_back(j);
         }
+        h->n_pack3 = (int)jobs.size();
         ok = ok && dalloc(h, &h->d_pack3, jobs.size()) == hipSuccess;
         if (ok) ok = hipMemcpy(h->d_pack3, jobs.data(), jobs.size() * sizeof(LcPackSplitJob), hipMemcpyHostToDevice) == hipSuccess;
     }
@@ -1646,6 +1673,84 @@ int mzlc_set_wgrad_precision(mzlc_learner* h, int precision, std::string& err) {
 }
 int mzlc_wgrad_precision(const mzlc_learner* h) { return h->wsplit ? MZL_WGRAD_BF16X3 : MZL_WGRAD_F32; }
 
+namespace {
+// the dynamic-LDS limit of the split builds an Atari handle dispatches (towers: whole images at the tilings of gm and g12; tile path: HALO / PLANE builds)
+hipError_t atari_split_attrs() {
+    hipError_t e = conv_split_attr<9, 0>();
+    if (e == hipSuccess) e = conv_split_attr<6, 0>();
+    if (e == hipSuccess) e = conv_split_attr<5, 0>();
+    if (e == hipSuccess) e = conv_split_attr<13, 0>();
+    if (e == hipSuccess) e = conv_split_attr<15, 0>();
+    auto attr = [](const void* f) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
+    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<16, IN_IDENT, 0>));
+    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<12, IN_IDENT, 0, true, false>));
+    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<12, IN_IDENT, 0, true, true>));
+    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<9, IN_IDENT, 0, true, false>));
+    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<9, IN_IDENT, 0, true, true>));
+    return e;
+}
+}  // namespace
+
+// The conv arithmetic of an Atari handle, per group of layers (before mzlc_bind): tower_precision -- res_blocks_3 (12 x 12) and the dynamics / prediction
+// towers (6 x 6), whole images; stage_precision -- res_blocks_1 / res_blocks_2, the tile path's stride-1 convs.  Forward convs and data gradients of
+// the named layers run k_lc_conv_bf16x3 on split operand copies, which exist (and are repacked by mzlc_commit / mzlc_apply) for those layers only; the
+// float32 copies stay for every layer.  Weight gradients, the stride-2 convs, BatchNorm, heads and Adam are untouched.  A refusal leaves the handle as it was.
+int mzlc_set_atari_precision(mzlc_learner* h, int tower_precision, int stage_precision, std::string& err) {
+    for (const int v : {tower_precision, stage_precision})
+        if (v != MZL_CONV_F32 && v != MZL_CONV_BF16X3) {
+            err = "atari precision: tower_precision and stage_precision must be MZL_CONV_F32 (0) or MZL_CONV_BF16X3 (1), not " + std::to_string(v);
+            return MZL_E_INVALID;
+        }
+    if (!h->atari) { err = "mzl_set_atari_precision needs net_kind MZL_NET_ATARI: a board net's switch is mzl_config.conv_precision"; return MZL_E_INVALID; }
+    if (h->params) { err = "mzl_set_atari_precision is legal after mzl_create and before mzl_bind"; return MZL_E_STATE; }
+    const bool ts = tower_precision == MZL_CONV_BF16X3, ss = stage_precision == MZL_CONV_BF16X3;
+    std::vector<char> is_split(h->layers.size(), 0);
+    if (ts) {
+        for (int l : h->t12.layers) is_split[l] = 1;
+        for (int t = 1; t < 3; t++)
+            for (int l : h->tower[t].layers) is_split[l] = 1;
+    }
+    if (ss) {
+        for (int l : h->l_b1) is_split[l] = 1;
+        for (int l : h->l_b2) is_split[l] = 1;
+    }
+    if (ts && (conv_split_lds(h->gm.G, h->h, h->w, pad16(h->P + h->A)) > 160 * 1024 || conv_split_lds(h->g12.G, h->g12.h, h->g12.w, pad16(h->P)) > 160 * 1024)) {
+        err = "tower_precision MZL_CONV_BF16X3: the split conv's LDS slab does not hold this net's planes";
+        return MZL_E_INVALID;
+    }
+    if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+    // the split copies of the split layers, back to back, and their pack jobs
+    std::vector<LcPackSplitJob> jobs;
+    std::vector<long long> f3(h->layers.size(), 0), d3(h->layers.size(), 0);
+    size_t words = 0;
+    for (size_t i = 0; i < h->layers.size(); i++) {
+        const LayerInfo& L = h->layers[i];
+        if (!is_split[i]) continue;
+        f3[i] = (long long)words; words += (size_t)L.co_tiles * L.n_cb3 * 9 * 192;
+        d3[i] = (long long)words; words += (size_t)L.co_tiles_d * L.n_cb3_d * 9 * 192;
+        LcPackSplitJob j{};
+        j.w_off = L.w_off; j.cout = L.cout; j.cin = L.cin; j.cin_d = L.cin_d; j.f_off = f3[i]; j.d_off = d3[i];
+        j.n_cb = L.n_cb3; j.co_tiles = L.co_tiles; j.n_cb_d = L.n_cb3_d; j.co_tiles_d = L.co_tiles_d;
+        jobs.push_back(j);
+    }
+    u32x4* p3 = h->packed3;
+    LcPackSplitJob* dj = h->d_pack3;
+    if (!jobs.empty()) {  // (a repeated call allocates again; the earlier buffers are freed with the handle)
+        hipError_t e = dalloc(h, &p3, words);
+        if (e == hipSuccess) e = dalloc(h, &dj, jobs.size());
+        if (e == hipSuccess) e = hipMemcpy(dj, jobs.data(), jobs.size() * sizeof(LcPackSplitJob), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = atari_split_attrs();
+        if (e == hipSuccess) e = hipDeviceSynchronize();  // (dalloc's fills run on the NULL stream)
+        if (e != hipSuccess) { err = std::string("mzl_set_atari_precision: ") + hipGetErrorString(e); return MZL_E_HIP; }
+    }
+    h->packed3 = p3; h->d_pack3 = dj; h->packed3_words = words; h->n_pack3 = (int)jobs.size();
+    for (size_t i = 0; i < h->layers.size(); i++) { h->layers[i].split3 = is_split[i] != 0; h->layers[i].f3_off = f3[i]; h->layers[i].d3_off = d3[i]; }
+    h->tower_split = ts; h->stage_split = ss;
+    return MZL_OK;
+}
+int mzlc_tower_precision(const mzlc_learner* h) { return h->tower_split ? MZL_CONV_BF16X3 : MZL_CONV_F32; }
+int mzlc_stage_precision(const mzlc_learner* h) { return h->stage_split ? MZL_CONV_BF16X3 : MZL_CONV_F32; }
+
 int mzlc_bind(mzlc_learner* h, float* params, float* grads, float* m, float* v) {
     h->params = params; h->grads = grads; h->m = m; h->v = v;
     h->committed = false;
@@ -1664,8 +1769,10 @@ static void pack_lin(const LchHead* head, const int* lwT_off, int hw, const floa
     }
 }
 static int pack_all(mzlc_learner* h, hipStream_t st) {
-    if (h->split) hipLaunchKernelGGL(k_lc_pack_bf16x3, dim3(64, h->n_pack), dim3(256), 0, st, h->d_pack3, h->params, h->packed3);  // (no conv reads the f32 copies then)
-    else hipLaunchKernelGGL(k_lc_pack, dim3(64, h->n_pack), dim3(256), 0, st, h->d_pack, h->params, h->packed);
+    // conv_precision bf16x3 (board nets): every conv reads the split copies, the f32 ones are not written.  An Atari handle keeps the f32 copies of
+    // all its layers (one job table, written at create) and adds the split copies of the layers mzlc_set_atari_precision named.
+    if (!h->split) hipLaunchKernelGGL(k_lc_pack, dim3(64, h->n_pack), dim3(256), 0, st, h->d_pack, h->params, h->packed);
+    if (h->n_pack3) hipLaunchKernelGGL(k_lc_pack_bf16x3, dim3(64, h->n_pack3), dim3(256), 0, st, h->d_pack3, h->params, h->packed3);
     if (h->n_pack_par) hipLaunchKernelGGL(k_lc_pack_par, dim3(64, h->n_pack_par), dim3(256), 0, st, h->d_pack_par, h->params, h->packed);
     pack_lin(h->head, h->lwT_off, h->hw, h->params, h->lwT, st);
     return hipGetLastError() == hipSuccess ? MZL_OK : MZL_E_HIP;
@@ -1881,7 +1988,7 @@ int mzlc_apply(mzlc_learner* h, double lr, double beta1, double beta2, double ep
 // (b = block: the block's inner post-ReLU tensor -- only with MZLC_KEEP_H1=1; else "s48_y1" / "s48_fcoef1" / .., its raw conv output and BatchNorm
 // coefficients as for "y" / "fcoef" -- and the block's output), "hraw" (the pooled 6 x 6 state before normalisation); "obs": the gathered,
 // decoded observations [B][C0][H][W] of the last batch (tests/test_gpu_replay_codec.py).  *count: floats of the
-// tensor at the last batch where the shape is known here, else the allocation's.
+// tensor at the last batch where the shape is known here, else the allocation's.  "packed3": the split operand copies (32-bit words), where the handle has any.
 int mzlc_debug_tensor(const mzlc_learner* h, const char* what, int a, int b, void** ptr, int64_t* count) {
     const std::string w = what;
     const AppBufs* ap = nullptr;
@@ -1914,6 +2021,7 @@ int mzlc_debug_tensor(const mzlc_learner* h, const char* what, int a, int b, voi
         }
     }
     if (w == "gs") { *ptr = a ? h->GsB : h->GsA; return MZL_OK; }
+    if (w == "packed3" && h->packed3 && h->n_pack3) { *ptr = h->packed3; *count = (int64_t)h->packed3_words * 4; return MZL_OK; }  // the split operand copies, as 32-bit words
     return MZL_E_INVALID;
 }
 
@@ -1983,7 +2091,7 @@ int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int
         hipLaunchKernelGGL(k_lc_pack, dim3(64, 1), dim3(256), 0, st, reinterpret_cast<const LcPackJob*>(d_job), d_w, d_packed);
     }
     Op o{};
-    o.kind = OP_CONV; o.npt = g.npt; o.side15 = g.side15 ? 1 : 0;
+    o.kind = OP_CONV; o.npt = g.npt; o.side15 = g.side15 ? 1 : 0; o.split = h->split;
     LcConv& c = o.conv;
     c.B = batch; c.G = g.G; c.h = bh; c.w_img = bw; c.qstride = g.qstride;
     c.cin_real = c_in_mem; c.cin = k_in; c.n_cb = n_cb; c.cout = c_out; c.co_tiles = co_tiles;
@@ -2012,6 +2120,121 @@ int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int
              g.G, direction == 0 ? "forward" : "dgrad", (double)ms * 1e3);
     h->debug_name = name;
     *build_name = h->debug_name.c_str();
+    return done(MZL_OK, "");
+}
+
+// diagnostic (tests): ONE stride-1 conv of the Atari representation's tile path as the update builds it -- k_lc_tile_gather cuts the host-supplied plane
+// into haloed tiles (AtariRun::gather, the geometry gt / gt16 by the plane's width), AtariRun::conv_tiles_plane_op (route 0: the update's default, the
+// out_plane epilogue) or conv_tiles_op + k_lc_tile_scatter (route 1: inner-only tiles, MZLC_NO_OUT_PLANE's form; route 2: whole haloed tiles,
+// MZLC_NO_HALO_IN's form) build the op from a one-layer table, launch_ops dispatches it -- at the precision of the CALL (the production packers
+// k_lc_pack | k_lc_pack_bf16x3 on the call's weight).  Every pointer of the op is redirected to a temporary buffer of this call (NULL stream); the
+// handle's weights, operand copies, saved tensors and switches are as before when it returns.  *build_name stays valid until the next call:
+//   "<precision> <kernel> NPT= HALO= PLANE= tile=12x<tw> tiles=<per image> groups= dir=forward|dgrad stat=ST_.. us=<HIP-event time of the conv launch>"
+int mzlc_debug_conv_tile(mzlc_learner* h, mzl_tile_call* c, const char** build_name, std::string& err) {
+    if (!h->atari) { err = "Atari nets only (MZL_NET_ATARI): the board nets' convs go through mzl_debug_conv"; return MZL_E_INVALID; }
+    if (!c->weight || !c->in || !c->out) { err = "null argument (weight, in, out)"; return MZL_E_INVALID; }
+    if (c->direction != 0 && c->direction != 1) { err = "direction must be 0 (forward) or 1 (data gradient)"; return MZL_E_INVALID; }
+    if (c->precision != MZL_CONV_F32 && c->precision != MZL_CONV_BF16X3) { err = "precision must be MZL_CONV_F32 (0) or MZL_CONV_BF16X3 (1)"; return MZL_E_INVALID; }
+    if (c->route < 0 || c->route > 2) { err = "route must be 0 (out_plane), 1 (inner tiles + scatter) or 2 (whole haloed tiles + scatter)"; return MZL_E_INVALID; }
+    const int B = c->batch, H = c->H, W = c->W;
+    if (B < 1 || B > 256 || c->cin < 1 || c->cin > 1024 || c->cout < 1 || c->cout > 1024 || H < TILE || W < TILE || H > 96 || W > 96 || H % TILE) {
+        err = "bad shape: batch in [1, 256], cin and cout in [1, 1024], H a multiple of 12, H and W in [12, 96]";
+        return MZL_E_INVALID;
+    }
+    const bool sv_halo = h->halo_in, sv_plane = h->out_plane, sv_bad = h->bad_dispatch;
+    std::vector<void*> tmp;
+    auto A = [&](void** p, size_t bytes, int fill = 0) {
+        if (hipMalloc(p, bytes + 256) != hipSuccess) return false;
+        tmp.push_back(*p);
+        return hipMemset(*p, fill, bytes + 256) == hipSuccess;
+    };
+    auto done = [&](int rc, const char* m) {
+        (void)hipDeviceSynchronize();
+        for (void* p : tmp) (void)hipFree(p);
+        h->halo_in = sv_halo; h->out_plane = sv_plane; h->bad_dispatch = sv_bad;
+        if (rc != MZL_OK) { err = m; (void)hipGetLastError(); }
+        return rc;
+    };
+    auto up = [&](float** d, const float* src, size_t n) { return A((void**)d, n * 4) && hipMemcpy(*d, src, n * 4, hipMemcpyHostToDevice) == hipSuccess; };
+    if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+    h->halo_in = c->route != 2; h->out_plane = c->route == 0; h->bad_dispatch = false;
+    hipStream_t st = nullptr;
+    const AtariRun R{h, B, st};
+    const int tw = R.tile_w(W);
+    if (W % tw) return done(MZL_E_INVALID, "bad shape: W must divide into tiles of 12 columns (or 16: widths that are a multiple of 16 and at least 48)");
+    const bool dg = c->direction == 1, split = c->precision == MZL_CONV_BF16X3;
+    const int c_in = dg ? c->cout : c->cin, c_out = dg ? c->cin : c->cout, cpo = pad16(c_out), nt = R.ntiles(H, W), groups = B * nt;
+    if ((size_t)B * (c_in > c_out ? c_in : c_out) * H * W * sizeof(float) >= ((size_t)1 << 32)) return done(MZL_E_INVALID, "the plane tensor must stay below 4 GiB");
+    if (c->route != 0 && (c->mask || c->partner || c->mcoef || c->part)) return done(MZL_E_INVALID, "mask, mcoef, partner and part belong to route 0: the scatter routes mask and sum in kernels of their own");
+    if (c->mcoef && !c->mask) return done(MZL_E_INVALID, "inconsistent arguments: mcoef without mask");
+    if ((c->mask != nullptr) != (c->partner != nullptr)) return done(MZL_E_INVALID, "inconsistent arguments: mask and partner come together (the update masks where it takes the BatchNorm-backward sums)");
+    if (c->mask && !c->part) return done(MZL_E_INVALID, "inconsistent arguments: a masked conv leaves its ST_BWD partial sums: part");
+    if (c->part && !c->mask && c->skip) return done(MZL_E_INVALID, "inconsistent arguments: the forward statistics (part without mask) are taken from a conv without skip");
+    LayerInfo L;  // a one-layer table: the packed copy of the asked direction at offset 0 of this call's buffer
+    L.cin_real = c->cin; L.cin = c->cin; L.cout = c->cout; L.cin_d = dg ? c->cin : 0;
+    L.n_cb = cdiv(L.cin, 16); L.co_tiles = cdiv(L.cout, 16); L.n_cb_d = cdiv(L.cout, 16); L.co_tiles_d = L.cin_d ? cdiv(L.cin_d, 16) : 0;
+    L.n_cb3 = cdiv(L.cin, 32); L.n_cb3_d = cdiv(L.cout, 32);
+    L.split3 = split;
+    const int co_tiles = dg ? L.co_tiles_d : L.co_tiles, n_cb = split ? (dg ? L.n_cb3_d : L.n_cb3) : (dg ? L.n_cb_d : L.n_cb);
+    const size_t n_w = (size_t)c->cout * c->cin * 9, n_packed = (size_t)co_tiles * n_cb * 9 * (split ? 192 * 4 : 256);
+    const size_t ts2 = (size_t)(TILE + 2) * (tw + 2), n_in = (size_t)B * c_in * H * W, n_out = (size_t)B * c_out * H * W;
+    float *d_w = nullptr, *d_packed = nullptr, *d_in = nullptr, *d_tiles = nullptr, *d_tb = nullptr, *d_out = nullptr, *d_skip = nullptr, *d_mask = nullptr, *d_partner = nullptr,
+          *d_mcoef = nullptr, *d_part = nullptr;
+    void* d_job = nullptr;
+    bool ok = up(&d_w, c->weight, n_w) && A((void**)&d_packed, n_packed * 4) && up(&d_in, c->in, n_in) && A((void**)&d_tiles, (size_t)groups * c_in * ts2 * 4) &&
+              A((void**)&d_out, n_out * 4, 0xff) && A(&d_job, sizeof(LcPackSplitJob) > sizeof(LcPackJob) ? sizeof(LcPackSplitJob) : sizeof(LcPackJob));
+    if (c->route != 0) ok = ok && A((void**)&d_tb, (size_t)groups * c_out * ts2 * 4, 0xff);
+    if (c->skip) ok = ok && up(&d_skip, c->skip, n_out);
+    if (c->mask) ok = ok && up(&d_mask, c->mask, n_out) && up(&d_partner, c->partner, n_out);
+    if (c->mcoef) {
+        std::vector<float> t((size_t)2 * cpo, 0.0f);
+        for (int k = 0; k < 2; k++)
+            for (int ch = 0; ch < c_out; ch++) t[(size_t)k * cpo + ch] = c->mcoef[(size_t)k * c_out + ch];
+        ok = ok && up(&d_mcoef, t.data(), t.size());
+    }
+    if (c->part) ok = ok && A((void**)&d_part, (size_t)groups * cpo * 4 * 4, 0xff);
+    if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+    if (split) {
+        if (atari_split_attrs() != hipSuccess) return done(MZL_E_HIP, "hipFuncSetAttribute failed");
+        LcPackSplitJob j{};
+        j.w_off = 0; j.cout = c->cout; j.cin = c->cin; j.cin_d = L.cin_d;
+        if (!dg) { j.n_cb = n_cb; j.co_tiles = co_tiles; } else { j.n_cb_d = n_cb; j.co_tiles_d = co_tiles; }
+        if (hipMemcpy(d_job, &j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+        hipLaunchKernelGGL(k_lc_pack_bf16x3, dim3(64, 1), dim3(256), 0, st, reinterpret_cast<const LcPackSplitJob*>(d_job), d_w, reinterpret_cast<u32x4*>(d_packed));
+    } else {
+        LcPackJob j{};
+        j.w_off = 0; j.cout = c->cout; j.cin = c->cin; j.cin_d = L.cin_d;
+        if (!dg) { j.n_cb = n_cb; j.co_tiles = co_tiles; } else { j.n_cb_d = n_cb; j.co_tiles_d = co_tiles; }
+        if (hipMemcpy(d_job, &j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+        hipLaunchKernelGGL(k_lc_pack, dim3(64, 1), dim3(256), 0, st, reinterpret_cast<const LcPackJob*>(d_job), d_w, d_packed);
+    }
+    R.gather(d_in, nullptr, nullptr, IN_IDENT, c_in, H, W, H, W, 1, 1, 0, 0, 0, d_tiles);
+    Op o = c->route == 0 ? R.conv_tiles_plane_op(L, dg, H, W, d_tiles, d_out, d_skip, d_part, d_mask, d_partner, d_mcoef) : R.conv_tiles_op(L, dg, H, W, d_tiles, d_tb);
+    o.conv.w = d_packed;
+    if (o.conv.cin_real != c_in || o.conv.cout != c_out || o.conv.cpad_out != cpo || o.conv.n_cb != n_cb) return done(MZL_E_STATE, "internal: conv_base disagrees with the call's channels");
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) return done(MZL_E_HIP, "hipEventCreate failed");
+    (void)hipEventRecord(ev0, st);
+    const int rc = launch_ops(h, &o, nullptr, st);
+    (void)hipEventRecord(ev1, st);
+    const bool bad = h->bad_dispatch;
+    if (rc == 0 && !bad && c->route != 0) R.scatter(d_tb, c_out, H, W, d_out, H, W, 1, 1, 0, 0, d_skip, nullptr, R.halo_in());
+    const bool ran = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    float ms = 0.0f;
+    if (ran) (void)hipEventElapsedTime(&ms, ev0, ev1);
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    if (rc != 0 || bad) return done(MZL_E_INVALID, "no kernel build for this tile conv");
+    if (!ran) return done(MZL_E_HIP, "the tile conv failed to launch or run");
+    if (hipMemcpy(c->out, d_out, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+    if (c->part && hipMemcpy(c->part, d_part, (size_t)groups * cpo * (c->mask ? 2 : 4) * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(MZL_E_HIP, "hipMemcpy failed");
+    c->groups = groups;
+    char name[256];
+    snprintf(name, sizeof(name), "%s %s NPT=%d HALO=%d PLANE=%d tile=12x%d tiles=%d groups=%d dir=%s stat=%s us=%.1f", split ? "bf16x3" : "f32", split ? "k_lc_conv_bf16x3" : "k_lc_conv",
+             o.npt, o.conv.halo_in, o.conv.out_plane, tw, nt, groups, dg ? "dgrad" : "forward", o.conv.stat_mode == ST_FWD ? "ST_FWD" : o.conv.stat_mode == ST_BWD ? "ST_BWD" : "ST_NONE",
+             (double)ms * 1e3);
+    h->debug_name = name;
+    if (build_name) *build_name = h->debug_name.c_str();
     return done(MZL_OK, "");
 }
 
@@ -2319,6 +2542,7 @@ int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build
         L.cin_real = J.cin; L.cin = J.cin; L.cout = J.cout; L.cin_d = conv && J.direction == 1 ? J.cin : 0;
         L.n_cb = cdiv(L.cin, 16); L.co_tiles = cdiv(L.cout, 16); L.n_cb_d = cdiv(L.cout, 16); L.co_tiles_d = L.cin_d ? cdiv(L.cin_d, 16) : 0;
         L.n_cb3 = cdiv(L.cin, 32); L.n_cb3_d = cdiv(L.cout, 32);
+        L.split3 = h->split;
         L.bn.C = C; L.bn.cpad = D.cpo;
         Sched s{h, B, l, nj == 2, g, C};
         bool ok = A((void**)&D.part, n_part * 4, 0xff);
@@ -2358,7 +2582,7 @@ int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build
             k.skip = D.skip; k.mask = D.mask; k.mcoef = D.mcoef; k.partner = J.partner_is_mask ? D.mask : D.partner;
             k.stat_mode = J.stat_mode; k.stat_part = J.stat_mode != ST_NONE ? D.part : nullptr;
             if (k.cin_real != D.c_in || k.cout != D.c_out || k.cpad_out != D.cpo || k.cpad_in != cpi) return done(MZL_E_STATE, "internal: conv_base disagrees with the call's channels");
-            ops[l].push_back(s.op_conv(k));
+            ops[l].push_back(s.op_conv(k, L.split3));
         } else {
             ok = ok && hipMemcpy(D.part, J.part_in, (size_t)D.groups * D.cpo * (J.finalize == 1 ? 4 : 2) * 4, hipMemcpyHostToDevice) == hipSuccess;
         }

@@ -18,6 +18,10 @@ int mzlc_num_buffers(const mzlc_learner* h);
 int mzlc_buffer_info(const mzlc_learner* h, int i, const char** name, int64_t* offset, int32_t* count);
 int64_t mzlc_num_running(const mzlc_learner* h);
 int mzlc_set_wgrad_precision(mzlc_learner* h, int precision, std::string& err);
+int mzlc_wgrad_precision(const mzlc_learner* h);
+int mzlc_set_atari_precision(mzlc_learner* h, int tower_precision, int stage_precision, std::string& err);
+int mzlc_tower_precision(const mzlc_learner* h);
+int mzlc_stage_precision(const mzlc_learner* h);
 int mzlc_bind(mzlc_learner* h, float* params, float* grads, float* m, float* v);
 int mzlc_bind_buffers(mzlc_learner* h, float* running, int64_t* num_batches);
 int mzlc_commit(mzlc_learner* h, void* stream, std::string& err);
@@ -27,6 +31,27 @@ int mzlc_apply(mzlc_learner* h, double lr, double beta1, double beta2, double ep
 int mzlc_debug_tensor(const mzlc_learner* h, const char* what, int a, int b, void** ptr, int64_t* count);
 int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int cin, int cout, int bh, int bw, const float* h_weight, const float* h_in,
                     const int32_t* h_action, int num_actions, float* h_out, const char** build_name, std::string& err);
+
+// diagnostic (tests): ONE stride-1 conv of the Atari net's tile path (mzl_debug_conv_tile; exported, not part of include/mzlearner.h).  Host pointers
+// throughout; null = absent.  direction 0: the forward conv, c_in = cin input and c_out = cout output channels; 1: the data gradient (c_in = cout,
+// c_out = cin).  The plane is cut into 12 x 12 tiles, or 12 x 16 where the handle cuts wide tiles (W a multiple of 16, at least 48).
+struct mzl_tile_call {
+    int32_t direction;
+    int32_t precision;     // MZL_CONV_F32 | MZL_CONV_BF16X3, whatever the handle's switches
+    int32_t route;         // 0: halo_in + out_plane (the update); 1: halo_in, inner-only tiles + k_lc_tile_scatter; 2: whole haloed tiles + k_lc_tile_scatter
+    int32_t batch, cin, cout, H, W;
+    int32_t groups;        // out: the tiles of the call (workgroup rows of the conv; rows of `part`)
+    int32_t pad_;
+    const float* weight;   // [cout][cin][3][3], the LAYER's weight in both directions
+    const float* in;       // [B][c_in][H][W]
+    const float* skip;     // [B][c_out][H][W] or null
+    const float* mask;     // route 0: [B][c_out][H][W] or null; the result is zeroed where mask (mcoef: a mask + b) <= 0 and the ST_BWD sums are taken
+    const float* mcoef;    // [2][c_out] or null
+    const float* partner;  // [B][c_out][H][W]: comes with mask
+    float* out;            // [B][c_out][H][W]; preset to NaN bits, so an unwritten element shows
+    float* part;           // route 0, or null: [groups][pad16(c_out)][4] ST_FWD partials (no mask, no skip) | [groups][pad16(c_out)][2] ST_BWD partials (mask)
+};
+int mzlc_debug_conv_tile(mzlc_learner* h, mzl_tile_call* c, const char** build_name, std::string& err);
 
 // diagnostic (tests): ONE layer's weight gradient (mzl_debug_wgrad; exported, not part of include/mzlearner.h).  Host pointers throughout.
 struct mzl_wgrad_layer {

@@ -1,5 +1,6 @@
-// mz_learn_conv_split.h -- the opt-in split-bf16 3x3 conv of the board-net learner (mzl_config.conv_precision == MZL_CONV_BF16X3) for gfx950:
-// k_lc_conv's job -- the towers' forward convs and data gradients -- on v_mfma_f32_16x16x32_bf16 instead of v_mfma_f32_16x16x4_f32.
+// mz_learn_conv_split.h -- the opt-in split-bf16 3x3 conv of the conv-net learners (board nets: mzl_config.conv_precision == MZL_CONV_BF16X3, every
+// tower; the Atari net: mzl_set_atari_precision, per group of layers) for gfx950: k_lc_conv's job -- forward convs and data gradients -- on
+// v_mfma_f32_16x16x32_bf16 instead of v_mfma_f32_16x16x4_f32.
 //
 // A float32 is exactly the sum of three bf16 values (mz_split3.h), so a float32-grade product is six bf16 products accumulated in float32: hh, hm,
 // mh, hl, lh, mm (the three dropped cross terms are below 2^-24 of the product).  What k_lc_conv_bf16x3 keeps of k_lc_conv, bit for bit:
@@ -16,7 +17,8 @@
 // block, tap), zero-padded to 32 input channels, packed on the GPU by k_lc_pack_bf16x3 (one copy per orientation) and read from L2 one or two steps ahead.
 // LcConv::w points at that copy and LcConv::n_cb counts 32-channel blocks in this path.
 // ONE summation order in every build -- (32-channel block, tap, term hh, hm, mh, hl, lh, mm), channel 32 cb + k in k slot k of a step: the generic
-// and the SIDE build give the same bits.  No TAPMASK, PLANE or halo_in builds: the towers of the board nets need none.
+// and the SIDE build give the same bits, and so do the tile-path builds (HALO, PLANE: the Atari net's 48 x 48 and 24 x 24 stages, mzl_set_atari_precision).
+// No TAPMASK builds: the stride-2 parity planes stay float32.
 #pragma once
 #include "mz_learn_conv.h"
 #include "mz_split3.h"
@@ -28,11 +30,19 @@ typedef __bf16 lc_bf16x8 __attribute__((ext_vector_type(8)));
 // dynamic LDS of k_lc_conv_bf16x3: the slab of G haloed planes + the staging coefficients
 inline size_t conv_split_lds(int G, int h, int w, int cpad_in) { return (size_t)192 * G * (h + 2) * (w + 2) + (size_t)3 * cpad_in * sizeof(float); }
 
-template <int NPT, int MODE, int SIDE>
+// HALO / PLANE: the tile path of the Atari net's representation (LcConv::halo_in / out_plane, k_lc_conv's PLANE build), identity staging only.
+// HALO: in0 holds the (h + 2) x (w + 2) positions of a tile WITH its halo in the slab's own row pitch, so the staging is a linear copy of the
+// tile -- a lane's quad is four consecutive slab positions and may run over a row end, ring positions included -- and only the h x w inner
+// positions are computed.  PLANE: the epilogue writes them (and reads skip / mask / partner) at their place in planes [B][cout][pl_h][pl_w].
+// Neither touches the k loop: a tile-path conv sums in the order of every other build.
+template <int NPT, int MODE, int SIDE, bool HALO = false, bool PLANE = false>
 __global__ __launch_bounds__(256, 2) void k_lc_conv_bf16x3(const Pair<LcConv> PJ) {
+    static_assert(!HALO || (MODE == IN_IDENT && SIDE == 0), "the tile path stages gathered tiles: identity, one tile per workgroup");
+    static_assert(!PLANE || HALO, "the plane epilogue belongs to the halo_in builds");
     const bool second = (int)blockIdx.y >= PJ.na;
     LcConv L = second ? PJ.b : PJ.a;
     if constexpr (SIDE > 0) { L.h = SIDE; L.w_img = SIDE; L.G = 1; }
+    if constexpr (HALO) L.G = 1;
     L.in_mode = MODE;
     const int by = second ? (int)blockIdx.y - PJ.na : (int)blockIdx.y;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -46,16 +56,19 @@ __global__ __launch_bounds__(256, 2) void k_lc_conv_bf16x3(const Pair<LcConv> PJ
     const float r_qp = 1.0f / (float)QP, r_iw = 1.0f / (float)L.w_img, r_hw = 1.0f / (float)hw;
     const __amdgpu_buffer_rsrc_t rs_in0 = mkrs(L.in0), rs_in1 = mkrs(L.in1 ? L.in1 : L.in0), rs_mat = mkrs(L.mat_out ? L.mat_out : L.in0);
     // ---- staging plan: lane t of every wave owns pixel quad t of the group (k_lc_conv's); wave w the channel octet w of each 32-channel block ----
-    const int sg = lc_idiv(lane, r_qp), qd = lane - sg * QP, p0 = qd * 4, bimg = img0 + sg;
-    const bool w_ok = lane < L.G * QP && bimg < L.B;
+    const int in_hw = HALO ? plane : hw;  // positions per image and channel of in0
+    const int QPs = HALO ? (plane + 3) >> 2 : QP;
+    const float r_qps = HALO ? 1.0f / (float)QPs : r_qp;
+    const int sg = lc_idiv(lane, r_qps), qd = lane - sg * QPs, p0 = qd * 4, bimg = img0 + sg;
+    const bool w_ok = lane < L.G * QPs && bimg < L.B;
     const int cimg = bimg < L.B ? bimg : L.B - 1;
-    const unsigned w_voff = (unsigned)(((size_t)cimg * L.cin_real * hw + (size_t)(w_ok ? p0 : 0)) * sizeof(float));
+    const unsigned w_voff = (unsigned)(((size_t)cimg * L.cin_real * in_hw + (size_t)(w_ok ? p0 : 0)) * sizeof(float));
     const int w_act = (w_ok && L.action) ? L.action[cimg] : -1;
     int w_spos[4], w_pm[4];  // slab position (16-byte words, octet plane included) of the quad's pixels, or -1
 #pragma unroll
     for (int e = 0; e < 4; e++) {
         const int pp = p0 + e, py = lc_idiv(pp, r_iw), px = pp - py * L.w_img;
-        w_spos[e] = (w_ok && pp < hw) ? (sg < L.G ? sg : 0) * plane + (py + 1) * siw + px + 1 + wave * npos : -1;
+        w_spos[e] = (w_ok && pp < in_hw) ? (sg < L.G ? sg : 0) * plane + (HALO ? pp : (py + 1) * siw + px + 1) + wave * npos : -1;
         w_pm[e] = L.cin > L.cin_real ? pp % L.num_actions : 0;
     }
     constexpr bool TWO = MODE == IN_BNBWD || MODE == IN_BNRES;
@@ -64,8 +77,8 @@ __global__ __launch_bounds__(256, 2) void k_lc_conv_bf16x3(const Pair<LcConv> PJ
 #pragma unroll
         for (int c = 0; c < 8; c++) {
             const int ch = cb * 32 + 8 * wave + c, chc = ch < L.cin_real ? ch : 0;
-            sv0[c] = ld4(rs_in0, w_voff, chc * hw * (int)sizeof(float));
-            if constexpr (TWO) sv1[c] = ld4(rs_in1, w_voff, chc * hw * (int)sizeof(float));
+            sv0[c] = ld4(rs_in0, w_voff, chc * in_hw * (int)sizeof(float));
+            if constexpr (TWO) sv1[c] = ld4(rs_in1, w_voff, chc * in_hw * (int)sizeof(float));
         }
     };
     auto transform_store = [&](int cb) {
@@ -203,14 +216,19 @@ __global__ __launch_bounds__(256, 2) void k_lc_conv_bf16x3(const Pair<LcConv> PJ
         if (cb + 1 < L.n_cb) transform_store(cb + 1);
         __syncthreads();
     }
-    // ---- epilogue: k_lc_conv's (its builds without out_plane), on the float32 accumulators: lane (q, j) holds pixel slots pt * 16 + 4 q + r
+    // ---- epilogue: k_lc_conv's (PLANE: its out_plane build's), on the float32 accumulators: lane (q, j) holds pixel slots pt * 16 + 4 q + r
     // (r = 0..3) of output channel 16 cot + j ----
     if (cot >= L.co_tiles) return;  // wave-uniform (no barrier below)
     const int co = cot * 16 + j;
     const bool co_ok = co < L.cout;
     const __amdgpu_buffer_rsrc_t rs_out = mkrs(L.out), rs_skip = mkrs(L.skip ? L.skip : L.out), rs_mask = mkrs(L.mask ? L.mask : L.out),
                                  rs_part = mkrs(L.partner ? L.partner : L.out);
-    const unsigned soff = (unsigned)((size_t)img0 * L.cout * hw * sizeof(float));
+    // (PLANE: the workgroup's image is tile (tyi, txi) of plane image pimg; offsets stay below 4 GiB: the launcher checks the plane tensor's size)
+    const int pl_nt = PLANE ? L.pl_nty * L.pl_ntx : 1;
+    const int pimg = PLANE ? img0 / pl_nt : 0, ptl = PLANE ? img0 - pimg * pl_nt : 0, tyi = PLANE ? ptl / L.pl_ntx : 0, txi = PLANE ? ptl - tyi * L.pl_ntx : 0;
+    const int pl_hw = L.pl_h * L.pl_w;
+    const unsigned soff = PLANE ? (unsigned)(((size_t)pimg * L.cout * pl_hw + (size_t)(tyi * L.h) * L.pl_w + (size_t)txi * L.w_img) * sizeof(float))
+                                : (unsigned)((size_t)img0 * L.cout * hw * sizeof(float));
     float ma = 1.0f, mb = 0.0f;
     if (L.mask && L.mcoef && co_ok) { ma = L.mcoef[co]; mb = L.mcoef[L.cpad_out + co]; }
     const bool part_is_mask = L.partner == L.mask;
@@ -257,6 +275,10 @@ __global__ __launch_bounds__(256, 2) void k_lc_conv_bf16x3(const Pair<LcConv> PJ
             const int g = lc_idiv(p, r_hw), pp = p - g * hw;
             b.valid[e] = co_ok && (pb + e < NPT) && (g < L.G) && (img0 + g < L.B);
             const int gs = b.valid[e] ? g : 0, cs = co_ok ? co : 0, ps = b.valid[e] ? pp : 0;  // (a real address for every lane)
+            if constexpr (PLANE) {
+                const int py = lc_idiv(ps, r_iw), px = ps - py * L.w_img;
+                b.vo[e] = (unsigned)(cs * pl_hw + py * L.pl_w + px) * (unsigned)sizeof(float);
+            } else
             b.vo[e] = (unsigned)((gs * L.cout + cs) * hw + ps) * (unsigned)sizeof(float);
             b.kv[e] = b.mv[e] = b.yv[e] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (pb + e < NPT) {
@@ -312,6 +334,10 @@ __global__ __launch_bounds__(256, 2) void k_lc_conv_bf16x3(const Pair<LcConv> PJ
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 ok[e][r] = co_ok && (pb + e < NPT) && (g < L.G) && (img0 + g < L.B);
+                if constexpr (PLANE) {
+                    const int py = lc_idiv(pp, r_iw), px = pp - py * L.w_img;
+                    vo[e][r] = (unsigned)(co * pl_hw + py * L.pl_w + px) * (unsigned)sizeof(float);
+                } else
                 vo[e][r] = (unsigned)((g * L.cout + co) * hw + pp) * (unsigned)sizeof(float);
                 pp++;
                 if (pp == hw) { pp = 0; g++; }

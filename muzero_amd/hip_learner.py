@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libmzlearner_hip.so')
 
 # every symbol include/mzlearner.h declares (tests/test_abi.py checks the library exports all of them)
-ABI_SYMBOLS = ['mzl_last_error', 'mzl_create', 'mzl_destroy', 'mzl_set_wgrad_precision', 'mzl_num_params', 'mzl_grad_floats', 'mzl_num_tensors', 'mzl_tensor_info',
+ABI_SYMBOLS = ['mzl_last_error', 'mzl_create', 'mzl_destroy', 'mzl_set_wgrad_precision', 'mzl_set_atari_precision', 'mzl_num_params', 'mzl_grad_floats', 'mzl_num_tensors', 'mzl_tensor_info',
                'mzl_num_buffers', 'mzl_num_running', 'mzl_buffer_info', 'mzl_bind_buffers', 'mzl_bind', 'mzl_commit', 'mzl_grad', 'mzl_apply',
                'mzl_replay_scratch_doubles', 'mzl_replay_sample', 'mzl_replay_update_priorities', 'mzl_replay_set_error_counters']
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
@@ -44,6 +44,15 @@ def _wgrad_precision(v):
     if not isinstance(v, (str, bool)) and v in (0, 1):
         return int(v)
     raise ValueError(f"wgrad_precision must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
+
+
+def _atari_precision(v, which):
+    """tower_precision / stage_precision of an Atari handle (mzl_set_atari_precision): MZL_CONV_F32 / MZL_CONV_BF16X3."""
+    if isinstance(v, str) and v in CONV_PRECISIONS:
+        return CONV_PRECISIONS[v]
+    if not isinstance(v, (str, bool)) and v in (0, 1):
+        return int(v)
+    raise ValueError(f"{which} must be 0, 1, 'f32' or 'bf16x3', not {v!r}")
 
 
 class MzlConfig(C.Structure):
@@ -81,6 +90,13 @@ class MzlWgradCall(C.Structure):
                                          'ring_rows', 'tapmask')] + [('layer', MzlWgradLayer * 2)]
 
 
+class MzlTileCall(C.Structure):
+    """mzl_tile_call (csrc/mz_learn_conv_host.h): the host operands of mzl_debug_conv_tile."""
+    _fields_ = [(n, C.c_int32) for n in ('direction', 'precision', 'route', 'batch', 'cin', 'cout', 'H', 'W', 'groups', 'pad_')] + \
+               [(n, C.c_void_p) for n in ('weight', 'in_', 'skip', 'mask', 'mcoef', 'partner', 'out', 'part')]
+
+
+TILE_ROUTES = {'plane': 0, 'inner': 1, 'whole': 2}
 WGRAD_MODES = {'plain': 0, 'pair': 1, 'steps': 2, 'ring': 3}
 
 _FUSED_IN = ('weight', 'in0', 'in1', 'coef', 'mat_preload', 'skip', 'mask', 'mcoef', 'partner', 'gamma', 'beta', 'save_in', 'part_in')
@@ -126,6 +142,8 @@ def load_library():
     L.mzl_destroy.argtypes = [vp]
     if hasattr(L, 'mzl_set_wgrad_precision'):  # (an older library loaded for an A/B run, tools/*_vs_parent.py, has none; wgrad_precision != 0 then fails at the call)
         L.mzl_set_wgrad_precision.argtypes = [vp, i32]
+    if hasattr(L, 'mzl_set_atari_precision'):  # (the same: the parent commit's library has none)
+        L.mzl_set_atari_precision.argtypes = [vp, i32, i32]
     L.mzl_num_params.argtypes = [vp]
     L.mzl_num_params.restype = i64
     L.mzl_grad_floats.argtypes = [vp]
@@ -154,6 +172,9 @@ def load_library():
         L.mzl_debug_wgrad.argtypes = [vp, C.POINTER(MzlWgradCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     if hasattr(L, 'mzl_debug_conv_fused'):
         L.mzl_debug_conv_fused.argtypes = [vp, C.POINTER(MzlFusedCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
+    if hasattr(L, 'mzl_debug_conv_tile'):
+        L.mzl_debug_conv_tile.argtypes = [vp, C.POINTER(MzlTileCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
+        L.mzl_debug_precisions.argtypes = [vp, C.POINTER(i32)]
     if hasattr(L, 'mzl_debug_heads'):
         L.mzl_debug_heads.argtypes = [vp, C.POINTER(MzlHeadsCall)]  # diagnostic: exported, not declared
     _lib = L
@@ -241,14 +262,18 @@ class HipLearner:
 
     def __init__(self, network, device, unroll_steps: int, max_batch: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  milestones: Sequence[int] = (), gamma: float = 0.1, clip_grad: bool = False, max_grad_norm: float = 40.0, grad_slices: Optional[int] = None,
-                 conv_precision=0, wgrad_precision=0):
+                 conv_precision=0, wgrad_precision=0, tower_precision=0, stage_precision=0):
         """conv_precision: 'f32' (0, the default) or 'bf16x3' (1): board nets only -- the towers' forward and data-gradient convs as split-bf16
         MFMAs (csrc/mz_learn_conv_split.h).  wgrad_precision: 'f32' (0, the default) or 'bf16x3' (1): board nets only, independent of
-        conv_precision -- the towers' weight gradients as split-bf16 MFMAs (csrc/mz_learn_conv_split_wgrad.h).  BatchNorm, heads and Adam stay
-        float32 either way."""
+        conv_precision -- the towers' weight gradients as split-bf16 MFMAs (csrc/mz_learn_conv_split_wgrad.h).  tower_precision / stage_precision:
+        'f32' (0, the default) or 'bf16x3' (1), Atari nets only (mzl_set_atari_precision), independent of each other: the forward convs and data
+        gradients of the whole-image towers (res_blocks_3, dynamics, prediction) / of the tile path's stride-1 convs (res_blocks_1, res_blocks_2) as
+        split-bf16 MFMAs.  BatchNorm, heads and Adam stay float32 either way."""
         self._h = C.c_void_p()
         self.conv_precision = _conv_precision(conv_precision)
         self.wgrad_precision = _wgrad_precision(wgrad_precision)
+        self.tower_precision = _atari_precision(tower_precision, 'tower_precision')
+        self.stage_precision = _atari_precision(stage_precision, 'stage_precision')
         if not torch.cuda.is_available():
             raise LearnerError('HipLearner needs a GPU (no CPU fallback)')
         L = load_library()
@@ -278,6 +303,11 @@ class HipLearner:
         _check(L.mzl_create(C.byref(cfg), self.device.index or 0, C.byref(self._h)))
         if self.wgrad_precision:  # (the default never calls the setter: the handle is what mzl_create made)
             _check(L.mzl_set_wgrad_precision(self._h, self.wgrad_precision))
+        # (the same: the default, 0, leaves the handle as mzl_create made it; a value given by NAME on an Atari net is passed on even when it is
+        # 'f32' -- the setter called with MZL_CONV_F32 twice is the same update bit for bit, and tests/test_gpu_split_atari_learner.py holds it to that)
+        named = self.kind == 'atari' and (isinstance(tower_precision, str) or isinstance(stage_precision, str))
+        if self.tower_precision or self.stage_precision or named:
+            _check(L.mzl_set_atari_precision(self._h, self.tower_precision, self.stage_precision))
         self.K, self.A, self.in_dim, self.max_batch = unroll_steps, spec['num_actions'], in_dim, max_batch
         if self.kind in ('board', 'atari'):  # (debug_heads: planes, positions of the hidden state, reward / value support)
             self._heads_geom = (spec['num_planes'], bh * bw if self.kind == 'board' else (bh // 16) * (bw // 16), spec['reward_support_size'], spec['value_support_size'])
@@ -539,6 +569,53 @@ class HipLearner:
                                              x.ctypes.data_as(C.c_void_p), None if act is None else act.ctypes.data_as(C.c_void_p), int(num_actions),
                                              out.ctypes.data_as(C.c_void_p), C.byref(name)))
         return out, (name.value or b'').decode()
+
+    def debug_conv_tile(self, direction: int, weight, x, skip=None, mask=None, mcoef=None, partner=None, precision='f32', route: str = 'plane',
+                        want_part: bool = False):
+        """Diagnostic (tests): ONE stride-1 conv of the Atari net's tile path as the update builds it (gather into haloed tiles, op builder,
+        dispatcher), at `precision` ('f32' | 'bf16x3') whatever the handle's switches.  direction 0: the forward conv of the plane x [B, cin, H, W]
+        with weight [cout, cin, 3, 3]; direction 1: the data gradient of dy = x [B, cout, H, W].  route: 'plane' (the update: the out_plane
+        epilogue; skip, mask + partner (+ mcoef) and the statistics partials belong to it), 'inner' / 'whole' (inner-only or whole haloed tiles and
+        k_lc_tile_scatter; skip only).  Host arrays; returns (out, build name) or, want_part, (out, build name, partials [tiles, pad16(c_out), 4 | 2])."""
+        f32 = np.float32
+        weight, x = np.ascontiguousarray(weight, f32), np.ascontiguousarray(x, f32)
+        if weight.ndim != 4 or x.ndim != 4 or tuple(weight.shape[2:]) != (3, 3):
+            raise LearnerError('mzl_debug_conv_tile: weight [cout, cin, 3, 3] and x [B, channels, H, W]')
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        B, xc, H, W = (int(v) for v in x.shape)
+        c_out = cout if direction == 0 else cin
+        if xc != (cin if direction == 0 else cout):
+            raise LearnerError(f'mzl_debug_conv_tile: weight {weight.shape} does not fit x {x.shape} in direction {direction}')
+        if route not in TILE_ROUTES:
+            raise ValueError(f"route must be one of {sorted(TILE_ROUTES)}, not {route!r}")
+        keep = [weight, x]
+
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, f32)
+            if tuple(a.shape) != shape:
+                raise LearnerError(f'mzl_debug_conv_tile: an operand of shape {a.shape}, expected {shape}')
+            keep.append(a)
+            return a.ctypes.data_as(C.c_void_p)
+
+        out = np.zeros((B, c_out, H, W), f32)
+        cpo = (c_out + 15) // 16 * 16
+        # (a masked conv always leaves its ST_BWD sums; rows: at least the tiles of the call)
+        part = np.zeros((B * (H // 12) * (W // 12), cpo, 2 if mask is not None else 4), f32) if want_part or mask is not None else None
+        call = MzlTileCall(int(direction), _atari_precision(precision, 'precision'), TILE_ROUTES[route], B, cin, cout, H, W, 0, 0,
+                           weight.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), arr(skip, out.shape), arr(mask, out.shape), arr(mcoef, (2, c_out)),
+                           arr(partner, out.shape), out.ctypes.data_as(C.c_void_p), None if part is None else part.ctypes.data_as(C.c_void_p))
+        name = C.c_char_p()
+        _check(load_library().mzl_debug_conv_tile(self._h, C.byref(call), C.byref(name)))
+        name = (name.value or b'').decode()
+        return (out, name, part[:call.groups]) if want_part else (out, name)
+
+    def debug_precisions(self):
+        """Diagnostic (tests): (tower_precision, stage_precision, wgrad_precision) as the HANDLE holds them (conv nets)."""
+        v = (C.c_int32 * 3)()
+        _check(load_library().mzl_debug_precisions(self._h, v))
+        return tuple(int(x) for x in v)
 
     def debug_wgrad(self, dz, x, mode: str = 'plain', y=None, dcoef=None, xcoef=None, action=None, num_actions: int = 0, cin: Optional[int] = None,
                     preload=None, accumulate: bool = False, second=None, sg: int = 0, layout: int = 0, ipw: int = 0, remap: int = 0, act_route: int = 0,

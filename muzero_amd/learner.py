@@ -276,17 +276,19 @@ def make_capturable_adam(network, config, device):
                             capturable=True)
 
 
-def make_hip_learner(config, network, device, max_batch: Optional[int] = None, conv_precision=0, wgrad_precision=0):
+def make_hip_learner(config, network, device, max_batch: Optional[int] = None, conv_precision=0, wgrad_precision=0, tower_precision=0, stage_precision=0):
     """The learner step on hand-written gfx950 kernels (muzero_amd.hip_learner.HipLearner, MLP nets) with the optimizer the
     reference's launchers build (classic/run_training.py:94-95: Adam(lr_init, weight_decay) + MultiStepLR(lr_milestones, lr_decay_rate)).
     Hand `hl.optimizer` / `hl.lr_scheduler` to `run_training` in place of the torch objects.  conv_precision: 'f32' (default) or 'bf16x3'
     (board nets: the towers' forward and data-gradient convs as split-bf16 MFMAs); wgrad_precision: 'f32' (default) or 'bf16x3' (board nets: the
-    towers' weight gradients as split-bf16 MFMAs, independent of conv_precision); everything else stays float32."""
+    towers' weight gradients as split-bf16 MFMAs, independent of conv_precision); tower_precision / stage_precision: 'f32' (default) or 'bf16x3'
+    (Atari nets: the whole-image towers' / the tile path's stride-1 convs, forward and data gradient, as split-bf16 MFMAs); everything else stays
+    float32."""
     from muzero_amd.hip_learner import HipLearner
 
     return HipLearner(network, device, config.unroll_steps, max_batch or config.batch_size, lr=config.lr_init, weight_decay=config.weight_decay,
                       milestones=config.lr_milestones, gamma=config.lr_decay_rate, clip_grad=bool(config.clip_grad), max_grad_norm=config.max_grad_norm,
-                      conv_precision=conv_precision, wgrad_precision=wgrad_precision)
+                      conv_precision=conv_precision, wgrad_precision=wgrad_precision, tower_precision=tower_precision, stage_precision=stage_precision)
 
 
 def _all_ranks(flag_any: bool, device) -> bool:
