@@ -385,6 +385,16 @@ extern "C" int mzl_debug_conv_tile(mz_learner* h, mzl_tile_call* call, const cha
     const int rc = mzlc_debug_conv_tile(h->conv, call, build_name, err);
     return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_conv_tile: " + err);
 }
+// diagnostic (tests; exported, NOT part of include/mzlearner.h): ONE launch group of the Atari representation outside its stride-1 convs -- a stride-2
+// conv or its data gradient over the parity planes, a pool, the ReLU backward, the entry / normalize kernels, one gather or one scatter -- through the
+// AtariRun members the update calls (learner_conv.hip mzlc_debug_atari_stage; the argument block is mz_learn_conv_host.h's); host pointers
+extern "C" int mzl_debug_atari_stage(mz_learner* h, mzl_stage_call* call, const char** build_name) {
+    if (!h || !h->conv) return fail(MZL_E_INVALID, "mzl_debug_atari_stage: needs a conv-net learner (MZL_NET_BOARD or MZL_NET_ATARI)");
+    if (!call || !build_name) return fail(MZL_E_INVALID, "mzl_debug_atari_stage: null argument");
+    std::string err;
+    const int rc = mzlc_debug_atari_stage(h->conv, call, build_name, err);
+    return rc == MZL_OK ? MZL_OK : fail(rc, "mzl_debug_atari_stage: " + err);
+}
 // diagnostic (tests): the Atari handle's switches as the handle holds them: [0] tower_precision, [1] stage_precision, [2] wgrad_precision
 extern "C" int mzl_debug_precisions(const mz_learner* h, int32_t* out3) {
     if (!h || !h->conv || !out3) return fail(MZL_E_INVALID, "mzl_debug_precisions: needs a conv-net learner");

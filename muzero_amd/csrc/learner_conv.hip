@@ -892,14 +892,16 @@ void launch_entry(mzlc_learner* h, const LcEntry& e, hipStream_t st) {
     else if (cpt <= 16) hipLaunchKernelGGL(k_lc_entry<16>, grid, dim3(256), 0, st, e);
     else hipLaunchKernelGGL(k_lc_entry<32>, grid, dim3(256), 0, st, e);
 }
-void launch_normalize(mzlc_learner* h, const float* in, float* out, int B, hipStream_t st) {
-    const dim3 grid(cdiv(h->hw, 32), B);
-    const int cpt = cdiv(h->P, 8);
-    if (cpt <= 2) hipLaunchKernelGGL(k_lc_normalize<2>, grid, dim3(256), 0, st, in, out, B, h->P, h->hw);
-    else if (cpt <= 8) hipLaunchKernelGGL(k_lc_normalize<8>, grid, dim3(256), 0, st, in, out, B, h->P, h->hw);
-    else if (cpt <= 16) hipLaunchKernelGGL(k_lc_normalize<16>, grid, dim3(256), 0, st, in, out, B, h->P, h->hw);
-    else hipLaunchKernelGGL(k_lc_normalize<32>, grid, dim3(256), 0, st, in, out, B, h->P, h->hw);
+// (C, hw: the handle's P and hw in the update; mzlc_debug_atari_stage passes its call's)
+void launch_normalize(const float* in, float* out, int B, int C, int hw, hipStream_t st) {
+    const dim3 grid(cdiv(hw, 32), B);
+    const int cpt = cdiv(C, 8);
+    if (cpt <= 2) hipLaunchKernelGGL(k_lc_normalize<2>, grid, dim3(256), 0, st, in, out, B, C, hw);
+    else if (cpt <= 8) hipLaunchKernelGGL(k_lc_normalize<8>, grid, dim3(256), 0, st, in, out, B, C, hw);
+    else if (cpt <= 16) hipLaunchKernelGGL(k_lc_normalize<16>, grid, dim3(256), 0, st, in, out, B, C, hw);
+    else hipLaunchKernelGGL(k_lc_normalize<32>, grid, dim3(256), 0, st, in, out, B, C, hw);
 }
+void launch_normalize(mzlc_learner* h, const float* in, float* out, int B, hipStream_t st) { launch_normalize(in, out, B, h->P, h->hw, st); }
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -908,6 +910,27 @@ void launch_normalize(mzlc_learner* h, const float* in, float* out, int B, hipSt
 // fused path of the towers) -> avg pool -> 6 x 6.  Launched one job at a time (nothing to pair with); the planes are cut into 12 x 12 tiles.
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int TILE = 12;
+
+// tap maps of the parity planes (mz_learn_conv.h, LcTileGather).  Forward / weight gradient: stride-1 tap (sy, sx) of plane (p, q) is weight tap
+// (krow(p, sy), krow(q, sx)); data gradient of a stride-2 conv: output parity plane (p, q) of dx from dy.
+int par_row(int p, int s) { return p == 0 ? (s == 1 ? 1 : -1) : (s == 0 ? 0 : (s == 1 ? 2 : -1)); }
+int par_row_d(int p, int s) { return p == 0 ? (s == 1 ? 1 : -1) : (s == 2 ? 0 : (s == 1 ? 2 : -1)); }
+void par_tapmap(int p, int q, bool dgrad, signed char* m) {
+    for (int sy = 0; sy < 3; sy++)
+        for (int sx = 0; sx < 3; sx++) {
+            const int ky = dgrad ? par_row_d(p, sy) : par_row(p, sy), kx = dgrad ? par_row_d(q, sx) : par_row(q, sx);
+            m[sy * 3 + sx] = (signed char)((ky >= 0 && kx >= 0) ? ky * 3 + kx : -1);
+        }
+}
+
+int par_tapmask(int p, int q, bool dgrad) {
+    signed char m[9];
+    par_tapmap(p, q, dgrad, m);
+    int mask = 0;
+    for (int t = 0; t < 9; t++)
+        if (m[t] >= 0) mask |= 1 << t;
+    return mask;
+}
 
 struct AtariRun {
     mzlc_learner* h;
@@ -997,17 +1020,38 @@ struct AtariRun {
         o.side15 = 0;
         return o;
     }
-    // one parity plane's share of a stride-2 conv: the packed copy at `w_off`; accumulate: out += (the earlier planes' sum rides in `skip`)
-    void conv_par(int w_off, int cin, int cout, int H, int W, const float* in, float* out, bool accumulate, int tapmask) const {
+    // one parity plane's share of a stride-2 conv: the packed copy at `packed + w_off`; accumulate: out += (the earlier planes' sum rides in `skip`).
+    // false: the dispatcher has no build for this tap set (nothing was launched)
+    bool conv_par(const float* packed, int w_off, int cin, int cout, int H, int W, const float* in, float* out, bool accumulate, int tapmask) const {
         const Sched s = tiles(cin, H, W);
         const Geom& tg = tgeom(W);
         LcConv c{};
         c.B = B * ntiles(H, W); c.G = tg.G; c.h = tg.h; c.w_img = tg.w; c.qstride = tg.qstride;
-        c.cin_real = cin; c.cin = cin; c.n_cb = cdiv(cin, 16); c.cout = cout; c.co_tiles = cdiv(cout, 16); c.w = h->packed + w_off;
+        c.cin_real = cin; c.cin = cin; c.n_cb = cdiv(cin, 16); c.cout = cout; c.co_tiles = cdiv(cout, 16); c.w = packed + w_off;
         c.cpad_in = pad16(cin); c.cpad_out = pad16(cout); c.num_actions = h->A;
         c.in0 = in; c.in_mode = IN_IDENT; c.out = out; c.skip = accumulate ? out : nullptr; c.stat_mode = ST_NONE;
         c.tapmask = h->par_compact ? tapmask : 0;
-        run(s.op_conv(c, false));  // (the parity planes' tap-set builds are float32 only)
+        const Op o = s.op_conv(c, false);  // (the parity planes' tap-set builds are float32 only)
+        return launch_ops(h, &o, nullptr, st) == 0;
+    }
+    // a stride-2 conv (conv_1, conv_2) of src [B][cin][2H][2W]: its four parity planes gathered into `ta`, convolved on their own taps (the packed
+    // copies at packed + w_off[pq]) and accumulated on the tiles `tb`, which are scattered into y [B][cout][H][W].  Also mzlc_debug_atari_stage's
+    // s2_fwd, on buffers of its own.  false: no build (see conv_par)
+    bool s2_fwd(const float* packed, const int* w_off, const float* src, int cin, int cout, int H, int W, float* ta, float* tb, float* y) const {
+        for (int pq = 0; pq < 4; pq++) {
+            gather(src, nullptr, nullptr, IN_IDENT, cin, H, W, 2 * H, 2 * W, 2, 2, pq >> 1, pq & 1, 0, ta);
+            if (!conv_par(packed, w_off[pq], cin, cout, H, W, ta, tb, pq > 0, par_tapmask(pq >> 1, pq & 1, false))) return false;
+        }
+        scatter(tb, cout, H, W, y, H, W, 1, 1, 0, 0, nullptr, nullptr);
+        return true;
+    }
+    // its data gradient from the haloed dy tiles [B tiles][cout][14][tw + 2]: parity plane (p, q) of dx [B][cin][2H][2W] per conv + scatter
+    bool s2_dgrad(const float* packed, const int* w_off, const float* dy_tiles, int cin, int cout, int H, int W, float* tb, float* dx) const {
+        for (int pq = 0; pq < 4; pq++) {
+            if (!conv_par(packed, w_off[pq], cout, cin, H, W, dy_tiles, tb, false, par_tapmask(pq >> 1, pq & 1, true))) return false;
+            scatter(tb, cin, H, W, dx, 2 * H, 2 * W, 2, 2, pq >> 1, pq & 1, nullptr, nullptr);
+        }
+        return true;
     }
     void bn_fwd(const LayerInfo& L, float* fcoef, float* save, int groups, float count) const {
         const Sched s = plain(L.cout);
@@ -1028,9 +1072,9 @@ struct AtariRun {
         run(o);
     }
     // dz = extra [x > 0] + the BatchNorm-backward partial sums against `partner`; returns the groups written to stat[0]
-    int entry(const float* x, const float* gs, float scale, const float* extra, const float* partner, float* dz, int C, int hw) const {
+    int entry(const float* x, const float* gs, float scale, const float* extra, const float* partner, float* dz, int C, int hw, float* stat_part) const {
         LcEntry e{};
-        e.x = x; e.gs = gs; e.extra = extra; e.partner = partner; e.dz = dz; e.stat_part = h->stat[0]; e.scale = scale; e.B = B; e.C = C; e.hw = hw; e.cpad = pad16(C);
+        e.x = x; e.gs = gs; e.extra = extra; e.partner = partner; e.dz = dz; e.stat_part = stat_part; e.scale = scale; e.B = B; e.C = C; e.hw = hw; e.cpad = pad16(C);
         const int cpt = cdiv(C, 8);
         if (!gs && extra && hw % 4 == 0) {  // the tiled stages: four positions per lane
             const int nchunks = cdiv(hw / 4, 32), split = nchunks < 32 ? nchunks : 32;
@@ -1048,6 +1092,32 @@ struct AtariRun {
         else if (cpt <= 16) hipLaunchKernelGGL(k_lc_entry<16>, grid, dim3(256), 0, st, e);
         else hipLaunchKernelGGL(k_lc_entry<32>, grid, dim3(256), 0, st, e);
         return B * split;
+    }
+    // the same ahead of the 12 x 12 stage (whole images on the towers' fused path): k_lc_entry over ENTRY_SPLIT workgroups per image, no normalize
+    int entry12(const float* x, const float* extra, const float* partner, float* dz, int C, int hw, float* stat_part) const {
+        LcEntry e{};
+        e.x = x; e.gs = nullptr; e.extra = extra; e.partner = partner; e.dz = dz; e.stat_part = stat_part; e.scale = 1.0f;
+        e.B = B; e.C = C; e.hw = hw; e.cpad = pad16(C);
+        const int nchunks = cdiv(e.hw, 32), split = nchunks < ENTRY_SPLIT ? nchunks : ENTRY_SPLIT;
+        const dim3 grid(split, B);
+        const int cpt = cdiv(C, 8);
+        if (cpt <= 2) hipLaunchKernelGGL(k_lc_entry<2>, grid, dim3(256), 0, st, e);
+        else if (cpt <= 8) hipLaunchKernelGGL(k_lc_entry<8>, grid, dim3(256), 0, st, e);
+        else if (cpt <= 16) hipLaunchKernelGGL(k_lc_entry<16>, grid, dim3(256), 0, st, e);
+        else hipLaunchKernelGGL(k_lc_entry<32>, grid, dim3(256), 0, st, e);
+        return B * split;
+    }
+    // AvgPool 3/2/1 of [B][C][ih][iw] and its backward; dz = g [x > 0] of a ReLU without BatchNorm (also mzlc_debug_atari_stage's, on buffers of its own)
+    void pool_fwd(const float* in, float* out, int C, int ih, int iw) const {
+        const long long n = (long long)B * C * (ih / 2) * (iw / 2);
+        hipLaunchKernelGGL(k_lc_pool_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, n, ih, iw, ih / 2, iw / 2);
+    }
+    void pool_bwd(const float* gout, float* gin, int C, int ih, int iw) const {
+        const long long n = (long long)B * C * ih * iw;
+        hipLaunchKernelGGL(k_lc_pool_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gout, gin, n, ih, iw, ih / 2, iw / 2);
+    }
+    void relu_bwd(const float* g, const float* x, float* dz, long long n) const {
+        hipLaunchKernelGGL(k_lc_relu_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, x, dz, n);
     }
     // weight gradient of layer L from dy tiles (already BatchNorm-backward transformed, halo included: ring_zero) and x tiles
     void wgrad_tiles(const LayerInfo& L, int cin, int H, int W, const float* dy_tiles, const float* x_tiles, const signed char* tapmap) const {
@@ -1140,7 +1210,7 @@ struct AtariRun {
                     conv_tiles(L2, true, H, W, h->TA, h->TB);
                     scatter(h->TB, C, H, W, sb.gF, H, W, 1, 1, 0, 0, nullptr, nullptr, halo_in());
                 }
-                ng = entry(sb.h1[r], nullptr, 1.0f, sb.gF, sb.y[2 * r], sb.dzB, C, hw);
+                ng = entry(sb.h1[r], nullptr, 1.0f, sb.gF, sb.y[2 * r], sb.dzB, C, hw, h->stat[0]);
             }
             bn_bwd(L1, sb.save[2 * r], sb.bcoef[2 * r], ng, count);
             gather(sb.dzB, sb.y[2 * r], sb.bcoef[2 * r], IN_BNBWD, C, H, W, H, W, 1, 1, 0, 0, 0, h->TA);
@@ -1154,32 +1224,11 @@ struct AtariRun {
                     conv_tiles(L1, true, H, W, h->TA, h->TB);
                     scatter(h->TB, C, H, W, sb.gF, H, W, 1, 1, 0, 0, sb.dzA, nullptr, halo_in());  // + the block's skip gradient
                 }
-                if (r > 0) ng = entry(xin_blk, nullptr, 1.0f, sb.gF, sb.y[2 * r - 1], sb.dzA, C, hw);
+                if (r > 0) ng = entry(xin_blk, nullptr, 1.0f, sb.gF, sb.y[2 * r - 1], sb.dzA, C, hw, h->stat[0]);
             }
         }
     }
 };
-
-// tap maps of the parity planes (mz_learn_conv.h, LcTileGather).  Forward / weight gradient: stride-1 tap (sy, sx) of plane (p, q) is weight tap
-// (krow(p, sy), krow(q, sx)); data gradient of a stride-2 conv: output parity plane (p, q) of dx from dy.
-int par_row(int p, int s) { return p == 0 ? (s == 1 ? 1 : -1) : (s == 0 ? 0 : (s == 1 ? 2 : -1)); }
-int par_row_d(int p, int s) { return p == 0 ? (s == 1 ? 1 : -1) : (s == 2 ? 0 : (s == 1 ? 2 : -1)); }
-void par_tapmap(int p, int q, bool dgrad, signed char* m) {
-    for (int sy = 0; sy < 3; sy++)
-        for (int sx = 0; sx < 3; sx++) {
-            const int ky = dgrad ? par_row_d(p, sy) : par_row(p, sy), kx = dgrad ? par_row_d(q, sx) : par_row(q, sx);
-            m[sy * 3 + sx] = (signed char)((ky >= 0 && kx >= 0) ? ky * 3 + kx : -1);
-        }
-}
-
-int par_tapmask(int p, int q, bool dgrad) {
-    signed char m[9];
-    par_tapmap(p, q, dgrad, m);
-    int mask = 0;
-    for (int t = 0; t < 9; t++)
-        if (m[t] >= 0) mask |= 1 << t;
-    return mask;
-}
 
 // forward of the Atari representation; returns the 6 x 6 raw hidden state
 float* atari_rep_fwd(mzlc_learner* h, int B, hipStream_t st) {
@@ -1187,33 +1236,19 @@ float* atari_rep_fwd(mzlc_learner* h, int B, hipStream_t st) {
     const int H1 = h->obsH / 2, W1 = h->obsW / 2, H2 = H1 / 2, W2 = W1 / 2, H3 = H2 / 2, W3 = W2 / 2;
     const LayerInfo &C1 = h->layers[h->l_c1], &C2 = h->layers[h->l_c2];
     // conv_1: four parity planes of the observation, accumulated on the tiles
-    for (int pq = 0; pq < 4; pq++) {
-        R.gather(h->obs, nullptr, nullptr, IN_IDENT, h->C0, H1, W1, h->obsH, h->obsW, 2, 2, pq >> 1, pq & 1, 0, h->TA);
-        R.conv_par(h->par_f[0][pq], h->C0, C1.cout, H1, W1, h->TA, h->TB, pq > 0, par_tapmask(pq >> 1, pq & 1, false));
-    }
-    R.scatter(h->TB, C1.cout, H1, W1, h->y_c1, H1, W1, 1, 1, 0, 0, nullptr, nullptr);
+    R.s2_fwd(h->packed, h->par_f[0], h->obs, h->C0, C1.cout, H1, W1, h->TA, h->TB, h->y_c1);
     const int big = pad16(h->P > 128 ? h->P : 128);  // the row stride of coef_relu / coef_ident
     R.apply(h->y_c1, nullptr, h->coef_relu, h->a1, C1.cout, H1 * W1, big);
     float* x48 = R.stage_fwd(h->sb48, h->l_b1, h->a1, 128, H1, W1);
-    for (int pq = 0; pq < 4; pq++) {
-        R.gather(x48, nullptr, nullptr, IN_IDENT, 128, H2, W2, H1, W1, 2, 2, pq >> 1, pq & 1, 0, h->TA);
-        R.conv_par(h->par_f[1][pq], 128, C2.cout, H2, W2, h->TA, h->TB, pq > 0, par_tapmask(pq >> 1, pq & 1, false));
-    }
-    R.scatter(h->TB, h->P, H2, W2, h->y_c2, H2, W2, 1, 1, 0, 0, nullptr, nullptr);
+    R.s2_fwd(h->packed, h->par_f[1], x48, 128, C2.cout, H2, W2, h->TA, h->TB, h->y_c2);
     R.apply(h->y_c2, nullptr, h->coef_relu, h->a2, h->P, H2 * W2, big);
     float* x24 = R.stage_fwd(h->sb24, h->l_b2, h->a2, h->P, H2, W2);
-    {
-        const long long n = (long long)B * h->P * H3 * W3;
-        hipLaunchKernelGGL(k_lc_pool_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x24, h->p1, n, H2, W2, H3, W3);
-    }
+    R.pool_fwd(x24, h->p1, h->P, H2, W2);
     std::vector<Op> ops;
     const Sched s12{h, B, 0, false, h->g12, h->P};
     float* x12 = s12.tower_fwd(ops, h->t12, h->a12, h->p1, nullptr);
     for (const Op& o : ops) launch_ops(h, &o, nullptr, st);
-    {
-        const long long n = (long long)B * h->P * h->hw;
-        hipLaunchKernelGGL(k_lc_pool_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x12, h->hraw, n, H3, W3, h->h, h->w);
-    }
+    R.pool_fwd(x12, h->hraw, h->P, H3, W3);
     return h->hraw;
 }
 
@@ -1228,42 +1263,24 @@ void atari_rep_bwd(mzlc_learner* h, int B, const float* gs0, hipStream_t st) {
     float* x48 = h->sb48.x[1];
     // normalize backward (the mask x > 0 of k_lc_entry is harmless on an average of ReLU outputs: where it is 0 every input of the window is 0 and masked
     // below), average-pool backward, mask + partial sums of res_blocks_3's last BatchNorm
-    R.entry(h->hraw, gs0, 1.0f, nullptr, h->hraw, h->dH, P, h->hw);
+    R.entry(h->hraw, gs0, 1.0f, nullptr, h->hraw, h->dH, P, h->hw, h->stat[0]);
+    R.pool_bwd(h->dH, h->g12in, P, H3, W3);
     {
-        const long long n = (long long)B * P * H3 * W3;
-        hipLaunchKernelGGL(k_lc_pool_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->dH, h->g12in, n, H3, W3, h->h, h->w);
-    }
-    {
-        LcEntry e{};
         float* keep[3] = {h->D[0][0], h->D[0][1], h->D[0][2]};
         for (int i = 0; i < 3; i++) h->D[0][i] = h->D12[i];  // (the op builders read the buffers of lane 0; restored below)
-        e.x = x12; e.gs = nullptr; e.extra = h->g12in; e.partner = h->a12.y.back(); e.dz = h->D[0][0]; e.stat_part = h->stat[0]; e.scale = 1.0f;
-        e.B = B; e.C = P; e.hw = H3 * W3; e.cpad = pad16(P);
-        const int nchunks = cdiv(e.hw, 32), split = nchunks < ENTRY_SPLIT ? nchunks : ENTRY_SPLIT;
-        const dim3 grid(split, B);
-        const int cpt = cdiv(P, 8);
-        if (cpt <= 2) hipLaunchKernelGGL(k_lc_entry<2>, grid, dim3(256), 0, st, e);
-        else if (cpt <= 8) hipLaunchKernelGGL(k_lc_entry<8>, grid, dim3(256), 0, st, e);
-        else if (cpt <= 16) hipLaunchKernelGGL(k_lc_entry<16>, grid, dim3(256), 0, st, e);
-        else hipLaunchKernelGGL(k_lc_entry<32>, grid, dim3(256), 0, st, e);
+        const int ng12 = R.entry12(x12, h->g12in, h->a12.y.back(), h->D[0][0], P, H3 * W3, h->stat[0]);
         std::vector<Op> ops;
         const Sched s12{h, B, 0, false, h->g12, P};
-        s12.tower_bwd(ops, h->t12, h->a12, h->p1, nullptr, B * split, 0, h->g12in, nullptr);  // gradient wrt the pooled 12 x 12 input -> g12in
+        s12.tower_bwd(ops, h->t12, h->a12, h->p1, nullptr, ng12, 0, h->g12in, nullptr);  // gradient wrt the pooled 12 x 12 input -> g12in
         for (const Op& o : ops) launch_ops(h, &o, nullptr, st);
         for (int i = 0; i < 3; i++) h->D[0][i] = keep[i];
     }
     // 24 x 24 stage
-    {
-        const long long n = (long long)B * P * H2 * W2;
-        hipLaunchKernelGGL(k_lc_pool_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->g12in, h->sb24.gF, n, H2, W2, H3, W3);
-    }
-    int ng = R.entry(x24, nullptr, 1.0f, h->sb24.gF, h->sb24.y[3], h->sb24.dzA, P, H2 * W2);
+    R.pool_bwd(h->g12in, h->sb24.gF, P, H2, W2);
+    int ng = R.entry(x24, nullptr, 1.0f, h->sb24.gF, h->sb24.y[3], h->sb24.dzA, P, H2 * W2, h->stat[0]);
     R.stage_bwd(h->sb24, h->l_b2, h->a2, P, H2, W2, ng);
     // conv_2 (stride 2, relu without BatchNorm): dy = g [a2 > 0]
-    {
-        const long long n = (long long)B * P * H2 * W2;
-        hipLaunchKernelGGL(k_lc_relu_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->sb24.gF, h->a2, h->sb24.dzB, n);
-    }
+    R.relu_bwd(h->sb24.gF, h->a2, h->sb24.dzB, (long long)B * P * H2 * W2);
     R.gather(h->sb24.dzB, nullptr, nullptr, IN_IDENT, P, H2, W2, H2, W2, 1, 1, 0, 0, 0, h->TA);  // dy tiles with halo: both gradients read them
     for (int pq = 0; pq < 4; pq++) {
         signed char m[9];
@@ -1271,17 +1288,11 @@ void atari_rep_bwd(mzlc_learner* h, int B, const float* gs0, hipStream_t st) {
         R.gather(x48, nullptr, nullptr, IN_IDENT, 128, H2, W2, H1, W1, 2, 2, pq >> 1, pq & 1, 0, h->TC);
         R.wgrad_tiles(C2, 128, H2, W2, h->TA, h->TC, m);
     }
-    for (int pq = 0; pq < 4; pq++) {  // data gradient: parity plane (p, q) of the 48 x 48 gradient from the dy tiles
-        R.conv_par(h->par_d[pq], P, 128, H2, W2, h->TA, h->TB, false, par_tapmask(pq >> 1, pq & 1, true));
-        R.scatter(h->TB, 128, H2, W2, h->sb48.gF, H1, W1, 2, 2, pq >> 1, pq & 1, nullptr, nullptr);
-    }
-    ng = R.entry(x48, nullptr, 1.0f, h->sb48.gF, h->sb48.y[3], h->sb48.dzA, 128, H1 * W1);
+    R.s2_dgrad(h->packed, h->par_d, h->TA, 128, P, H2, W2, h->TB, h->sb48.gF);  // data gradient: the four parity planes of the 48 x 48 gradient from the dy tiles
+    ng = R.entry(x48, nullptr, 1.0f, h->sb48.gF, h->sb48.y[3], h->sb48.dzA, 128, H1 * W1, h->stat[0]);
     R.stage_bwd(h->sb48, h->l_b1, h->a1, 128, H1, W1, ng);
     // conv_1: weight gradient only (its input is the observation)
-    {
-        const long long n = (long long)B * 128 * H1 * W1;
-        hipLaunchKernelGGL(k_lc_relu_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->sb48.gF, h->a1, h->sb48.dzB, n);
-    }
+    R.relu_bwd(h->sb48.gF, h->a1, h->sb48.dzB, (long long)B * 128 * H1 * W1);
     R.gather(h->sb48.dzB, nullptr, nullptr, IN_IDENT, 128, H1, W1, H1, W1, 1, 1, 0, 0, 0, h->TA);
     for (int pq = 0; pq < 4; pq++) {
         signed char m[9];
@@ -2233,6 +2244,210 @@ int mzlc_debug_conv_tile(mzlc_learner* h, mzl_tile_call* c, const char** build_n
     snprintf(name, sizeof(name), "%s %s NPT=%d HALO=%d PLANE=%d tile=12x%d tiles=%d groups=%d dir=%s stat=%s us=%.1f", split ? "bf16x3" : "f32", split ? "k_lc_conv_bf16x3" : "k_lc_conv",
              o.npt, o.conv.halo_in, o.conv.out_plane, tw, nt, groups, dg ? "dgrad" : "forward", o.conv.stat_mode == ST_FWD ? "ST_FWD" : o.conv.stat_mode == ST_BWD ? "ST_BWD" : "ST_NONE",
              (double)ms * 1e3);
+    h->debug_name = name;
+    if (build_name) *build_name = h->debug_name.c_str();
+    return done(MZL_OK, "");
+}
+
+// diagnostic (tests): ONE launch group of the Atari representation outside its stride-1 convs (mz_learn_conv_host.h, mzl_stage_call), through the
+// AtariRun members the update itself calls -- s2_fwd / s2_dgrad (gather, tap-set convs on copies packed by k_lc_pack_par at the handle's par_compact,
+// accumulation, scatter), pool_fwd / pool_bwd / relu_bwd, entry / entry12 / launch_entry, launch_normalize, gather, scatter.  Every device pointer is
+// a temporary buffer of this call (NULL stream), outputs and intermediate tiles are preset to NaN bits; the handle's weights, saved tensors and
+// switches are as before when it returns.  A bad shape is refused before any launch; a tap set the dispatcher has no build for ends the call with
+// nothing launched after it.  *build_name stays valid until the next call and says what ran.
+int mzlc_debug_atari_stage(mzlc_learner* h, mzl_stage_call* c, const char** build_name, std::string& err) {
+    const int op = c->op, B = c->batch, C = c->cin, H = c->H, W = c->W;
+    auto bad = [&](const char* m) { err = m; return (int)MZL_E_INVALID; };
+    if (op < MZL_STAGE_S2_FWD || op > MZL_STAGE_SCATTER) return bad("op: not one of MZL_STAGE_*");
+    const bool s2 = op == MZL_STAGE_S2_FWD || op == MZL_STAGE_S2_DGRAD, gs = op == MZL_STAGE_GATHER || op == MZL_STAGE_SCATTER, pool = op == MZL_STAGE_POOL_FWD || op == MZL_STAGE_POOL_BWD;
+    if ((s2 || gs) && !h->atari) return bad("op: s2_fwd, s2_dgrad, gather and scatter need an Atari handle (MZL_NET_ATARI): the tile geometries are its own");
+    if (B < 1 || B > 256) return bad("batch: must be in [1, 256]");
+    if (C < 1 || C > 1024) return bad("C (cin): must be in [1, 1024]");
+    if (s2 && (c->cout < 1 || c->cout > 1024)) return bad("cout: must be in [1, 1024]");
+    if (H < 1 || W < 1 || H > 96 || W > 96) return bad("H, W: must be in [1, 96]");
+    if (!c->in0) return bad("in0: null argument");
+    if (!c->out) return bad("out: null argument");
+    if (s2 && !c->weight) return bad("weight: null argument");
+    const int stride = s2 ? 2 : (gs ? c->stride : 1);
+    if (gs && stride != 1 && stride != 2) return bad("stride: must be 1 or 2");
+    if (gs && (c->py < 0 || c->py >= stride || c->px < 0 || c->px >= stride)) return bad("origin (py, px): must lie in [0, stride)");
+    if ((s2 || gs) && H % TILE) return bad("H: the tiled plane's height must be a multiple of 12");
+    if ((s2 || gs) && (stride * H > 96 || stride * W > 96)) return bad("H, W: the strided plane must stay within 96 x 96");
+    if (pool && ((H | W) & 1)) return bad("H, W: odd source sizes (the pools halve an even plane)");
+    const int hw = H * W, cpad = pad16(C);
+    if (op == MZL_STAGE_RELU_BWD && !c->in1) return bad("in1 (x): null argument");
+    if (op == MZL_STAGE_ENTRY) {
+        if (!c->in3) return bad("in3 (partner): null argument");
+        if (!c->stats) return bad("stats: null argument");
+        if (c->launcher < MZL_ENTRY_ATARI || c->launcher > MZL_ENTRY_REP12) return bad("launcher: must be 0 (atari), 1 (tower) or 2 (rep12)");
+        if (c->launcher == MZL_ENTRY_TOWER && hw != h->hw) return bad("hw (H, W): launcher tower runs launch_entry, whose grid is cut for the handle's own hw");
+        if (c->launcher == MZL_ENTRY_REP12 && (c->in1 || !c->in2)) return bad("in1 (gs), in2 (extra): launcher rep12 takes extra and no gs");
+    }
+    if (op == MZL_STAGE_GATHER) {
+        if (c->mode != IN_IDENT && c->mode != IN_BNRELU && c->mode != IN_BNBWD) return bad("mode: must be 0 (ident), 1 (bnrelu) or 2 (bnbwd)");
+        if (c->mode != IN_IDENT && !c->coef) return bad("coef: null argument (modes bnrelu and bnbwd)");
+        if (c->mode == IN_BNBWD && !c->in1) return bad("in1 (src1): null argument (mode bnbwd)");
+    }
+    if (op == MZL_STAGE_SCATTER && c->want_stats && !c->stats) return bad("stats: null argument (want_stats)");
+    const int cmax = s2 && c->cout > C ? c->cout : C;
+    if ((size_t)B * cmax * stride * H * stride * W * sizeof(float) > ((size_t)1 << 30)) return bad("batch: the planes of the call must stay within 1 GiB");
+    if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
+    hipStream_t st = nullptr;
+    const AtariRun R{h, B, st};
+    int tw = TILE, nt = 0;
+    if (s2 || gs) {
+        tw = R.tile_w(W);
+        if (W % tw) return bad("W: the tiled plane's width must divide into tiles of 12 columns (or 16: widths that are a multiple of 16 and at least 48)");
+        nt = R.ntiles(H, W);
+        if (s2 && conv_lds(R.tgeom(W).qstride, pad16(op == MZL_STAGE_S2_FWD ? C : c->cout)) > 160 * 1024) return bad("cin / cout: the conv's input channels do not fit its LDS slab");
+    }
+    const bool sv_bad = h->bad_dispatch;
+    std::vector<void*> tmp;
+    auto A = [&](void** p, size_t bytes, int fill = 0) {
+        if (hipMalloc(p, bytes + 256) != hipSuccess) return false;
+        tmp.push_back(*p);
+        return hipMemset(*p, fill, bytes + 256) == hipSuccess;
+    };
+    auto done = [&](int rc, const char* m) {
+        (void)hipDeviceSynchronize();
+        for (void* p : tmp) (void)hipFree(p);
+        h->bad_dispatch = sv_bad;
+        if (rc != MZL_OK) { err = m; (void)hipGetLastError(); }
+        return rc;
+    };
+    auto up = [&](float** d, const float* src, size_t n) { return A((void**)d, n * 4) && hipMemcpy(*d, src, n * 4, hipMemcpyHostToDevice) == hipSuccess; };
+    auto nanbuf = [&](float** d, size_t n) { return A((void**)d, n * 4, 0xff); };
+    auto down = [&](float* dst, const float* d, size_t n) { return hipMemcpy(dst, d, n * 4, hipMemcpyDeviceToHost) == hipSuccess; };
+    auto ran = [&]() { return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess; };
+    const size_t ts2 = (size_t)(TILE + 2) * (tw + 2), n_plane = (size_t)B * C * hw;
+    char name[320];
+    name[0] = 0;
+    c->groups = 0;
+    h->bad_dispatch = false;
+    float *d_in0 = nullptr, *d_in1 = nullptr, *d_in2 = nullptr, *d_in3 = nullptr, *d_out = nullptr, *d_stats = nullptr;
+    if (s2) {
+        const bool dg = op == MZL_STAGE_S2_DGRAD;
+        const int cin = C, cout = c->cout, k_in = dg ? cout : cin, k_out = dg ? cin : cout;  // the conv's own input / output channels
+        const size_t n_w = (size_t)cout * cin * 9, per = (size_t)cdiv(k_out, 16) * cdiv(k_in, 16) * 9 * 256;
+        const size_t n_x = dg ? (size_t)B * cout * hw : (size_t)B * cin * 4 * hw, n_y = dg ? (size_t)B * cin * 4 * hw : (size_t)B * cout * hw;
+        float *d_w = nullptr, *d_packed = nullptr, *d_ta = nullptr, *d_tb = nullptr;
+        void* d_jobs = nullptr;
+        std::vector<LcPackPar> pj(4);
+        int w_off[4];
+        for (int pq = 0; pq < 4; pq++) {
+            LcPackPar j{};
+            w_off[pq] = (int)(pq * per);
+            j.w_off = 0; j.cout = cout; j.cin = cin; j.dst_off = w_off[pq]; j.n_cb = cdiv(k_in, 16); j.co_tiles = cdiv(k_out, 16); j.transpose = dg ? 1 : 0; j.compact = h->par_compact ? 1 : 0;
+            par_tapmap(pq >> 1, pq & 1, dg, j.tapmap);
+            pj[pq] = j;
+        }
+        bool ok = up(&d_w, c->weight, n_w) && A((void**)&d_packed, 4 * per * 4) && up(&d_in0, c->in0, n_x) && nanbuf(&d_ta, (size_t)B * nt * pad16(k_in) * ts2) &&
+                  nanbuf(&d_tb, (size_t)B * nt * pad16(k_out) * ts2) && nanbuf(&d_out, n_y) && A(&d_jobs, 4 * sizeof(LcPackPar));
+        ok = ok && hipMemcpy(d_jobs, pj.data(), 4 * sizeof(LcPackPar), hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        hipLaunchKernelGGL(k_lc_pack_par, dim3(64, 4), dim3(256), 0, st, reinterpret_cast<const LcPackPar*>(d_jobs), d_w, d_packed);
+        bool built;
+        if (!dg) built = R.s2_fwd(d_packed, w_off, d_in0, cin, cout, H, W, d_ta, d_tb, d_out);
+        else {
+            R.gather(d_in0, nullptr, nullptr, IN_IDENT, cout, H, W, H, W, 1, 1, 0, 0, 0, d_ta);  // dy tiles with halo, as atari_rep_bwd cuts them
+            built = R.s2_dgrad(d_packed, w_off, d_ta, cin, cout, H, W, d_tb, d_out);
+        }
+        const int npt = R.tgeom(W).npt;
+        if (!built || h->bad_dispatch) {
+            snprintf(name, sizeof(name), "no kernel build: launch_conv_tapmask has none for NPT=%d (tile 12x%d) and the %s tap sets in the compact form", npt, tw,
+                     dg ? "data-gradient" : "forward");
+            h->debug_name = name;
+            return done(MZL_E_INVALID, h->debug_name.c_str());
+        }
+        if (!ran()) return done(MZL_E_HIP, "the stride-2 conv failed to launch or run");
+        if (!down(c->out, d_out, n_y)) return done(MZL_E_HIP, "hipMemcpy failed");
+        int m[4];
+        for (int pq = 0; pq < 4; pq++) m[pq] = h->par_compact ? par_tapmask(pq >> 1, pq & 1, dg) : 0x1ff;
+        snprintf(name, sizeof(name), "f32 k_lc_conv %s NPT=%d tile=12x%d tiles=%d compact=%d masks=0x%03x,0x%03x,0x%03x,0x%03x", dg ? "s2_dgrad" : "s2_fwd", npt, tw, nt,
+                 h->par_compact ? 1 : 0, m[0], m[1], m[2], m[3]);
+    } else if (pool) {
+        const bool fwd = op == MZL_STAGE_POOL_FWD;
+        const size_t n_small = n_plane / 4;
+        if (!(up(&d_in0, c->in0, fwd ? n_plane : n_small) && nanbuf(&d_out, fwd ? n_small : n_plane))) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        if (fwd) R.pool_fwd(d_in0, d_out, C, H, W);
+        else R.pool_bwd(d_in0, d_out, C, H, W);
+        if (!ran()) return done(MZL_E_HIP, "the pool failed to launch or run");
+        if (!down(c->out, d_out, fwd ? n_small : n_plane)) return done(MZL_E_HIP, "hipMemcpy failed");
+        snprintf(name, sizeof(name), "%s %dx%d -> %dx%d", fwd ? "k_lc_pool_fwd" : "k_lc_pool_bwd", fwd ? H : H / 2, fwd ? W : W / 2, fwd ? H / 2 : H, fwd ? W / 2 : W);
+    } else if (op == MZL_STAGE_RELU_BWD) {
+        if (!(up(&d_in0, c->in0, n_plane) && up(&d_in1, c->in1, n_plane) && nanbuf(&d_out, n_plane))) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        R.relu_bwd(d_in0, d_in1, d_out, (long long)n_plane);
+        if (!ran()) return done(MZL_E_HIP, "k_lc_relu_bwd failed to launch or run");
+        if (!down(c->out, d_out, n_plane)) return done(MZL_E_HIP, "hipMemcpy failed");
+        snprintf(name, sizeof(name), "k_lc_relu_bwd n=%lld", (long long)n_plane);
+    } else if (op == MZL_STAGE_ENTRY) {
+        const size_t n_stat = (size_t)B * cdiv(hw, 32) * cpad * 2;
+        bool ok = up(&d_in0, c->in0, n_plane) && up(&d_in3, c->in3, n_plane) && nanbuf(&d_out, n_plane) && nanbuf(&d_stats, n_stat);
+        if (c->in1) ok = ok && up(&d_in1, c->in1, n_plane);
+        if (c->in2) ok = ok && up(&d_in2, c->in2, n_plane);
+        if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        int groups;
+        const char* what;
+        if (c->launcher == MZL_ENTRY_ATARI) {
+            groups = R.entry(d_in0, d_in1, c->scale, d_in2, d_in3, d_out, C, hw, d_stats);
+            what = (!c->in1 && c->in2 && hw % 4 == 0) ? "AtariRun::entry k_lc_entry_plain" : "AtariRun::entry k_lc_entry";
+        } else if (c->launcher == MZL_ENTRY_REP12) {
+            groups = R.entry12(d_in0, d_in2, d_in3, d_out, C, hw, d_stats);
+            what = "AtariRun::entry12 k_lc_entry";
+        } else {
+            LcEntry e{};
+            e.x = d_in0; e.gs = d_in1; e.extra = d_in2; e.partner = d_in3; e.dz = d_out; e.stat_part = d_stats; e.scale = c->scale; e.B = B; e.C = C; e.hw = hw; e.cpad = cpad;
+            launch_entry(h, e, st);
+            groups = entry_groups(h, B);
+            what = "launch_entry k_lc_entry";
+        }
+        if (groups < 1 || (size_t)groups * cpad * 2 > n_stat) return done(MZL_E_STATE, "internal: more statistic groups than chunks");
+        if (!ran()) return done(MZL_E_HIP, "the entry kernel failed to launch or run");
+        if (!down(c->out, d_out, n_plane) || !down(c->stats, d_stats, (size_t)groups * cpad * 2)) return done(MZL_E_HIP, "hipMemcpy failed");
+        c->groups = groups;
+        const int cpt = cdiv(C, 8);
+        snprintf(name, sizeof(name), "%s CPT=%d groups=%d", what, cpt <= 2 ? 2 : cpt <= 8 ? 8 : cpt <= 16 ? 16 : 32, groups);
+    } else if (op == MZL_STAGE_NORMALIZE) {
+        if (!(up(&d_in0, c->in0, n_plane) && nanbuf(&d_out, n_plane))) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        launch_normalize(d_in0, d_out, B, C, hw, st);
+        if (!ran()) return done(MZL_E_HIP, "k_lc_normalize failed to launch or run");
+        if (!down(c->out, d_out, n_plane)) return done(MZL_E_HIP, "hipMemcpy failed");
+        const int cpt = cdiv(C, 8);
+        snprintf(name, sizeof(name), "k_lc_normalize CPT=%d", cpt <= 2 ? 2 : cpt <= 8 ? 8 : cpt <= 16 ? 16 : 32);
+    } else if (op == MZL_STAGE_GATHER) {
+        const size_t n_src = n_plane * stride * stride, n_t = (size_t)B * nt * C * ts2;
+        float* d_coef = nullptr;
+        bool ok = up(&d_in0, c->in0, n_src) && nanbuf(&d_out, n_t);
+        if (c->in1) ok = ok && up(&d_in1, c->in1, n_src);
+        if (c->coef) {
+            std::vector<float> t((size_t)3 * cpad, 0.0f);
+            for (int k = 0; k < 3; k++)
+                for (int ch = 0; ch < C; ch++) t[(size_t)k * cpad + ch] = c->coef[(size_t)k * C + ch];
+            ok = ok && up(&d_coef, t.data(), t.size());
+        }
+        if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        R.gather(d_in0, d_in1, d_coef, c->mode, C, H, W, stride * H, stride * W, stride, stride, c->py, c->px, c->inner_only ? 1 : 0, d_out);
+        if (!ran()) return done(MZL_E_HIP, "k_lc_tile_gather failed to launch or run");
+        if (!down(c->out, d_out, n_t)) return done(MZL_E_HIP, "hipMemcpy failed");
+        c->groups = B * nt;
+        static const bool xcd = !getenv("MZLC_NO_GATHER_XCD");
+        snprintf(name, sizeof(name), "k_lc_tile_gather tile=12x%d tiles=%d mode=%d stride=%d origin=(%d,%d) inner_only=%d remap=%d chunks=%d", tw, B * nt, c->mode, stride, c->py, c->px,
+                 c->inner_only ? 1 : 0, (xcd && (B * nt) % 8 == 0) ? 1 : 0, cdiv(C * (int)ts2, 1024));
+    } else {  // MZL_STAGE_SCATTER
+        const size_t n_dst = n_plane * stride * stride, n_t = (size_t)B * nt * C * (c->src_inner ? (size_t)TILE * tw : ts2), n_stat = (size_t)B * cdiv(hw, 32) * cpad * 4;
+        bool ok = up(&d_in0, c->in0, n_t) && nanbuf(&d_out, n_dst);
+        if (c->in1) ok = ok && up(&d_in1, c->in1, n_dst);
+        if (c->want_stats) ok = ok && nanbuf(&d_stats, n_stat);
+        if (!ok) return done(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
+        const int groups = R.scatter(d_in0, C, H, W, d_out, stride * H, stride * W, stride, stride, c->py, c->px, d_in1, d_stats, c->src_inner != 0);
+        if ((size_t)groups * cpad * 4 > n_stat) return done(MZL_E_STATE, "internal: more statistic groups than chunks");
+        if (!ran()) return done(MZL_E_HIP, "k_lc_tile_scatter failed to launch or run");
+        if (!down(c->out, d_out, n_dst) || (c->want_stats && !down(c->stats, d_stats, (size_t)groups * cpad * 4))) return done(MZL_E_HIP, "hipMemcpy failed");
+        c->groups = c->want_stats ? groups : 0;
+        const int cpt = cdiv(C, 8);
+        snprintf(name, sizeof(name), "k_lc_tile_scatter CPT=%d tile=12x%d stride=%d origin=(%d,%d) src_inner=%d skip=%d stats=%d", cpt <= 2 ? 2 : cpt <= 8 ? 8 : cpt <= 16 ? 16 : 32, tw,
+                 stride, c->py, c->px, c->src_inner ? 1 : 0, c->in1 ? 1 : 0, c->want_stats ? 1 : 0);
+    }
     h->debug_name = name;
     if (build_name) *build_name = h->debug_name.c_str();
     return done(MZL_OK, "");

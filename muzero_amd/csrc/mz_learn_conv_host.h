@@ -53,6 +53,42 @@ struct mzl_tile_call {
 };
 int mzlc_debug_conv_tile(mzlc_learner* h, mzl_tile_call* c, const char** build_name, std::string& err);
 
+// diagnostic (tests): ONE launch group of the Atari representation outside its stride-1 convs (mzl_debug_atari_stage; exported, not part of
+// include/mzlearner.h), through the AtariRun members the update calls.  Host pointers throughout; null = absent; outputs are preset to NaN bits.
+//   S2_FWD    weight [cout][cin][3][3], in0 = x [B][cin][2H][2W]  -> out = y [B][cout][H][W]     (gather, k_lc_pack_par, tap-set convs, accumulate, scatter)
+//   S2_DGRAD  weight, in0 = dy [B][cout][H][W]                    -> out = dx [B][cin][2H][2W]   (transposed pack, par_row_d taps, the parity scatter)
+//   POOL_FWD  in0 [B][cin][H][W] (H, W even)                      -> out [B][cin][H/2][W/2]
+//   POOL_BWD  in0 = gout [B][cin][H/2][W/2]                       -> out = gin [B][cin][H][W]
+//   RELU_BWD  in0 = g, in1 = x, both B cin H W elements           -> out = dz
+//   ENTRY     in0 = x, in1 = gs | null, in2 = extra | null, in3 = partner, all [B][cin][H W]; scale; launcher
+//                                                                 -> out = dz, stats [groups][pad16(cin)][2], groups
+//   NORMALIZE in0 = x [B][cin][H W]                               -> out = s
+//   GATHER    in0 = src0 (in1 = src1: IN_BNBWD) [B][cin][stride H][stride W], coef [3][cin] | null, mode (IN_* of mz_learn_conv.h: 0 ident, 1 bnrelu,
+//             2 bnbwd), stride 1 | 2, origin (py, px), inner_only  -> out = tiles [B nty ntx][cin][14][tw + 2]
+//   SCATTER   in0 = tiles [B nty ntx][cin][14][tw + 2] (src_inner: [..][cin][12][tw]), in1 = skip [B][cin][stride H][stride W] | null, stride, origin,
+//             want_stats                                          -> out = plane [B][cin][stride H][stride W] (NaN bits where this parity does not
+//             write), stats [groups][pad16(cin)][4] (pivot, sum, sum of squares, count), groups
+// S2_*, GATHER and SCATTER need an Atari handle (its tile geometries and switches: wide tiles, par_compact); the others run on any conv handle.
+enum { MZL_STAGE_S2_FWD = 0, MZL_STAGE_S2_DGRAD = 1, MZL_STAGE_POOL_FWD = 2, MZL_STAGE_POOL_BWD = 3, MZL_STAGE_RELU_BWD = 4, MZL_STAGE_ENTRY = 5,
+       MZL_STAGE_NORMALIZE = 6, MZL_STAGE_GATHER = 7, MZL_STAGE_SCATTER = 8 };
+enum { MZL_ENTRY_ATARI = 0, MZL_ENTRY_TOWER = 1, MZL_ENTRY_REP12 = 2 };  // AtariRun::entry | launch_entry (H W = the handle's hw) | AtariRun::entry12
+struct mzl_stage_call {
+    int32_t op;            // MZL_STAGE_*
+    int32_t batch, cin, cout, H, W;
+    int32_t mode, stride, py, px, inner_only, src_inner, want_stats, launcher;
+    int32_t groups;        // out: rows of `stats`
+    float scale;           // ENTRY: on gs
+    const float* weight;
+    const float* in0;
+    const float* in1;
+    const float* in2;
+    const float* in3;
+    const float* coef;
+    float* out;
+    float* stats;          // sized by the caller for the most groups the op can write: B * ceil(H W / 32)
+};
+int mzlc_debug_atari_stage(mzlc_learner* h, mzl_stage_call* c, const char** build_name, std::string& err);
+
 // diagnostic (tests): ONE layer's weight gradient (mzl_debug_wgrad; exported, not part of include/mzlearner.h).  Host pointers throughout.
 struct mzl_wgrad_layer {
     const float* dz;        // [nsrc][B][cout][h][w]   (nsrc = 1 outside mode `steps`)

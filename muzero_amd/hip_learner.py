@@ -96,6 +96,15 @@ class MzlTileCall(C.Structure):
                [(n, C.c_void_p) for n in ('weight', 'in_', 'skip', 'mask', 'mcoef', 'partner', 'out', 'part')]
 
 
+class MzlStageCall(C.Structure):
+    """mzl_stage_call (csrc/mz_learn_conv_host.h): the host operands of mzl_debug_atari_stage."""
+    _fields_ = [(n, C.c_int32) for n in ('op', 'batch', 'cin', 'cout', 'H', 'W', 'mode', 'stride', 'py', 'px', 'inner_only', 'src_inner', 'want_stats', 'launcher',
+                                         'groups')] + [('scale', C.c_float)] + \
+               [(n, C.c_void_p) for n in ('weight', 'in0', 'in1', 'in2', 'in3', 'coef', 'out', 'stats')]
+
+
+STAGE_OPS = {'s2_fwd': 0, 's2_dgrad': 1, 'pool_fwd': 2, 'pool_bwd': 3, 'relu_bwd': 4, 'entry': 5, 'normalize': 6, 'gather': 7, 'scatter': 8}
+ENTRY_LAUNCHERS = {'atari': 0, 'tower': 1, 'rep12': 2}
 TILE_ROUTES = {'plane': 0, 'inner': 1, 'whole': 2}
 WGRAD_MODES = {'plain': 0, 'pair': 1, 'steps': 2, 'ring': 3}
 
@@ -175,6 +184,8 @@ def load_library():
     if hasattr(L, 'mzl_debug_conv_tile'):
         L.mzl_debug_conv_tile.argtypes = [vp, C.POINTER(MzlTileCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
         L.mzl_debug_precisions.argtypes = [vp, C.POINTER(i32)]
+    if hasattr(L, 'mzl_debug_atari_stage'):
+        L.mzl_debug_atari_stage.argtypes = [vp, C.POINTER(MzlStageCall), C.POINTER(C.c_char_p)]  # diagnostic: exported, not declared
     if hasattr(L, 'mzl_debug_heads'):
         L.mzl_debug_heads.argtypes = [vp, C.POINTER(MzlHeadsCall)]  # diagnostic: exported, not declared
     _lib = L
@@ -301,6 +312,7 @@ class HipLearner:
             cfg = MzlConfig(in_dim, spec['num_actions'], spec['num_planes'], spec['hidden_dim'], spec['value_support_size'], spec['reward_support_size'],
                             unroll_steps, max_batch, grad_slices, NET_MLP, 0, 0, 0, 0, self.conv_precision)
         _check(L.mzl_create(C.byref(cfg), self.device.index or 0, C.byref(self._h)))
+        self._wide_tiles = 'MZLC_NO_WIDE_TILES' not in os.environ  # (read by the library at create; debug_atari_stage sizes its tile arrays by it)
         if self.wgrad_precision:  # (the default never calls the setter: the handle is what mzl_create made)
             _check(L.mzl_set_wgrad_precision(self._h, self.wgrad_precision))
         # (the same: the default, 0, leaves the handle as mzl_create made it; a value given by NAME on an Atari net is passed on even when it is
@@ -610,6 +622,127 @@ class HipLearner:
         _check(load_library().mzl_debug_conv_tile(self._h, C.byref(call), C.byref(name)))
         name = (name.value or b'').decode()
         return (out, name, part[:call.groups]) if want_part else (out, name)
+
+    def debug_atari_stage(self, op: str, **a):
+        """Diagnostic (tests): ONE launch group of the Atari representation outside its stride-1 convs, through the members the update calls
+        (mzl_debug_atari_stage).  Host arrays in, (result, build name) or (result, build name, statistics partials) out:
+          's2_fwd'    weight [cout, cin, 3, 3], x [B, cin, 2H, 2W]                     -> y [B, cout, H, W]
+          's2_dgrad'  weight, dy [B, cout, H, W]                                       -> dx [B, cin, 2H, 2W]
+          'pool_fwd'  x [B, C, ih, iw]                                                 -> [B, C, ih / 2, iw / 2]
+          'pool_bwd'  g [B, C, ih / 2, iw / 2]                                         -> [B, C, ih, iw]
+          'relu_bwd'  g, x [B, C, H, W]                                                -> dz
+          'entry'     x [B, C, H, W], gs=None, extra=None, partner, scale=1.0, launcher='atari' | 'tower' | 'rep12'
+                                                                                       -> dz, name, partials [groups, pad16(C), 2]
+          'normalize' x [B, C, H, W]                                                   -> s
+          'gather'    src0 [B, C, stride H, stride W], src1=None, coef=None [3, C], mode='ident' | 'bnrelu' | 'bnbwd', stride=1, origin=(0, 0),
+                      inner_only=False                                                 -> tiles [B nty ntx, C, 14, tw + 2]
+          'scatter'   tiles [B nty ntx, C, 14, tw + 2] (src_inner: [.., C, 12, tw]), H, W (the tiled plane), stride=1, origin=(0, 0), skip=None,
+                      src_inner=False, want_stats=False                                -> plane [B, C, stride H, stride W] (NaN where this parity
+                                                                                          does not write)[, name, partials [groups, pad16(C), 4]]"""
+        if op not in STAGE_OPS:
+            raise ValueError(f"op must be one of {sorted(STAGE_OPS)}, not {op!r}")
+        f32 = np.float32
+        keep = []
+
+        def arr(v, ndim=4):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, f32)
+            if v.ndim != ndim:
+                raise LearnerError(f'mzl_debug_atari_stage: {op}: an operand of {v.ndim} dimensions, expected {ndim}')
+            keep.append(v)
+            return v
+
+        def ptr(v):
+            return None if v is None else v.ctypes.data_as(C.c_void_p)
+
+        def same(v, ref, what):
+            if v is not None and v.shape != ref.shape:
+                raise LearnerError(f'mzl_debug_atari_stage: {op}: {what} of shape {v.shape}, expected {ref.shape}')
+            return v
+
+        call = MzlStageCall()
+        call.op, call.scale, call.stride = STAGE_OPS[op], 1.0, 1
+        stats = None
+        if op in ('s2_fwd', 's2_dgrad'):
+            w, x = arr(a.pop('weight')), arr(a.pop('x' if op == 's2_fwd' else 'dy'))
+            if tuple(w.shape[2:]) != (3, 3) or x.shape[1] != w.shape[1 if op == 's2_fwd' else 0]:
+                raise LearnerError(f'mzl_debug_atari_stage: {op}: weight {w.shape} does not fit the plane {x.shape}')
+            B, _, h, wd = x.shape
+            if op == 's2_fwd':
+                if h % 2 or wd % 2:
+                    raise LearnerError(f'mzl_debug_atari_stage: s2_fwd: x: odd source sizes {h} x {wd}')
+                H, W, out = h // 2, wd // 2, np.zeros((B, w.shape[0], h // 2, wd // 2), f32)
+            else:
+                H, W, out = h, wd, np.zeros((B, w.shape[1], 2 * h, 2 * wd), f32)
+            call.batch, call.cin, call.cout, call.H, call.W = B, w.shape[1], w.shape[0], H, W
+            call.weight, call.in0 = ptr(w), ptr(x)
+        elif op in ('pool_fwd', 'pool_bwd'):
+            x = arr(a.pop('x' if op == 'pool_fwd' else 'g'))
+            B, Cn, h, wd = x.shape
+            H, W = (h, wd) if op == 'pool_fwd' else (2 * h, 2 * wd)
+            out = np.zeros((B, Cn, H // 2, W // 2) if op == 'pool_fwd' else (B, Cn, H, W), f32)
+            call.batch, call.cin, call.H, call.W, call.in0 = B, Cn, H, W, ptr(x)
+        elif op == 'relu_bwd':
+            g = arr(a.pop('g'))
+            x = same(arr(a.pop('x')), g, 'x')
+            out = np.zeros(g.shape, f32)
+            (call.batch, call.cin, call.H, call.W), call.in0, call.in1 = g.shape, ptr(g), ptr(x)
+        elif op in ('entry', 'normalize'):
+            x = arr(a.pop('x'))
+            out = np.zeros(x.shape, f32)
+            (call.batch, call.cin, call.H, call.W), call.in0 = x.shape, ptr(x)
+            if op == 'entry':
+                launcher = a.pop('launcher', 'atari')
+                if launcher not in ENTRY_LAUNCHERS:
+                    raise ValueError(f"launcher must be one of {sorted(ENTRY_LAUNCHERS)}, not {launcher!r}")
+                call.launcher, call.scale = ENTRY_LAUNCHERS[launcher], float(a.pop('scale', 1.0))
+                call.in1, call.in2 = ptr(same(arr(a.pop('gs', None)), x, 'gs')), ptr(same(arr(a.pop('extra', None)), x, 'extra'))
+                call.in3 = ptr(same(arr(a.pop('partner', None)), x, 'partner'))
+                stats = np.zeros((x.shape[0] * -(-(x.shape[2] * x.shape[3]) // 32), (x.shape[1] + 15) // 16 * 16, 2), f32)
+        elif op == 'gather':
+            src0 = arr(a.pop('src0'))
+            src1 = same(arr(a.pop('src1', None)), src0, 'src1')
+            B, Cn, h, wd = src0.shape
+            mode, stride, (py, px) = a.pop('mode', 'ident'), int(a.pop('stride', 1)), a.pop('origin', (0, 0))
+            if mode not in ('ident', 'bnrelu', 'bnbwd'):
+                raise ValueError(f"mode must be 'ident', 'bnrelu' or 'bnbwd', not {mode!r}")
+            if stride not in (1, 2) or h % stride or wd % stride:
+                raise LearnerError(f'mzl_debug_atari_stage: gather: stride {stride} on a source of odd sizes or not 1 | 2: {h} x {wd}')
+            coef = arr(a.pop('coef', None), 2)
+            if coef is not None and coef.shape != (3, Cn):
+                raise LearnerError(f'mzl_debug_atari_stage: gather: coef of shape {coef.shape}, expected {(3, Cn)}')
+            H, W = h // stride, wd // stride
+            tw = 16 if self.debug_atari_wide_tiles(W) else 12
+            out = np.zeros((B * (H // 12) * (W // tw), Cn, 14, tw + 2), f32)
+            call.batch, call.cin, call.H, call.W, call.mode, call.stride, call.py, call.px = B, Cn, H, W, IN_MODES[mode], stride, int(py), int(px)
+            call.inner_only, call.in0, call.in1, call.coef = int(bool(a.pop('inner_only', False))), ptr(src0), ptr(src1), ptr(coef)
+        else:  # scatter
+            tiles = arr(a.pop('tiles'))
+            H, W, stride, (py, px) = int(a.pop('H')), int(a.pop('W')), int(a.pop('stride', 1)), a.pop('origin', (0, 0))
+            src_inner, want_stats = bool(a.pop('src_inner', False)), bool(a.pop('want_stats', False))
+            Cn = tiles.shape[1]
+            tw = 16 if self.debug_atari_wide_tiles(W) else 12
+            B = tiles.shape[0] // max(1, (H // 12) * (W // tw))
+            if H < 12 or W < 12 or stride not in (1, 2) or tiles.shape != (B * (H // 12) * (W // tw), Cn) + ((12, tw) if src_inner else (14, tw + 2)) or B < 1:
+                raise LearnerError(f'mzl_debug_atari_stage: scatter: tiles of shape {tiles.shape} do not cut a {H} x {W} plane (tile width {tw})')
+            out = np.zeros((B, Cn, stride * H, stride * W), f32)
+            skip = same(arr(a.pop('skip', None)), out, 'skip')
+            call.batch, call.cin, call.H, call.W, call.stride, call.py, call.px = B, Cn, H, W, stride, int(py), int(px)
+            call.src_inner, call.want_stats, call.in0, call.in1 = int(src_inner), int(want_stats), ptr(tiles), ptr(skip)
+            if want_stats:
+                stats = np.zeros((B * -(-(H * W) // 32), (Cn + 15) // 16 * 16, 4), f32)
+        if a:
+            raise TypeError(f'debug_atari_stage({op!r}): unexpected arguments {sorted(a)}')
+        call.out, call.stats = ptr(out), ptr(stats)
+        name = C.c_char_p()
+        _check(load_library().mzl_debug_atari_stage(self._h, C.byref(call), C.byref(name)))
+        name = (name.value or b'').decode()
+        return (out, name) if stats is None else (out, name, stats[:call.groups])
+
+    def debug_atari_wide_tiles(self, W: int) -> bool:
+        """AtariRun::tile_w: does this handle cut a plane of width W into 16-column tiles?  (MZLC_NO_WIDE_TILES=1 at create: never.)"""
+        return self._wide_tiles and W % 16 == 0 and W // 16 >= 3
 
     def debug_precisions(self):
         """Diagnostic (tests): (tower_precision, stage_precision, wgrad_precision) as the HANDLE holds them (conv nets)."""
