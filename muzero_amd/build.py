@@ -19,7 +19,11 @@ LIB_PATH = os.path.join(LIB_DIR, 'libmzplanner_hip.so')
 SOURCES = ['planner.hip']
 LEARNER_LIB_PATH = os.path.join(LIB_DIR, 'libmzlearner_hip.so')
 LEARNER_SOURCES = ['learner.hip', 'learner_conv.hip', 'learner_replay.hip']
-LEARNER_FILES = ('learner.hip', 'learner_conv.hip', 'learner_replay.hip', 'mz_learn.h', 'mz_learn_conv.h', 'mz_learn_conv_split.h', 'mz_learn_conv_split_wgrad.h', 'mz_learn_conv_host.h', 'mzlearner.h')  # what only the learner library is compiled from (besides mz_device.h)
+# what only the learner library is compiled from (besides the shared mz_device.h and mz_split3.h): the ONE list -- _deps() leaves these out of the planner's
+# fingerprint, _learner_deps() is made from them.  A learner file missing here would enter source_fingerprint() and orphan the committed planner profiles.
+LEARNER_HEADER = 'mzlearner.h'  # (in include/, the others in csrc/)
+LEARNER_FILES = ('learner.hip', 'learner_conv.hip', 'learner_replay.hip', 'mz_learn.h', 'mz_learn_conv.h', 'mz_learn_conv_split.h', 'mz_learn_conv_split_wgrad.h', 'mz_learn_conv_host.h',
+                 'mz_learn_conv_debug.h', LEARNER_HEADER)
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in ordinary VGPRs where they fit.  The search kernels read every accumulator
 # with VALU code right after the layer (ReLU, normalisation, partial sums); in the default AGPR form each of those reads is a
 # v_accvgpr_read first (96 per simulation in k_search_fast: +2 % on C2, measured), and no kernel of this library needs the
@@ -38,10 +42,10 @@ def _deps():
 
 
 def _learner_deps():
-    return [os.path.join(CSRC, 'learner.hip'), os.path.join(CSRC, 'learner_conv.hip'), os.path.join(CSRC, 'learner_replay.hip'), os.path.join(CSRC, 'mz_learn.h'), os.path.join(CSRC, 'mz_learn_conv.h'),
-            os.path.join(CSRC, 'mz_learn_conv_split.h'), os.path.join(CSRC, 'mz_learn_conv_split_wgrad.h'), os.path.join(CSRC, 'mz_learn_conv_host.h'), os.path.join(CSRC, 'mz_device.h'),
-            os.path.join(CSRC, 'mz_split3.h'),  # (shared with the planner's split conv: the one definition of the float32 -> three-bf16 split)
-            os.path.join(HERE, '..', 'include', 'mzlearner.h'), os.path.abspath(__file__)]
+    """Every file the learner library is compiled from: LEARNER_FILES, the two headers it shares with the planner (mz_split3.h: the one definition of the
+    float32 -> three-bf16 split), the public C header, this script."""
+    return [os.path.join(CSRC, f) for f in LEARNER_FILES if f != LEARNER_HEADER] + [os.path.join(CSRC, 'mz_device.h'), os.path.join(CSRC, 'mz_split3.h')] + \
+        [os.path.join(HERE, '..', 'include', LEARNER_HEADER), os.path.abspath(__file__)]
 
 
 def source_fingerprint():

@@ -1,5 +1,6 @@
 // mz_learn_conv_host.h -- what learner.hip (the C ABI of include/mzlearner.h) calls for net_kind == MZL_NET_BOARD: the conv-net learner of
-// learner_conv.hip over the kernels of mz_learn_conv.h.  Internal to libmzlearner_hip.so.
+// learner_conv.hip over the kernels of mz_learn_conv.h, and the call structs of its diagnostic hooks (mzlc_debug_*, defined in mz_learn_conv_debug.h, which
+// learner_conv.hip includes).  Internal to libmzlearner_hip.so.
 #pragma once
 #include <stdint.h>
 

@@ -5,7 +5,7 @@ a full-size batch always lies within float32 rounding of zero, the float32 pass 
 moves by that element's contribution (tests/test_gpu_atari_learner.py: the 8e-2 / 0.25 bars).  That noise is a property of comparing two
 passes that DECIDE differently, not of the kernels.  Here the reference is told what the HIP pass decided:
 
-  * every ReLU mask of the HIP forward pass, read back through the library's diagnostic hook `mzl_debug_tensor` (csrc/learner_conv.hip):
+  * every ReLU mask of the HIP forward pass, read back through the library's diagnostic hook `mzl_debug_tensor` (csrc/mz_learn_conv_debug.h):
     materialised post-ReLU tensors give `x > 0` directly; where the kernels never materialise the activation (the first ReLU of a residual
     block: relu(a y + b) is formed while the next conv stages its input, mz_learn_conv.h `IN_BNRELU`) the mask is the sign of a y + b from the
     saved raw conv output y and the BatchNorm coefficients (a, b) the kernels applied -- they evaluate fmaf(a, y, b), one rounding, so its
