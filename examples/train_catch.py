@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""End-to-end MuZero with `MuZeroAtariNet` on Catch, a learnable image game that lives on the GPU: device Catch self-play (96 x 96 uint8
+frames rendered on the device, stacked 4 deep into the 8 x 96 x 96 observation of the Atari nets, kept in a compact `frames_u8` record
+ring) -> device epilogue into a `frames_u8` HBM replay -> `DeviceSampler` -> the Atari `HipLearner` step -> weights repacked into the
+planner on the GPU (`Planner.reload` -> `refresh_weights`).  One process, one GPU, event order: every draw happens after the moves before
+it are in the replay, so a seed gives one learning curve.
+
+    python examples/train_catch.py --train-steps 2000 --envs 256
+
+Evaluation: `--eval-envs` host `games.CatchEnv` objects play one lock-step batch with deterministic `Planner.search` (no root noise, the
+most-visited action); the ball columns cover every column equally often.  One JSON line per evaluation with the mean return, its standard
+error, the catch rate, and the uniformly random policy's exact expected return (`games.catch_random_policy_return`) for comparison."""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--train-steps', type=int, default=2000)
+    ap.add_argument('--envs', type=int, default=256)
+    ap.add_argument('--moves-per-iter', type=int, default=4)
+    ap.add_argument('--updates-per-iter', type=int, default=8)
+    ap.add_argument('--batch-size', type=int, default=128)
+    ap.add_argument('--min-replay', type=int, default=4000)
+    ap.add_argument('--replay-size', type=int, default=50000)
+    ap.add_argument('--simulations', type=int, default=25)
+    ap.add_argument('--planes', type=int, default=32)
+    ap.add_argument('--blocks', type=int, default=2)
+    ap.add_argument('--lr', type=float, default=0.002)
+    ap.add_argument('--report-every', type=int, default=200)
+    ap.add_argument('--eval-every', type=int, default=500, help='evaluate every N training steps (and at the end); 0: only at the end')
+    ap.add_argument('--eval-envs', type=int, default=96, help='evaluation episodes, rounded up to a multiple of the 12 columns')
+    ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--tower-precision', choices=('f32', 'bf16x3'), default='f32', help='planner and learner: the fused residual towers')
+    ap.add_argument('--stage-precision', choices=('f32', 'bf16x3'), default='f32', help='learner: the tile path\'s stride-1 convs')
+    ap.add_argument('--record-format', choices=('f32', 'frames_u8'), default='frames_u8', help='the self-play record ring')
+    ap.add_argument('--out', default='')
+    args = ap.parse_args()
+
+    from muzero_amd import games, learner
+    from muzero_amd import planner as pl
+    from muzero_amd.config import make_catch_config
+    from muzero_amd.network import MuZeroAtariNet
+    from muzero_amd.replay import PrioritizedReplay
+
+    torch.manual_seed(args.seed)
+    dev = torch.device('cuda', 0)
+    cfg = make_catch_config(num_training_steps=args.train_steps, batch_size=args.batch_size, min_replay_size=args.min_replay)
+    cfg.num_envs, cfg.num_simulations, cfg.num_planes, cfg.num_res_blocks, cfg.lr_init = args.envs, args.simulations, args.planes, args.blocks, args.lr
+    S, rows, cols = cfg.stack_history, cfg.rows, cfg.cols
+    H, W = cfg.input_shape[1:]
+    net = MuZeroAtariNet(cfg.input_shape, cfg.num_actions, cfg.num_res_blocks, cfg.num_planes, cfg.value_support_size, cfg.reward_support_size).to(dev)
+    hl = learner.make_hip_learner(cfg, net, dev, tower_precision=args.tower_precision, stage_precision=args.stage_precision)
+    replay = PrioritizedReplay(args.replay_size, 0.0, 0.0, np.random.RandomState(args.seed), device='cuda', state_format='frames_u8',
+                               frame_spec=(S, 1, H, W, cfg.num_actions))
+
+    p = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=args.envs, seed=args.seed), 0, tower_precision=args.tower_precision)
+    net.eval()
+    p.reload(hl.planner_weights())
+    p.attach_replay(replay, cfg, obs_shape=cfg.input_shape)
+    p.selfplay_reset_catch(rows, cols, record_format=args.record_format)
+    sampler = replay.device_sampler(seed=args.seed)
+
+    n_eval = -(-args.eval_envs // cols) * cols
+    pe = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=n_eval, seed=args.seed + 1), 0, tower_precision=args.tower_precision)
+    random_return = games.catch_random_policy_return(rows, cols)
+
+    def evaluate():
+        """n_eval host envs in one lock-step batch, ball column i % cols: greedy search, no noise."""
+        net.eval()
+        pe.reload(hl.planner_weights())
+        envs = [games.make_catch_env(rows, cols, H // rows, W // cols, stack_history=S) for _ in range(n_eval)]
+        obs = np.stack([e.reset(ball_col=i % cols) for i, e in enumerate(envs)])
+        mask = np.ones((n_eval, cfg.num_actions), bool)
+        rets = np.zeros(n_eval)
+        for _ in range(rows - 1):
+            act = pe.search(obs, mask, 1, 1, 0.0, deterministic=True)['action']
+            nxt = []
+            for i, e in enumerate(envs):
+                o, r, _, _ = e.step(int(act[i]))
+                rets[i] += r
+                nxt.append(o)
+            obs = np.stack(nxt)
+        return dict(eval_mean_return=float(rets.mean()), eval_standard_error=float(rets.std(ddof=1) / np.sqrt(n_eval)),
+                    eval_catch_rate=float((rets > 0).mean()), eval_episodes=n_eval, random_policy_return=random_return)
+
+    steps, t0, last = 0, time.time(), dict(episodes=0)
+    log, evals = [], []
+    ev = dict(train_steps=0, seconds=0.0, **evaluate())
+    evals.append(ev)
+    print(json.dumps(ev), flush=True)
+    while steps < args.train_steps:
+        T = float(cfg.visit_softmax_temperature_fn(0, steps))
+        p.selfplay_step(T, args.moves_per_iter)
+        p.synchronize()  # event order: the moves above are in the replay before anything is drawn from it
+        if replay.size < cfg.min_replay_size:
+            continue
+        net.train()
+        for _ in range(args.updates_per_iter):
+            idx_t, w_t, ring = sampler.sample(cfg.batch_size)  # draw, gather, update: all on the device
+            loss, prio = hl.step(ring, idx_t, w_t, cfg.batch_size)
+            steps += 1
+            if steps % args.report_every == 0:
+                c = p.selfplay_counters()
+                rec = dict(train_steps=steps, env_steps=int(c['env_steps']), episodes=int(c['episodes']), loss=float(loss), replay=replay.size,
+                           seconds=round(time.time() - t0, 1))
+                log.append(rec)
+                print(json.dumps(rec), flush=True)
+        net.eval()
+        p.reload(hl.planner_weights())  # actor <- learner, packed on the GPU
+        if args.eval_every and steps < args.train_steps and steps // args.eval_every > (steps - args.updates_per_iter) // args.eval_every:
+            ev = dict(train_steps=steps, seconds=round(time.time() - t0, 1), **evaluate())
+            evals.append(ev)
+            print(json.dumps(ev), flush=True)
+    ev = dict(train_steps=steps, seconds=round(time.time() - t0, 1), **evaluate())
+    evals.append(ev)
+    print(json.dumps(ev), flush=True)
+    learned = ev['eval_mean_return'] - random_return > 3 * ev['eval_standard_error']
+    summary = dict(final=ev, learned=bool(learned), record_info=p.record_info(), env_steps=int(p.selfplay_counters()['env_steps']))
+    print(json.dumps(summary), flush=True)
+    if args.out:
+        json.dump(dict(args=vars(args), log=log, evals=evals, summary=summary), open(args.out, 'w'), indent=1)
+    p.close()
+    pe.close()
+
+
+if __name__ == '__main__':
+    main()

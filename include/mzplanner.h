@@ -35,13 +35,15 @@ extern "C" {
 #define MZ_ENV_GOMOKU 3    /* GomokuEnv (board = obs_h, stack 4, five in a row), games/gomoku.py + games/env.py */
 #define MZ_ENV_SYNTHETIC 4 /* stand-in for the Atari emulator (absent dependency): fresh U[0,1) frames, reward 0, 1000-step episodes */
 #define MZ_ENV_EXTERNAL 5  /* any environment the caller steps on the host (mz_selfplay_reset_external) */
+#define MZ_ENV_CATCH 6     /* Catch as an image game on the device: uint8 frames through the host-stepped path's kernels (mz_selfplay_reset_catch) */
 
 /* Everything uct_search reads from MuZeroConfig (config.py:51-103) and from the network constructors
  * (network.py:239-247, 504-512, 543-549), plus planner-only sizing knobs. */
 typedef struct {
     /* network */
     int32_t net_kind;            /* MZ_NET_* */
-    int32_t obs_c, obs_h, obs_w; /* observation shape; MLP nets flatten it (network.py:153-154) */
+    int32_t obs_c, obs_h, obs_w; /* observation shape; MLP nets flatten it (network.py:153-154) and read only the product: a caller may
+                                    give them c = all elements, h = w = 1, or the image's own shape (mz_selfplay_reset_catch reads it) */
     int32_t num_actions;         /* board nets (MZ_NET_BOARD): <= 384, boards of at most 361 points (19 x 19); MLP / Atari nets: <= 256 */
     int32_t num_planes;
     int32_t hidden_dim;          /* MLP only */
@@ -285,7 +287,7 @@ typedef struct {
      * (decoded as MZ_STATE_FRAMES_U8 rows are).  The ring keeps S moves more than the float32 ring would, and its 64 -> 16 rule counts frame
      * bytes.  Refused (MZ_E_INVALID naming record_format) by mz_selfplay_reset_external: without stack_history > 0, is_obs_image and
      * frame_u8; with num_actions > 256; with an attached replay whose state_format is not MZ_STATE_FRAMES_U8; any other value.
-     * mz_selfplay_reset (device envs) always keeps float32 records. */
+     * mz_selfplay_reset (device envs) always keeps float32 records; the device Catch env has its own reset, mz_selfplay_reset_catch. */
     int32_t record_format;
 } mz_external_env;
 #define MZ_RECORD_F32 0
@@ -300,6 +302,27 @@ int mz_selfplay_external_act(mz_planner* p, const void* h_frames, const uint8_t*
 /* Report the outcome of the actions returned by the last act call: h_reward float32 [B], h_done uint8 [B].  done[e] = 1 means the host
  * will hand env e's reset frame to the next act call. */
 int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done);
+
+/* Catch (MZ_ENV_CATCH): an image game that lives on the device and renders the uint8 frames a host env would upload, so the host-stepped
+ * path's device work -- frame stacking, record ring (float32 or compact), epilogue into a float32 or MZ_STATE_FRAMES_U8 replay -- runs
+ * with no host in the loop.  The game (muzero_amd.games.CatchEnv is the specification): a rows x cols grid of cells drawn on a one-channel
+ * frame; a ball falls one row per move, the paddle in the last row moves left / stays / right (actions 0 / 1 / 2, clipped at the walls)
+ * before the ball falls; when the ball reaches the last row the episode ends with reward +1 if it meets the paddle, else -1; every other
+ * reward is 0.  Frame pixels are 0, the ball's and the paddle's cells 255.  Mask all legal, players 1 / 1.  A finished env restarts at once
+ * (ball in row 0, paddle at cols / 2); the ball column of env e, episode k is min(cols - 1, floor(u * cols)), u the first double of
+ * Philox(seed, e, k, 0x70000000).  Episode 0 of env e starts with the ball in row e % (rows - 1), so envs do not finish in step.
+ * Geometry comes from the planner's mz_config: obs_c = 2 * S (S frames of one channel and S action planes, stack_history = S >= 1), frame
+ * obs_h x obs_w, cells of (obs_h / rows) x (obs_w / cols) pixels -- both must divide -- num_actions == 3, not a board game; anything else
+ * is MZ_E_INVALID naming the field.  record_format is mz_external_env's, with its rules and refusals; an attached replay is MZ_STATE_F32
+ * or MZ_STATE_FRAMES_U8.  After this reset mz_selfplay_step(p, T, n) plays n moves with nothing crossing PCIe and no host synchronisation
+ * (with a replay attached: one at the end of the call, which reads back the record ring's capacity check and the search kernels' error
+ * word once per call); mz_selfplay_read, _counters, _record_info and _attach_replay work as on the other kinds;
+ * mz_selfplay_external_act / _commit return MZ_E_STATE; mz_arena_reset refuses the kind. */
+typedef struct {
+    int32_t rows, cols;     /* the grid; rows = cols = 0: 12 x 12 */
+    int32_t record_format;  /* MZ_RECORD_F32 or MZ_RECORD_FRAMES_U8 */
+} mz_catch_env;
+int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env);
 
 /* Arena: the evaluators' game loops (pipeline.py:289-397 board games, pipeline.py:400-488 one-player envs) for num_envs games in
  * lock-step on the device.  Every searched move is uct_search(deterministic = True) on the planner's search kernels: no root noise, the
@@ -318,7 +341,7 @@ int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint
  *   envs) from a Philox stream of their own: both games of a pair start from the same position with colours swapped.
  *   Random moves (openings, MZ_ARENA_RANDOM): legal[floor(u * n_legal)], u one Philox double per (pair or env, ply), recorded.
  *   Game length is capped by the env: 500 steps (CartPole), the point count (boards).
- * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC, MZ_ENV_EXTERNAL: MZ_E_INVALID); h_init_state as
+ * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC, MZ_ENV_EXTERNAL, MZ_ENV_CATCH: MZ_E_INVALID); h_init_state as
  * mz_selfplay_reset (CartPole only).  Arena and self-play exclude each other on a handle: mz_selfplay_step during an arena is MZ_E_STATE,
  * mz_arena_step without mz_arena_reset (e.g. during self-play) is MZ_E_STATE; each mode's reset enters it. */
 #define MZ_ARENA_NONE 0

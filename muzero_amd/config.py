@@ -137,3 +137,24 @@ def make_atari_config(num_training_steps=int(10e6), batch_size=128, min_replay_s
         reward_support_size=61, min_replay_size=min_replay_size, acc_seq_length=200, train_delay=0.0, clip_grad=clip_grad,
         use_tensorboard=use_tensorboard, is_board_game=False,
     )
+
+
+def catch_visit_softmax_temperature_fn(env_steps, training_steps):
+    return _by_training_steps(training_steps, 2000, 4000)
+
+
+def make_catch_config(num_training_steps=3000, batch_size=128, min_replay_size=2000, rows=12, cols=12, cell=8, stack_history=4, use_tensorboard=False,
+                      clip_grad=False) -> MuZeroConfig:
+    """Catch (`games.CatchEnv`, the device env 'Catch') for `MuZeroAtariNet`: the Atari config's categorical heads and frame stack on a game
+    of rows - 1 moves with one reward at its end.  td_steps covers the whole game (the n-step target is the discounted outcome),
+    acc_seq_length is short (window acc + unroll + td > rows - 1: an episode is never cut), the net is small.  Not in the reference; the
+    extra attributes (num_actions, stack_history, rows, cols, input_shape) describe the env."""
+    cfg = MuZeroConfig(
+        discount=0.997, dirichlet_alpha=0.25, num_simulations=25, batch_size=batch_size, td_steps=rows - 1, lr_init=0.002,
+        lr_milestones=[100e3], visit_softmax_temperature_fn=catch_visit_softmax_temperature_fn, num_training_steps=num_training_steps,
+        num_planes=32, num_res_blocks=2, hidden_dim=0, value_support_size=11, reward_support_size=11, min_replay_size=min_replay_size,
+        checkpoint_interval=100, acc_seq_length=4, train_delay=0.0, clip_grad=clip_grad, use_tensorboard=use_tensorboard, is_board_game=False,
+    )
+    cfg.num_actions, cfg.stack_history, cfg.rows, cfg.cols = 3, stack_history, rows, cols
+    cfg.input_shape = (2 * stack_history, rows * cell, cols * cell)
+    return cfg

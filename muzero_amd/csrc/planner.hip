@@ -16,6 +16,7 @@
 #include "mz_env.h"
 #include "mz_arena.h"
 #include "mz_extenv.h"
+#include "mz_catch.h"
 #include "mz_search.h"
 #include "mz_search_fast.h"
 #include "mz_convnet.h"
@@ -213,6 +214,7 @@ struct mz_planner {
     RecRing rr{};                  // compact record ring (MZ_RECORD_FRAMES_U8; rr.frames null: float32 records in env.r_obs)
     int rec_S = 0;                 // its stack_history
     float* d_rec_stage = nullptr;  // [B][obs] one move of decoded observations (mz_selfplay_read, allocated by the first read)
+    CatchEnv catch_env{};          // MZ_ENV_CATCH (mz_catch.h): the game's state; frames, rewards and done flags are ext's buffers
 
     // arena (mz_arena.h): evaluation games in lock-step on this handle's env state
     ArenaState arena{};
@@ -590,6 +592,7 @@ static int planner_init(mz_planner* p, bool conv) {
 }
 
 static void ext_free(mz_planner* p);
+static int catch_moves(mz_planner* p, double temperature, int n_moves);
 
 extern "C" int mz_planner_destroy(mz_planner* p) {
     if (!p) return MZ_OK;
@@ -1586,6 +1589,8 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         num_to_win = 5;
     } else if (env_kind == MZ_ENV_SYNTHETIC) {
         if (h_init_state) return fail(MZ_E_INVALID, "the synthetic env takes no initial state");
+    } else if (env_kind == MZ_ENV_CATCH) {
+        return fail(MZ_E_INVALID, "MZ_ENV_CATCH has its own reset: mz_selfplay_reset_catch");
     } else {
         return fail(MZ_E_INVALID, "unknown env kind");
     }
@@ -1623,6 +1628,7 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
     if (p->env_kind == MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "mz_selfplay_step on host-stepped envs: use mz_selfplay_external_act / _commit");
     if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
+    if (p->env_kind == MZ_ENV_CATCH) return catch_moves(p, temperature, n_moves);
     const mz_config& c = p->cfg;
     for (int m = 0; m < n_moves; m++) {
         EnvLaunch L{};
@@ -1664,6 +1670,10 @@ static void ext_free(mz_planner* p) {
         if (b) (void)hipHostFree(b);
     p->ext = ExtEnv{};
     rec_free(p);
+    void* cbufs[] = {p->catch_env.br, p->catch_env.bc, p->catch_env.pc};
+    for (void* b : cbufs)
+        if (b) (void)hipFree(b);
+    p->catch_env = CatchEnv{};
     p->h_ext_frames = nullptr; p->h_ext_mask = p->h_ext_done = nullptr;
     p->h_ext_cur = p->h_ext_opp = p->h_ext_action = p->h_ext_err = nullptr;
     p->h_ext_reward = nullptr;
@@ -1680,8 +1690,9 @@ static ExtLaunch ext_launch(mz_planner* p, double temperature) {
     return L;
 }
 
-extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* x) {
-    if (!p || !x) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_external");
+// The reset of both kinds that run on ExtEnv: host-stepped envs (`sname` "mz_external_env") and the device Catch env, which describes its
+// frames with the same struct ("mz_catch_env": its refusals name that struct's record_format).
+static int ext_reset(mz_planner* p, const mz_external_env* x, int env_kind, const std::string& sname) {
     HIPCHK(hipSetDevice(p->device));
     const mz_config& c = p->cfg;
     const int S = x->stack_history;
@@ -1702,18 +1713,18 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
         if (c.num_actions > 256) return fail(MZ_E_INVALID, "mz_replay_ring.state_format MZ_STATE_FRAMES_U8 holds an action in one byte: num_actions > 256");
     }
     if (x->record_format != MZ_RECORD_F32 && x->record_format != MZ_RECORD_FRAMES_U8)
-        return fail(MZ_E_INVALID, "mz_external_env.record_format must be MZ_RECORD_F32 or MZ_RECORD_FRAMES_U8");
+        return fail(MZ_E_INVALID, sname + ".record_format must be MZ_RECORD_F32 or MZ_RECORD_FRAMES_U8");
     const bool rec = x->record_format == MZ_RECORD_FRAMES_U8;
     if (rec) {
         if (S == 0 || !x->is_obs_image || !x->frame_u8)
-            return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8 needs stack_history > 0, is_obs_image and frame_u8 (a record is one uint8 frame)");
-        if (c.num_actions > 256) return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8 rebuilds one-byte actions: num_actions > 256");
+            return fail(MZ_E_INVALID, sname + ".record_format MZ_RECORD_FRAMES_U8 needs stack_history > 0, is_obs_image and frame_u8 (a record is one uint8 frame)");
+        if (c.num_actions > 256) return fail(MZ_E_INVALID, sname + ".record_format MZ_RECORD_FRAMES_U8 rebuilds one-byte actions: num_actions > 256");
         if (p->has_replay && fmt != STATE_FRAMES_U8)
-            return fail(MZ_E_INVALID, "mz_external_env.record_format MZ_RECORD_FRAMES_U8 feeds a replay of mz_replay_ring.state_format MZ_STATE_FRAMES_U8 only");
+            return fail(MZ_E_INVALID, sname + ".record_format MZ_RECORD_FRAMES_U8 feeds a replay of mz_replay_ring.state_format MZ_STATE_FRAMES_U8 only");
     }
     ext_free(p);
     p->arena_open = false;
-    p->env_kind = MZ_ENV_EXTERNAL;
+    p->env_kind = env_kind;
     p->ext_pending = p->ext_broken = false;
     const size_t rec_stride = ((size_t)FE + 15) / 16 * 16;
     if (rec) ring_start(p, x->max_episode_steps, rec_stride, S);
@@ -1741,7 +1752,7 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
     X.temp_steps = x->temp_switch_steps > 0 ? x->temp_switch_steps : (c.num_actions <= 10 ? 6 : 30);
     p->ext_od = obs_dim(c);
     const size_t B = (size_t)c.num_envs, fbytes = (size_t)FE * (X.u8 ? 1 : 4);
-    HIPCHK(hipMalloc(&X.frames, B * fbytes));
+    HIPCHK(hipMalloc(&X.frames, (B * fbytes + 15) / 16 * 16));  // (whole 16-byte runs: k_catch_render stores nothing narrower)
     if (S > 0) {
         HIPCHK(hipMalloc(&X.hist, B * S * fbytes));
         HIPCHK(hipMalloc(&X.hist_act, B * S * sizeof(int)));
@@ -1776,6 +1787,40 @@ extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* 
     return MZ_OK;
 }
 
+extern "C" int mz_selfplay_reset_external(mz_planner* p, const mz_external_env* x) {
+    if (!p || !x) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_external");
+    return ext_reset(p, x, MZ_ENV_EXTERNAL, "mz_external_env");
+}
+
+// The device work of an act, shared by the host-stepped path and Catch: observations from ext.frames into the search input and the record
+// ring, the search (move_counter keys the Philox draws as in mz_selfplay_step), the move's action / pi / root value into the record slot.
+static int ext_enqueue_act(mz_planner* p, const ExtLaunch& L) {
+    const mz_config& c = p->cfg;
+    const int OD = p->ext_od;
+    const bool vec4 = (p->ext.S > 0 && p->ext.image && p->ext.HW % 4 == 0) || (p->ext.S == 0 && OD % 4 == 0);  // (four floats of one plane / run per group)
+    const dim3 grid4((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), c.num_envs), grid1((OD + 63) / 64, c.num_envs);
+    if (p->rr.frames) {  // compact records: the same pass without the float32 record
+        if (vec4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_ingest<4, true>), grid4, dim3(256), 0, p->stream, L);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_ingest<1, true>), grid1, dim3(64), 0, p->stream, L);
+    } else if (vec4)
+        hipLaunchKernelGGL(k_ext_ingest<4>, grid4, dim3(256), 0, p->stream, L);
+    else
+        hipLaunchKernelGGL(k_ext_ingest<1>, grid1, dim3(64), 0, p->stream, L);
+    HIPCHK(hipGetLastError());
+    int rc = launch_search(p, c.num_envs, 0, true, false, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ext_record, dim3((c.num_envs * c.num_actions + 255) / 256), dim3(256), 0, p->stream, L);
+    HIPCHK(hipGetLastError());
+    return MZ_OK;
+}
+
+// The device work of a commit: ext.reward / ext.done into the record slot, step counts, counters, the record ring's capacity check.
+static int ext_enqueue_commit(mz_planner* p, const ExtLaunch& L) {
+    hipLaunchKernelGGL(k_ext_commit, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, L);
+    HIPCHK(hipGetLastError());
+    return MZ_OK;
+}
+
 extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur, const int32_t* h_opp,
                                         double temperature, int32_t* h_action) {
     if (!p || !h_frames || !h_mask || !h_cur || !h_opp || !h_action) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_act");
@@ -1795,22 +1840,8 @@ extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, con
     HIPCHK(hipMemcpyAsync(p->d_mask, p->h_ext_mask, B * c.num_actions, hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemcpyAsync(p->d_cur, p->h_ext_cur, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemcpyAsync(p->d_opp, p->h_ext_opp, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
-    const ExtLaunch L = ext_launch(p, temperature);
-    const int OD = p->ext_od;
-    const bool vec4 = (p->ext.S > 0 && p->ext.image && p->ext.HW % 4 == 0) || (p->ext.S == 0 && OD % 4 == 0);  // (four floats of one plane / run per group)
-    const dim3 grid4((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), c.num_envs), grid1((OD + 63) / 64, c.num_envs);
-    if (p->rr.frames) {  // compact records: the same pass without the float32 record
-        if (vec4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_ingest<4, true>), grid4, dim3(256), 0, p->stream, L);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_ingest<1, true>), grid1, dim3(64), 0, p->stream, L);
-    } else if (vec4)
-        hipLaunchKernelGGL(k_ext_ingest<4>, grid4, dim3(256), 0, p->stream, L);
-    else
-        hipLaunchKernelGGL(k_ext_ingest<1>, grid1, dim3(64), 0, p->stream, L);
-    HIPCHK(hipGetLastError());
-    int rc = launch_search(p, c.num_envs, 0, true, false, false);  // (move_counter keys the Philox draws as in mz_selfplay_step)
+    int rc = ext_enqueue_act(p, ext_launch(p, temperature));
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ext_record, dim3((c.num_envs * c.num_actions + 255) / 256), dim3(256), 0, p->stream, L);
-    HIPCHK(hipGetLastError());
     int err = 0;
     HIPCHK(hipMemcpyAsync(p->h_ext_action, p->d_action, B * sizeof(int), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipMemcpyAsync(&err, p->d_err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
@@ -1837,9 +1868,8 @@ extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward,
     std::memcpy(p->h_ext_done, h_done, B);
     HIPCHK(hipMemcpyAsync(p->ext.reward, p->h_ext_reward, B * sizeof(float), hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemcpyAsync(p->ext.done, p->h_ext_done, B, hipMemcpyHostToDevice, p->stream));
-    const ExtLaunch L = ext_launch(p, 0.0);
-    hipLaunchKernelGGL(k_ext_commit, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, L);
-    HIPCHK(hipGetLastError());
+    int crc = ext_enqueue_commit(p, ext_launch(p, 0.0));
+    if (crc) return crc;
     p->ext_pending = false;
     if (p->has_replay) {  // the length check must pass before the epilogue may read the trajectories
         HIPCHK(hipMemcpyAsync(p->h_ext_err, p->ext.err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
@@ -1861,6 +1891,95 @@ extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward,
         }
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Catch: the host-stepped path's device work around an env that lives on the device (mz_catch.h)
+// ---------------------------------------------------------------------------------------------------------
+static CatchLaunch catch_launch(mz_planner* p) {
+    CatchLaunch G{};
+    G.c = p->catch_env; G.B = p->cfg.num_envs; G.seed = p->cfg.seed;
+    G.action = p->d_action; G.episode = p->env.episode; G.reward = p->ext.reward; G.done = p->ext.done;
+    G.frames = static_cast<unsigned char*>(p->ext.frames); G.mask = p->d_mask; G.cur = p->d_cur; G.opp = p->d_opp;
+    return G;
+}
+
+static void catch_render(mz_planner* p, const CatchLaunch& G) {
+    const size_t runs = ((size_t)G.B * G.c.FE + 15) / 16;
+    hipLaunchKernelGGL(k_catch_render, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, G);
+}
+
+extern "C" int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_catch");
+    const mz_config& c = p->cfg;
+    const int rows = env->rows == 0 && env->cols == 0 ? 12 : env->rows, cols = env->rows == 0 && env->cols == 0 ? 12 : env->cols;
+    if (c.is_board_game) return fail(MZ_E_INVALID, "mz_selfplay_reset_catch: is_board_game must be 0 (Catch is a one-player game)");
+    if (c.num_actions != 3) return fail(MZ_E_INVALID, "mz_selfplay_reset_catch: num_actions must be 3 (left, stay, right), not " + std::to_string(c.num_actions));
+    if (c.obs_c < 2 || (c.obs_c & 1))
+        return fail(MZ_E_INVALID, "mz_selfplay_reset_catch: obs_c must be 2 * stack_history (S one-channel frames and S action planes), not " + std::to_string(c.obs_c));
+    if (rows < 2 || c.obs_h % rows != 0)
+        return fail(MZ_E_INVALID, "mz_catch_env.rows must be >= 2 and divide obs_h = " + std::to_string(c.obs_h) + ", not " + std::to_string(rows));
+    if (cols < 1 || c.obs_w % cols != 0)
+        return fail(MZ_E_INVALID, "mz_catch_env.cols must be >= 1 and divide obs_w = " + std::to_string(c.obs_w) + ", not " + std::to_string(cols));
+    if (p->has_replay && p->replay.state_format == STATE_I8)
+        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: Catch observations (action planes of 1/3, 2/3) are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
+    mz_external_env x{};
+    x.stack_history = c.obs_c / 2; x.is_obs_image = 1; x.frame_c = 1; x.frame_h = c.obs_h; x.frame_w = c.obs_w; x.frame_u8 = 1;
+    x.max_episode_steps = rows - 1;  // (an episode's length: the record ring always holds an open trajectory)
+    x.record_format = env->record_format;
+    int rc = ext_reset(p, &x, MZ_ENV_CATCH, "mz_catch_env");
+    if (rc) return rc;
+    CatchEnv& K = p->catch_env;
+    K.rows = rows; K.cols = cols; K.ch = c.obs_h / rows; K.cw = c.obs_w / cols; K.H = c.obs_h; K.W = c.obs_w; K.FE = c.obs_h * c.obs_w;
+    const size_t B = (size_t)c.num_envs;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.br), B * sizeof(int)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.bc), B * sizeof(int)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.pc), B * sizeof(int)));
+    const CatchLaunch G = catch_launch(p);
+    hipLaunchKernelGGL(k_catch_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
+    catch_render(p, G);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+// mz_selfplay_step on Catch: per move the act's device work, the env's step and next frame, the commit's device work, the epilogue.
+// Nothing is copied and nothing waits inside the loop.  What the host-stepped path reads back per commit is read back once per call, and
+// only with a replay attached (one synchronisation at the end of the call): the record ring's capacity check -- a guard here, the reset
+// sized the ring for the game's fixed episode length, so the moves of this call already ran their epilogues when it is read -- and the
+// search kernels' error word.
+static int catch_moves(mz_planner* p, double temperature, int n_moves) {
+    if (p->ext_broken) return fail(MZ_E_STATE, "an earlier mz_selfplay_step found an over-long trajectory or a search error: call mz_selfplay_reset_catch");
+    const CatchLaunch G = catch_launch(p);
+    for (int m = 0; m < n_moves; m++) {
+        const ExtLaunch L = ext_launch(p, temperature);
+        int rc = ext_enqueue_act(p, L);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_catch_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
+        catch_render(p, G);
+        rc = ext_enqueue_commit(p, L);
+        if (rc) return rc;
+        rc = ring_finish_move(p);
+        if (rc) return rc;
+    }
+    if (p->has_replay) {
+        int err = 0;
+        HIPCHK(hipMemcpyAsync(p->h_ext_err, p->ext.err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipMemcpyAsync(&err, p->d_err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        if (*p->h_ext_err != INT_MAX) {
+            p->ext_broken = true;
+            return fail(MZ_E_INVALID, "env " + std::to_string(*p->h_ext_err) + ": open trajectory of more than " + std::to_string(p->ring_len - p->rr.extra) +
+                                          " moves outgrew the record ring; reset next");
+        }
+        if (err) {
+            HIPCHK(hipMemsetAsync(p->d_err, 0, sizeof(int), p->stream));
+            HIPCHK(hipStreamSynchronize(p->stream));
+            p->ext_broken = true;
+            return fail(MZ_E_INVALID, "search kernel reported error " + std::to_string(err));
+        }
+    }
+    return MZ_OK;
 }
 
 extern "C" int mz_selfplay_attach_replay(mz_planner* p, const mz_replay_ring* ring) {
@@ -2027,6 +2146,8 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
             return fail(MZ_E_INVALID, "Gomoku env needs a board net with a (9,N,N) observation, N >= 5, and num_actions == N*N + 1");
         board_n = c.obs_h;
         num_to_win = 5;
+    } else if (env_kind == MZ_ENV_CATCH) {
+        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_CATCH is a self-play env only (the arena plays CartPole, TicTacToe and Gomoku)");
     } else {
         return fail(MZ_E_INVALID, "the arena plays the device envs CartPole, TicTacToe and Gomoku (not the synthetic or host-stepped kinds)");
     }

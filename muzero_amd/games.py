@@ -274,3 +274,80 @@ class CartPoleEnv(PlayerIdAndActionMaskWrapper):
 
     def reset(self, state=None) -> np.ndarray:
         return self.env.reset(state=state)
+
+
+class CatchEnv:
+    """Catch (as in bsuite) rendered as an image; the specification of the device env MZ_ENV_CATCH (`csrc/mz_catch.h`, same rules).
+    A `rows` x `cols` grid of `cell_h` x `cell_w` pixel cells on a uint8 frame [1, rows * cell_h, cols * cell_w].  The ball sits at
+    (br, bc), the paddle at column pc of the last row.  reset: br = `start_row`, bc = the `ball_col` given (else the next of `ball_cols`,
+    else a draw from the env's own RandomState), pc = cols // 2.  step(a), a in (0 left, 1 stay, 2 right): pc = clip(pc + a - 1, 0,
+    cols - 1), then br += 1; when br == rows - 1 the episode is done with reward +1.0 if bc == pc, else -1.0; every other reward is 0.
+    The frame is 0 with every pixel of the ball's cell and of the paddle's cell 255.  `first_row`: the ball's row in the first episode
+    only (the device env staggers its envs this way); `ball_cols`: an iterable of ball columns for successive resets."""
+
+    name = 'Catch'
+    num_actions = 3
+
+    def __init__(self, rows: int = 12, cols: int = 12, cell_h: int = 8, cell_w: int = 8, start_row: int = 0, seed: int = 1, ball_cols=None,
+                 first_row: Optional[int] = None) -> None:
+        if rows < 2 or cols < 1 or cell_h < 1 or cell_w < 1 or not 0 <= start_row <= rows - 2:
+            raise ValueError('CatchEnv needs rows >= 2, cols >= 1, cells of at least one pixel and 0 <= start_row <= rows - 2')
+        if first_row is not None and not 0 <= first_row <= rows - 2:
+            raise ValueError('first_row must be a row above the paddle\'s')
+        self.rows, self.cols, self.cell_h, self.cell_w, self.start_row = rows, cols, cell_h, cell_w, start_row
+        self.observation_shape = (1, rows * cell_h, cols * cell_w)
+        self.max_episode_steps = rows - 1
+        self._rs = np.random.RandomState(seed)
+        self._cols = None if ball_cols is None else iter(ball_cols)
+        self._first_row = first_row
+        self.br = self.bc = self.pc = 0
+        self.done = True
+
+    def reset(self, ball_col: Optional[int] = None) -> np.ndarray:
+        if ball_col is None:
+            ball_col = next(self._cols) if self._cols is not None else self._rs.randint(self.cols)
+        if not 0 <= ball_col < self.cols:
+            raise ValueError(f'ball column {ball_col} outside the {self.cols} columns')
+        self.br, self._first_row = (self.start_row if self._first_row is None else self._first_row), None
+        self.bc, self.pc, self.done = int(ball_col), self.cols // 2, False
+        return self.render()
+
+    def step(self, action: int):
+        if self.done:
+            raise RuntimeError('Episode is over, call reset before using step method.')
+        if action not in (0, 1, 2):
+            raise ValueError(f'Invalid action {action}')
+        self.pc = min(max(self.pc + int(action) - 1, 0), self.cols - 1)
+        self.br += 1
+        reward = 0.0
+        if self.br == self.rows - 1:
+            self.done = True
+            reward = 1.0 if self.bc == self.pc else -1.0
+        return self.render(), reward, self.done, {}
+
+    def render(self) -> np.ndarray:
+        h, w = self.cell_h, self.cell_w
+        frame = np.zeros(self.observation_shape, np.uint8)
+        frame[0, self.br * h:(self.br + 1) * h, self.bc * w:(self.bc + 1) * w] = 255
+        frame[0, (self.rows - 1) * h:, self.pc * w:(self.pc + 1) * w] = 255
+        return frame
+
+
+def make_catch_env(rows: int = 12, cols: int = 12, cell_h: int = 8, cell_w: int = 8, stack_history: int = 4, **kwargs):
+    """`CatchEnv` as the Atari nets see it: PlayerIdAndActionMaskWrapper(StackFrameAndAction(ScaledFloatFrame(env), stack_history, True)),
+    observations float32 [2 * stack_history, rows * cell_h, cols * cell_w]."""
+    return PlayerIdAndActionMaskWrapper(StackFrameAndAction(ScaledFloatFrame(CatchEnv(rows, cols, cell_h, cell_w, **kwargs)), stack_history, True))
+
+
+def catch_random_policy_return(rows: int = 12, cols: int = 12, start_row: int = 0) -> float:
+    """The expected return of the uniformly random policy on `CatchEnv`, exactly: dynamic programming over (paddle column, steps left)
+    for every ball column, averaged over the ball columns (each equally likely)."""
+    steps = rows - 1 - start_row
+    total = 0.0
+    for bc in range(cols):
+        v = np.where(np.arange(cols) == bc, 1.0, -1.0)  # the value with no step left: the catch test
+        for _ in range(steps):
+            left, right = np.concatenate([v[:1], v[:-1]]), np.concatenate([v[1:], v[-1:]])  # (clipped at the walls)
+            v = (left + v + right) / 3.0
+        total += v[cols // 2]
+    return float(total / cols)

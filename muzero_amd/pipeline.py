@@ -214,7 +214,7 @@ class EpisodeAssembler:
         del self.open[b][:n]
 
 
-DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari')
+DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari', 'Catch')
 MAX_ENV_THREADS = 16
 
 
@@ -285,8 +285,8 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
                   moves_per_drain: int = 16, max_moves: Optional[int] = None, device_stack: bool = True, env_threads: int = 1,
                   record_format: str = 'f32') -> int:
     """Self-play until `stop_event` is set (pipeline.py:41-167).  `env` names a device environment ('CartPole-v1',
-    'TicTacToe', 'Gomoku', or 'Synthetic-Atari': random frames standing in for the absent emulator); `config.num_envs` of
-    them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
+    'TicTacToe', 'Gomoku', 'Synthetic-Atari': random frames standing in for the absent emulator, or 'Catch': `games.CatchEnv` on the
+    device, its grid read off `env` when that is a CatchEnv object, else 12 x 12 on the network's frame); `config.num_envs` of them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
     `(Transition, priority)` tuples, assembled on the host from the device records -- or a
     `muzero_amd.replay.PrioritizedReplay(device='cuda')`: then the planner's DEVICE EPILOGUE builds the items on the GPU and
     writes them straight into that replay (no host assembly, no queue, no data collector thread); only rewards and done
@@ -299,8 +299,8 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     is reset on the host.  Envs that are `games.StackFrameAndAction` (directly or inside `games.PlayerIdAndActionMaskWrapper`)
     have their stacking done on the device from the newest frame (`device_stack=False`: on the host).  The actor owns the env
     objects while it runs: it may step an inner env of a wrapper, leaving the wrapper's own state stale.  `env_threads` (1 to 16)
-    host threads step the envs.  `record_format` 'frames_u8' (host-stepped envs whose uint8 image frames the device stacks; device envs
-    ignore it): the planner's record ring keeps one uint8 frame per move instead of the float32 observation
+    host threads step the envs.  `record_format` 'frames_u8' (host-stepped envs whose uint8 image frames the device stacks, and 'Catch';
+    the other device envs ignore it): the planner's record ring keeps one uint8 frame per move instead of the float32 observation
     (`Planner.selfplay_reset_external`); what reaches `data_queue` is the same."""
     kind, target = resolve_self_play_envs(env, int(getattr(config, 'num_envs', 1)))
     if kind == 'host':
@@ -310,16 +310,22 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
 
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU, 'Synthetic-Atari': pl.ENV_SYNTHETIC}
     name = target
+    if name == 'Catch':
+        pl._record_format(record_format)  # (an unknown name: before any GPU work)
     num_envs = int(getattr(config, 'num_envs', 1))
     idx = device.index if getattr(device, 'index', None) is not None else 0
-    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
+    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank,
+                                     keep_shape=name == 'Catch'), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
     p.reload(network.state_dict())
     from muzero_amd.replay import PrioritizedReplay
 
     on_device = isinstance(data_queue, PrioritizedReplay)
     if on_device:  # ONE device writer per replay (attach_device_writer raises on a second one): every actor rank its own shard
         p.attach_replay(data_queue, config, obs_shape=getattr(network, 'input_shape', None))
-    p.selfplay_reset(kinds[name])
+    if name == 'Catch':
+        p.selfplay_reset_catch(int(getattr(env, 'rows', 12)), int(getattr(env, 'cols', 12)), record_format=record_format)
+    else:
+        p.selfplay_reset(kinds[name])
     asm = EpisodeAssembler(config, num_envs, getattr(network, 'input_shape', None))
     from muzero_amd import metrics as mzm
 

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libmzplanner_hip.so')
 
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
-ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL = 0, 1, 2, 3, 4, 5
+ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_CATCH = 0, 1, 2, 3, 4, 5, 6
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
 ARENA_NONE, ARENA_RANDOM, ARENA_PLANNER = 0, 1, 2  # opponent kinds of mz_arena_reset
 SIDE_CHALLENGER, SIDE_OPPONENT, SIDE_RANDOM, SIDE_OPENING = 0, 1, 2, 3  # who chose a ply's move (arena_read_ply 'side')
@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
     'mz_selfplay_record_info',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
+    'mz_selfplay_reset_catch',
     'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
 ]
@@ -60,6 +61,10 @@ class MzReplayRing(C.Structure):
 class MzExternalEnv(C.Structure):
     _fields_ = [('stack_history', C.c_int32), ('is_obs_image', C.c_int32), ('frame_c', C.c_int32), ('frame_h', C.c_int32), ('frame_w', C.c_int32),
                 ('frame_u8', C.c_int32), ('max_episode_steps', C.c_int32), ('temp_switch_steps', C.c_int32), ('record_format', C.c_int32)]
+
+
+class MzCatchEnv(C.Structure):
+    _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('record_format', C.c_int32)]
 
 
 _lib = None
@@ -107,6 +112,7 @@ def load_library():
     L.mz_selfplay_reset_external.argtypes = [vp, C.POINTER(MzExternalEnv)]
     L.mz_selfplay_external_act.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp]
     L.mz_selfplay_external_commit.argtypes = [vp, vp, vp]
+    L.mz_selfplay_reset_catch.argtypes = [vp, C.POINTER(MzCatchEnv)]
     L.mz_arena_reset.argtypes = [vp, i32, i32, vp, i32, vp]
     L.mz_arena_step.argtypes = [vp, i32]
     L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
@@ -162,10 +168,12 @@ def _record_format(v):
     raise ValueError(f"record_format must be 'f32' or 'frames_u8', not {v!r}")
 
 
-def make_mz_config(spec, config=None, num_envs=1, max_ties=0, seed=1, **search_overrides):
-    """Build an mz_config from a network spec (MuZeroNet.planner_spec()) and a MuZeroConfig-like object."""
+def make_mz_config(spec, config=None, num_envs=1, max_ties=0, seed=1, keep_shape=False, **search_overrides):
+    """Build an mz_config from a network spec (MuZeroNet.planner_spec()) and a MuZeroConfig-like object.  MLP nets get their input
+    flattened (obs_c = all elements, obs_h = obs_w = 1) unless `keep_shape`: then a [C, H, W] input keeps its shape -- the MLP kernels read
+    only the product, `selfplay_reset_catch` reads the frame geometry off it."""
     shape = tuple(spec['input_shape'])
-    if spec['kind'] == 'mlp':
+    if spec['kind'] == 'mlp' and not (keep_shape and len(shape) == 3):
         c, h, w = int(np.prod(shape)), 1, 1
     else:
         c, h, w = shape
@@ -519,6 +527,22 @@ class Planner:
         r = np.ascontiguousarray(np.broadcast_to(reward, (self.B,)), np.float32)
         d = np.ascontiguousarray(np.broadcast_to(done, (self.B,)), np.uint8)
         _chk(self.lib.mz_selfplay_external_commit(self.h, _p(r), _p(d)))
+
+    def selfplay_reset_catch(self, rows=12, cols=12, record_format='f32'):
+        """Start self-play on the device Catch env (mz_selfplay_reset_catch; `games.CatchEnv` is the same game on the host): a `rows` x
+        `cols` grid drawn on the planner's own frame (obs_c = 2 * stack_history, obs_h x obs_w pixels, cells of obs_h / rows x obs_w / cols),
+        3 actions.  `selfplay_step` then plays whole moves on the device.  `record_format` as in `selfplay_reset_external`."""
+        rfmt = _record_format(record_format)
+        cfg = self.cfg
+        keep = getattr(self, '_replay_keepalive', None)
+        ring = None if keep is None else keep[0]._ring
+        if ring is not None and getattr(ring, 'state_format', 'f32') == 'frames_u8' and cfg.obs_c % 2 == 0 and \
+                tuple(ring.frame_spec[:4]) != (cfg.obs_c // 2, 1, cfg.obs_h, cfg.obs_w):
+            # (the kernel sizes a row from the env: a ring built for other frames would be written out of bounds)
+            raise PlannerError(f'the attached replay\'s frame_spec {tuple(ring.frame_spec)} is not this env\'s (stack_history, C, H, W) = '
+                               f'{(cfg.obs_c // 2, 1, cfg.obs_h, cfg.obs_w)}')
+        x = MzCatchEnv(int(rows), int(cols), rfmt)
+        _chk(self.lib.mz_selfplay_reset_catch(self.h, C.byref(x)))
 
     def selfplay_read(self, n_moves, fields=None):
         """Records of the last `n_moves` moves, arrays [n_moves, B, ...].  `fields`: subset of ('obs', 'action', 'reward', 'pi',
