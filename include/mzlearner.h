@@ -112,7 +112,9 @@ const char* mzl_last_error(void);
  *              ring zeroed, instead of the inner rows), MZLC_NO_ROW_STEPS=1 (16 flat positions per reduction step of those instead of one row of a wide tile's inner columns), MZLC_NO_QUAD_STEPS=1 (the 12-wide tiles' weight gradients step over whole pitch rows, pad quad included), MZLC_NO_KEEP_TILES=1 (the tiled stages' input tiles gathered again for the weight gradient instead of kept
  *              from the forward pass), MZLC_WGRAD_MIN_IPW=n (least images per weight-gradient workgroup), MZLC_DEFER_WGRAD=0 / 1 (the shared towers' block layers take their weight
  *              gradient per unroll step / in one launch per layer over all steps; default: one launch where a step's batch is at most four staging rounds per
- *              workgroup), MZLC_WGRAD_SG=n (at most n images per staging round) */
+ *              workgroup), MZLC_WGRAD_SG=n (at most n images per staging round), MZLC_WGRAD_SG_MAX=1 (as many images per staging round as fit, whatever
+ *              the batch, instead of the count with the shortest launch at max_batch), MZLC_NO_GATHER_XCD=1 (the Atari net's tile-gather workgroups in
+ *              launch order instead of neighbouring tiles on one XCD) */
 
 int mzl_create(const mzl_config* cfg, int device_id, mz_learner** out);
 int mzl_destroy(mz_learner* h);

@@ -87,20 +87,24 @@ int cdiv(int a, int b) { return (a + b - 1) / b; }
 // the tiling is then chosen by the time of one launch, (rounds of workgroups over the CUs) x (tiles per workgroup), `wg_per_group` workgroups
 // per image group (output-channel blocks x paired jobs): at batch 128 a 6 x 6 hidden state packs best as 4 images in 9 tiles, but that is 128
 // workgroups on 256 CUs, and 2 images in 6 tiles fills the chip in 2/3 of the time.  Ties / images == 0: the densest packing.
-// how make_geom picks the weight-gradient kernel's images per staging round: creation-time switches (wgrad_pick_env) or, for mzlc_debug_wgrad, arguments
+// how make_geom picks the weight-gradient kernel's images per staging round: creation-time switches (the handle's CreateSwitches::pick) or, for
+// mzlc_debug_wgrad, arguments over them
 struct WgradPick {
     bool stack_rows = false;  // MZLC_STACK_ROWS
     int sg_cap = 16;          // MZLC_WGRAD_SG
     bool sg_max = false;      // MZLC_WGRAD_SG_MAX: as many as fit, whatever the batch
     int sg_force = 0;         // > 0: exactly this many or no geometry (never from the environment)
 };
-WgradPick wgrad_pick_env() {
-    WgradPick p;
-    p.stack_rows = getenv("MZLC_STACK_ROWS") != nullptr;
-    if (const char* m = getenv("MZLC_WGRAD_SG")) p.sg_cap = atoi(m);
-    p.sg_max = getenv("MZLC_WGRAD_SG_MAX") != nullptr;
-    return p;
-}
+// the creation-time switches that are consulted after mzlc_create -- by the geometry (hidden_geom) and the tile gather -- or late in it: read once
+// (read_switches), never written by a hook
+struct CreateSwitches {
+    bool dense_tiling = false;  // MZLC_DENSE_TILING=1: the towers' pixel tiling by densest packing, not by launch time at the batch
+    bool wgrad_stack = true;    // MZLC_NO_WGRAD_STACK=1: one image per weight-gradient staging round
+    bool gather_xcd = true;     // MZLC_NO_GATHER_XCD=1: k_lc_tile_gather's workgroups in launch order
+    int defer_wgrad = -1;       // MZLC_DEFER_WGRAD=0 / 1 over mzlc_create's own decision (mzlc_learner::defer_wgrad); -1: not set
+    WgradPick pick;
+    int images(int batch) const { return dense_tiling ? 0 : batch; }  // make_geom's `images` for a batch
+};
 bool make_geom(Geom& g, int hh, int ww, bool allow_side15, const WgradPick& pick, int images = 0, int wg_per_group = 1, int cus = 256, bool stack_wgrad = true,
                bool allow16 = false, int wgrad_blocks = 0) {
     g.h = hh; g.w = ww; g.hw = hh * ww;
@@ -201,6 +205,7 @@ struct mzlc_learner {
     int device = 0, num_cus = 256;
     int P = 0, C0 = 0, A = 0, R = 0, K = 0, h = 0, w = 0, hw = 0, maxB = 0;
     Geom gm;                 // geometry of the hidden state (the board; 6 x 6 for the Atari net)
+    CreateSwitches sw;       // what built it, and builds the hooks' geometries (hidden_geom)
     int wgrad_min_ipw = 1;   // k_lc_wgrad: least images per workgroup (small images: the partial tile's write-out amortised over more of them)
     bool xcd_remap = true;   // k_lc_wgrad: the blocks of one image chunk on one XCD (MZLC_NO_XCD_REMAP=1 at create: launch order)
     bool fuse_apply = true;  // block outputs formed in the next conv's staging (MZLC_NO_FUSE_APPLY=1 at create: one k_lc_apply per block)
@@ -624,80 +629,83 @@ struct Sched {
     }
 };
 
-template <int NPT, int SIDE>
-void launch_conv(int mode, const Pair<LcConv>& pj, dim3 grid, size_t lds, hipStream_t st) {
-    if (mode == IN_IDENT) hipLaunchKernelGGL((k_lc_conv<NPT, IN_IDENT, SIDE>), grid, dim3(256), lds, st, pj);
-    else if (mode == IN_BNRELU) hipLaunchKernelGGL((k_lc_conv<NPT, IN_BNRELU, SIDE>), grid, dim3(256), lds, st, pj);
-    else if (mode == IN_BNRES) hipLaunchKernelGGL((k_lc_conv<NPT, IN_BNRES, SIDE>), grid, dim3(256), lds, st, pj);
-    else hipLaunchKernelGGL((k_lc_conv<NPT, IN_BNBWD, SIDE>), grid, dim3(256), lds, st, pj);
+// ---- the kernel builds -------------------------------------------------------------------------------------------------------
+// Every instantiation of k_lc_conv / k_lc_conv_bf16x3 and of k_lc_wgrad / k_lc_wgrad_bf16x3 the library holds, one entry each: launch_ops looks a
+// job's build up by its key and launches it by pointer, mzlc_create raises the dynamic-LDS limit of every entry.  A job without an entry is refused.
+struct ConvBuild {
+    bool split;       // k_lc_conv_bf16x3 (a split layer's job: Op::split)
+    int npt, in_mode;
+    int side;         // 15: the 15 x 15 build
+    int tapmask;      // 0x1ff, or the tap set of a parity plane (par_tapmap): forward rows {1} | {0, 1}, data-gradient rows {1} | {1, 2}, squared
+    bool halo;        // split builds: the HALO template parameter (LcConv::halo_in; the float32 kernel reads that field at run time)
+    bool plane;       // the PLANE build (LcConv::out_plane)
+    bool unpaired;    // built for one job per launch only
+    bool needs_halo;  // float32: computes the inner positions of a haloed tile only -- the job must carry halo_in
+    const void* fn;
+};
+#define MZ_CB(SPLIT, NPT, MODE, SIDE, MASK, HALO, PLANE, UNPAIRED, NEEDS_HALO, ...) \
+    {SPLIT, NPT, MODE, SIDE, MASK, HALO, PLANE, UNPAIRED, NEEDS_HALO, reinterpret_cast<const void*>(&__VA_ARGS__)}
+#define MZ_CF(NPT, MODE, SIDE) MZ_CB(false, NPT, MODE, SIDE, 0x1ff, false, false, false, false, k_lc_conv<NPT, MODE, SIDE>)
+#define MZ_CF4(NPT, SIDE) MZ_CF(NPT, IN_IDENT, SIDE), MZ_CF(NPT, IN_BNRELU, SIDE), MZ_CF(NPT, IN_BNBWD, SIDE), MZ_CF(NPT, IN_BNRES, SIDE)
+#define MZ_CS(NPT, MODE, SIDE) MZ_CB(true, NPT, MODE, SIDE, 0x1ff, false, false, false, false, k_lc_conv_bf16x3<NPT, MODE, SIDE>)
+#define MZ_CS4(NPT, SIDE) MZ_CS(NPT, IN_IDENT, SIDE), MZ_CS(NPT, IN_BNRELU, SIDE), MZ_CS(NPT, IN_BNBWD, SIDE), MZ_CS(NPT, IN_BNRES, SIDE)
+#define MZ_CT(NPT, MASK) MZ_CB(false, NPT, IN_IDENT, 0, MASK, false, false, true, false, k_lc_conv<NPT, IN_IDENT, 0, MASK>)
+#define MZ_CP(NPT) MZ_CB(false, NPT, IN_IDENT, 0, 0x1ff, false, true, true, true, k_lc_conv<NPT, IN_IDENT, 0, 0x1ff, true>)
+#define MZ_CH(NPT, PLANE) MZ_CB(true, NPT, IN_IDENT, 0, 0x1ff, true, PLANE, true, false, k_lc_conv_bf16x3<NPT, IN_IDENT, 0, true, PLANE>)
+const ConvBuild kConvBuilds[] = {
+    // whole images at the tilings make_geom picks, the four staging modes: float32, then conv_precision bf16x3's (mz_learn_conv_split.h)
+    MZ_CF4(15, 15), MZ_CF4(15, 0), MZ_CF4(13, 0), MZ_CF4(9, 0), MZ_CF4(6, 0), MZ_CF4(5, 0),
+    MZ_CS4(15, 15), MZ_CS4(15, 0), MZ_CS4(13, 0), MZ_CS4(9, 0), MZ_CS4(6, 0), MZ_CS4(5, 0),
+    // the parity planes of the Atari net's stride-2 convs on their own taps: whole gathered tiles, identity staging, float32 only
+    // (the data-gradient sets exist for conv_2 only: 24 x 24 planes, 12 x 12 tiles -- no NPT 16)
+    MZ_CT(13, 0x010), MZ_CT(13, 0x018), MZ_CT(13, 0x012), MZ_CT(13, 0x01b), MZ_CT(13, 0x030), MZ_CT(13, 0x090), MZ_CT(13, 0x1b0),
+    MZ_CT(15, 0x010), MZ_CT(15, 0x018), MZ_CT(15, 0x012), MZ_CT(15, 0x01b), MZ_CT(15, 0x030), MZ_CT(15, 0x090), MZ_CT(15, 0x1b0),
+    MZ_CT(16, 0x010), MZ_CT(16, 0x018), MZ_CT(16, 0x012), MZ_CT(16, 0x01b),
+    // a gathered wide tile as a whole 14 x 18 image (identity staging)
+    MZ_CF(16, IN_IDENT, 0), MZ_CS(16, IN_IDENT, 0),
+    // the tile path's stride-1 convs over the inner 12 x 12 / 12 x 16 of a haloed tile: into inner-only tiles, or (PLANE) straight into the plane
+    MZ_CB(false, 12, IN_IDENT, 0, 0x1ff, false, false, true, true, k_lc_conv<12, IN_IDENT, 0>),  // (NPT 9 without PLANE: the whole-image build above)
+    MZ_CP(9), MZ_CP(12),
+    MZ_CH(9, false), MZ_CH(9, true), MZ_CH(12, false), MZ_CH(12, true),
+};
+#undef MZ_CH
+#undef MZ_CP
+#undef MZ_CT
+#undef MZ_CS4
+#undef MZ_CS
+#undef MZ_CF4
+#undef MZ_CF
+#undef MZ_CB
+const ConvBuild* conv_find(bool split, int npt, int in_mode, int side, int tapmask, bool halo, bool plane) {
+    for (const ConvBuild& b : kConvBuilds)
+        if (b.split == split && b.npt == npt && b.in_mode == in_mode && b.side == side && b.tapmask == tapmask && b.halo == halo && b.plane == plane) return &b;
+    return nullptr;
 }
-// conv_precision bf16x3: the same jobs on the split-bf16 builds (mz_learn_conv_split.h)
-template <int NPT, int SIDE>
-void launch_conv_split(int mode, const Pair<LcConv>& pj, dim3 grid, size_t lds, hipStream_t st) {
-    if (mode == IN_IDENT) hipLaunchKernelGGL((k_lc_conv_bf16x3<NPT, IN_IDENT, SIDE>), grid, dim3(256), lds, st, pj);
-    else if (mode == IN_BNRELU) hipLaunchKernelGGL((k_lc_conv_bf16x3<NPT, IN_BNRELU, SIDE>), grid, dim3(256), lds, st, pj);
-    else if (mode == IN_BNRES) hipLaunchKernelGGL((k_lc_conv_bf16x3<NPT, IN_BNRES, SIDE>), grid, dim3(256), lds, st, pj);
-    else hipLaunchKernelGGL((k_lc_conv_bf16x3<NPT, IN_BNBWD, SIDE>), grid, dim3(256), lds, st, pj);
-}
-template <int NPT, int SIDE>
-hipError_t conv_split_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<NPT, IN_IDENT, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<NPT, IN_BNRELU, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<NPT, IN_BNBWD, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<NPT, IN_BNRES, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return e;
-}
-// the tap sets of the parity planes (par_tapmap): forward rows {1} | {0, 1}, data-gradient rows {1} | {1, 2}, squared
-template <int NPT, int MASK>
-void launch_conv_taps(const Pair<LcConv>& pj, dim3 grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_lc_conv<NPT, IN_IDENT, 0, MASK>), grid, dim3(256), lds, st, pj);
-}
-// (the data-gradient planes exist for conv_2 only: 24 x 24 planes, 12 x 12 tiles, NPT 15)
-bool launch_conv_tapmask(int npt, int mask, const Pair<LcConv>& pj, dim3 grid, size_t lds, hipStream_t st) {
-    if (npt == 16) {
-        switch (mask) {
-            case 0x010: launch_conv_taps<16, 0x010>(pj, grid, lds, st); return true;
-            case 0x018: launch_conv_taps<16, 0x018>(pj, grid, lds, st); return true;
-            case 0x012: launch_conv_taps<16, 0x012>(pj, grid, lds, st); return true;
-            case 0x01b: launch_conv_taps<16, 0x01b>(pj, grid, lds, st); return true;
-        }
-        return false;
-    }
-    if (npt == 13) {
-        switch (mask) {
-            case 0x010: launch_conv_taps<13, 0x010>(pj, grid, lds, st); return true;
-            case 0x018: launch_conv_taps<13, 0x018>(pj, grid, lds, st); return true;
-            case 0x012: launch_conv_taps<13, 0x012>(pj, grid, lds, st); return true;
-            case 0x01b: launch_conv_taps<13, 0x01b>(pj, grid, lds, st); return true;
-            case 0x030: launch_conv_taps<13, 0x030>(pj, grid, lds, st); return true;
-            case 0x090: launch_conv_taps<13, 0x090>(pj, grid, lds, st); return true;
-            case 0x1b0: launch_conv_taps<13, 0x1b0>(pj, grid, lds, st); return true;
-        }
-        return false;
-    }
-    if (npt != 15) return false;
-    switch (mask) {
-        case 0x010: launch_conv_taps<15, 0x010>(pj, grid, lds, st); return true;
-        case 0x018: launch_conv_taps<15, 0x018>(pj, grid, lds, st); return true;
-        case 0x012: launch_conv_taps<15, 0x012>(pj, grid, lds, st); return true;
-        case 0x01b: launch_conv_taps<15, 0x01b>(pj, grid, lds, st); return true;
-        case 0x030: launch_conv_taps<15, 0x030>(pj, grid, lds, st); return true;
-        case 0x090: launch_conv_taps<15, 0x090>(pj, grid, lds, st); return true;
-        case 0x1b0: launch_conv_taps<15, 0x1b0>(pj, grid, lds, st); return true;
-    }
-    return false;
-}
-template <int NPT, int MASK>
-hipError_t conv_taps_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<NPT, IN_IDENT, 0, MASK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-template <int NPT, int SIDE>
-hipError_t conv_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<NPT, IN_IDENT, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<NPT, IN_BNRELU, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<NPT, IN_BNBWD, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<NPT, IN_BNRES, SIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return e;
+
+struct WgradBuild {
+    bool split;   // k_lc_wgrad_bf16x3 (mzlc_set_wgrad_precision)
+    bool act;     // action planes inside the MFMA kernel
+    bool ring;    // the tile path: the dy tiles' ring zeroed (LcWgrad::ring_zero)
+    int tapmask;  // 0x1ff, or a parity plane's forward tap set
+    const void* fn;
+    const char* name;  // what mzlc_debug_wgrad reports
+};
+#define MZ_WB(SPLIT, ACT, RING, MASK, NAME, ...) {SPLIT, ACT, RING, MASK, reinterpret_cast<const void*>(&__VA_ARGS__), NAME}
+#define MZ_WT(MASK) MZ_WB(false, false, true, MASK, "k_lc_wgrad<ACT=0,RING=1,TAPS>", k_lc_wgrad<false, true, MASK>)
+const WgradBuild kWgradBuilds[] = {
+    MZ_WB(false, false, false, 0x1ff, "k_lc_wgrad<ACT=0,RING=0>", k_lc_wgrad<false, false>),
+    MZ_WB(false, true, false, 0x1ff, "k_lc_wgrad<ACT=1,RING=0>", k_lc_wgrad<true, false>),
+    MZ_WB(false, false, true, 0x1ff, "k_lc_wgrad<ACT=0,RING=1>", k_lc_wgrad<false, true>),
+    MZ_WT(0x010), MZ_WT(0x018), MZ_WT(0x012), MZ_WT(0x01b),
+    MZ_WB(true, false, false, 0x1ff, "k_lc_wgrad_bf16x3<ACT=0>", k_lc_wgrad_bf16x3<false>),
+    MZ_WB(true, true, false, 0x1ff, "k_lc_wgrad_bf16x3<ACT=1>", k_lc_wgrad_bf16x3<true>),
+};
+#undef MZ_WT
+#undef MZ_WB
+const WgradBuild* wgrad_find(bool split, bool act, bool ring, int tapmask) {
+    for (const WgradBuild& b : kWgradBuilds)
+        if (b.split == split && b.act == act && b.ring == ring && b.tapmask == tapmask) return &b;
+    return nullptr;
 }
 
 int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
@@ -721,52 +729,19 @@ int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
             if (b) { z = cdiv(b->conv.co_tiles, 4) > z ? cdiv(b->conv.co_tiles, 4) : z; cp = b->conv.cpad_in > cp ? b->conv.cpad_in : cp; }
             const dim3 grid(1, ga + gb, z);
             const size_t lds = conv_lds(a->conv.qstride, cp);
-            const int mode = a->conv.in_mode;
-            if (a->split) {  // a split layer: the towers' whole images (nine taps, the tilings make_geom picks) or the Atari net's stride-1 tile path
-                if (a->conv.tapmask && a->conv.tapmask != 0x1ff) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                const size_t slds = conv_split_lds(a->conv.G, a->conv.h, a->conv.w_img, cp);
-                if (a->conv.halo_in) {  // the inner 12 x 16 / 12 x 12 of a haloed tile, into planes (out_plane) or inner-only tiles: the float32 dispatcher's conditions
-                    if (mode != IN_IDENT || b || a->side15 || (a->npt != 9 && a->npt != 12) || a->conv.G != 1 || a->conv.action) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                    if (a->conv.out_plane && a->npt == 12) hipLaunchKernelGGL((k_lc_conv_bf16x3<12, IN_IDENT, 0, true, true>), grid, dim3(256), slds, st, pj);
-                    else if (a->conv.out_plane) hipLaunchKernelGGL((k_lc_conv_bf16x3<9, IN_IDENT, 0, true, true>), grid, dim3(256), slds, st, pj);
-                    else if (a->npt == 12) hipLaunchKernelGGL((k_lc_conv_bf16x3<12, IN_IDENT, 0, true, false>), grid, dim3(256), slds, st, pj);
-                    else hipLaunchKernelGGL((k_lc_conv_bf16x3<9, IN_IDENT, 0, true, false>), grid, dim3(256), slds, st, pj);
-                } else
-                if (a->conv.out_plane) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                else if (a->npt == 16) {  // a gathered wide tile as a whole 14 x 18 image (identity staging)
-                    if (mode != IN_IDENT) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                    hipLaunchKernelGGL((k_lc_conv_bf16x3<16, IN_IDENT, 0>), grid, dim3(256), slds, st, pj);
-                } else
-                if (a->npt == 15 && a->side15) launch_conv_split<15, 15>(mode, pj, grid, slds, st);
-                else if (a->npt == 15) launch_conv_split<15, 0>(mode, pj, grid, slds, st);
-                else if (a->npt == 13) launch_conv_split<13, 0>(mode, pj, grid, slds, st);
-                else if (a->npt == 9) launch_conv_split<9, 0>(mode, pj, grid, slds, st);
-                else if (a->npt == 6) launch_conv_split<6, 0>(mode, pj, grid, slds, st);
-                else if (a->npt == 5) launch_conv_split<5, 0>(mode, pj, grid, slds, st);
-                else { h->bad_dispatch = true; return MZL_E_INVALID; }
-            } else
-            if (a->conv.tapmask && a->conv.tapmask != 0x1ff) {  // (a parity plane: built as whole-tile, identity-mode, unpaired launches only)
-                if (b || a->side15 || mode != IN_IDENT || !launch_conv_tapmask(a->npt, a->conv.tapmask, pj, grid, lds, st)) { h->bad_dispatch = true; return MZL_E_INVALID; }
-            } else
-            if (a->conv.out_plane) {  // the tile path's stride-1 convs writing planes (halo_in; 12 x 12 or 12 x 16 inner positions)
-                if (mode != IN_IDENT || b || !a->conv.halo_in || (a->npt != 9 && a->npt != 12)) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                if (a->npt == 12) hipLaunchKernelGGL((k_lc_conv<12, IN_IDENT, 0, 0x1ff, true>), grid, dim3(256), lds, st, pj);
-                else hipLaunchKernelGGL((k_lc_conv<9, IN_IDENT, 0, 0x1ff, true>), grid, dim3(256), lds, st, pj);
-            } else
-            if (a->npt == 16) {  // the wide tiles of the Atari net (gathered: identity staging)
-                if (mode != IN_IDENT) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                hipLaunchKernelGGL((k_lc_conv<16, IN_IDENT, 0>), grid, dim3(256), lds, st, pj);
-            } else
-            if (a->npt == 12) {  // the inner 12 x 16 of a wide tile (halo_in)
-                if (mode != IN_IDENT || b || !a->conv.halo_in) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                hipLaunchKernelGGL((k_lc_conv<12, IN_IDENT, 0>), grid, dim3(256), lds, st, pj);
-            } else
-            if (a->npt == 15 && a->side15) launch_conv<15, 15>(mode, pj, grid, lds, st);
-            else if (a->npt == 15) launch_conv<15, 0>(mode, pj, grid, lds, st);
-            else if (a->npt == 13) launch_conv<13, 0>(mode, pj, grid, lds, st);
-            else if (a->npt == 9) launch_conv<9, 0>(mode, pj, grid, lds, st);
-            else if (a->npt == 6) launch_conv<6, 0>(mode, pj, grid, lds, st);
-            else launch_conv<5, 0>(mode, pj, grid, lds, st);
+            // the build's key.  A split layer: the towers' whole images or the stride-1 tile path (HALO), nine taps only.  Float32: halo_in is a
+            // run-time field, and a parity plane (its own tap set) is a whole tile, never a PLANE build.  SIDE is the 15 x 15 board's at NPT 15 alone.
+            const int taps = a->conv.tapmask ? a->conv.tapmask : 0x1ff;
+            const bool halo_in = a->conv.halo_in != 0, out_plane = a->conv.out_plane != 0;
+            const ConvBuild* cb = conv_find(a->split, a->npt, a->conv.in_mode, (a->npt == 15 && a->side15) ? 15 : 0, taps, a->split && halo_in,
+                                            a->split ? out_plane : (out_plane && taps == 0x1ff));
+            if (!cb || (cb->unpaired && b) || (cb->needs_halo && !halo_in) || ((cb->halo || taps != 0x1ff) && a->side15) ||
+                (cb->halo && (a->conv.G != 1 || a->conv.action))) {  // (HALO stages one gathered tile per workgroup, without action planes)
+                h->bad_dispatch = true;
+                return MZL_E_INVALID;
+            }
+            void* args[] = {&pj};
+            (void)hipLaunchKernel(cb->fn, grid, dim3(256), args, a->split ? conv_split_lds(a->conv.G, a->conv.h, a->conv.w_img, cp) : lds, st);
             break;
         }
         case OP_WGRAD: {
@@ -781,33 +756,18 @@ int launch_ops(mzlc_learner* h, const Op* a, const Op* b, hipStream_t st) {
             // a chunk's blocks on one XCD (k_lc_wgrad): needs the same block grid in both jobs and a group count the 8 XCDs divide
             const int groups = (ya + yb) / a->wg.co_blocks;
             pj.remap = (h->xcd_remap && (!b || (b->wg.co_blocks == a->wg.co_blocks && cdiv(b->wg.ci_tiles, 2) == cdiv(a->wg.ci_tiles, 2))) && groups % 8 == 0) ? 1 : 0;
-            const size_t wlds = ((size_t)32 * (a->wg.SPY + a->wg.SPX) + 160) * sizeof(float);
+            const size_t wlds = h->wsplit ? wgrad_split_lds(a->wg.SPY, a->wg.SPX) : ((size_t)32 * (a->wg.SPY + a->wg.SPX) + 160) * sizeof(float);
             const dim3 wgrid(x, ya + yb);
             h->dbg_wgrad_remap = pj.remap;  // (mzlc_debug_wgrad reports the build and the placement that ran)
-            if (h->wsplit) {  // a board net's towers: whole images, nine taps, no ring (make_geom_wsplit's planes)
-                if (a->wg.ring_zero || (a->wg.tapmask && a->wg.tapmask != 0x1ff) || (a->wg.P4 & 7)) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                const size_t slds = wgrad_split_lds(a->wg.SPY, a->wg.SPX);
-                const bool act = a->wg.action || (b && b->wg.action);
-                h->dbg_wgrad_build = act ? "k_lc_wgrad_bf16x3<ACT=1>" : "k_lc_wgrad_bf16x3<ACT=0>";
-                if (act) hipLaunchKernelGGL((k_lc_wgrad_bf16x3<true>), wgrid, dim3(256), slds, st, pj);
-                else hipLaunchKernelGGL((k_lc_wgrad_bf16x3<false>), wgrid, dim3(256), slds, st, pj);
-                break;
-            }
-            h->dbg_wgrad_build = (a->wg.tapmask && a->wg.tapmask != 0x1ff) ? "k_lc_wgrad<ACT=0,RING=1,TAPS>" : a->wg.ring_zero ? "k_lc_wgrad<ACT=0,RING=1>"
-                                 : (a->wg.action || (b && b->wg.action)) ? "k_lc_wgrad<ACT=1,RING=0>" : "k_lc_wgrad<ACT=0,RING=0>";
-            if (a->wg.tapmask && a->wg.tapmask != 0x1ff) {  // a parity plane (tile path: ring_zero, no action planes, unpaired)
-                if (b || !a->wg.ring_zero || a->wg.action) { h->bad_dispatch = true; return MZL_E_INVALID; }
-                switch (a->wg.tapmask) {
-                    case 0x010: hipLaunchKernelGGL((k_lc_wgrad<false, true, 0x010>), wgrid, dim3(256), wlds, st, pj); break;
-                    case 0x018: hipLaunchKernelGGL((k_lc_wgrad<false, true, 0x018>), wgrid, dim3(256), wlds, st, pj); break;
-                    case 0x012: hipLaunchKernelGGL((k_lc_wgrad<false, true, 0x012>), wgrid, dim3(256), wlds, st, pj); break;
-                    case 0x01b: hipLaunchKernelGGL((k_lc_wgrad<false, true, 0x01b>), wgrid, dim3(256), wlds, st, pj); break;
-                    default: h->bad_dispatch = true; return MZL_E_INVALID;
-                }
-            } else
-            if (a->wg.ring_zero) hipLaunchKernelGGL((k_lc_wgrad<false, true>), dim3(x, ya + yb), dim3(256), wlds, st, pj);
-            else if (a->wg.action || (b && b->wg.action)) hipLaunchKernelGGL((k_lc_wgrad<true, false>), dim3(x, ya + yb), dim3(256), wlds, st, pj);
-            else hipLaunchKernelGGL((k_lc_wgrad<false, false>), dim3(x, ya + yb), dim3(256), wlds, st, pj);
+            // the build's key.  The tile path (ring_zero) has no action planes: its nine-tap build never looks at them, a parity plane's (its own tap
+            // set: unpaired) refuses them.  The split builds are a board net's towers: whole images, nine taps, no ring, make_geom_wsplit's pitch
+            const int taps = a->wg.tapmask ? a->wg.tapmask : 0x1ff;
+            const bool ring = a->wg.ring_zero != 0, act = (a->wg.action || (b && b->wg.action)) && !(ring && taps == 0x1ff);
+            const WgradBuild* wb = wgrad_find(h->wsplit, act, ring, taps);
+            if (!wb || (taps != 0x1ff && b) || (h->wsplit && (a->wg.P4 & 7))) { h->bad_dispatch = true; return MZL_E_INVALID; }
+            h->dbg_wgrad_build = wb->name;
+            void* args[] = {&pj};
+            (void)hipLaunchKernel(wb->fn, wgrid, dim3(256), args, wlds, st);
             break;
         }
         case OP_WGRAD_ACT: {
@@ -951,8 +911,7 @@ struct AtariRun {
         g.src0 = src0; g.src1 = src1; g.coef = coef; g.dst = dst; g.mode = mode; g.B = B; g.C = C; g.cpad = pad16(C); g.H = H; g.W = W;
         g.srcH = srcH; g.srcW = srcW; g.sy = sy; g.sx = sx; g.py = py; g.px = px; g.Ty = TILE; g.Tx = tw; g.nty = H / TILE; g.ntx = W / tw; g.inner_only = inner_only;
         g.n = (long long)B * g.nty * g.ntx * C * ts2;
-        static const bool xcd = !getenv("MZLC_NO_GATHER_XCD");
-        g.xcd = xcd ? 1 : 0;
+        g.xcd = h->sw.gather_xcd ? 1 : 0;
         const dim3 grid((unsigned)(B * g.nty * g.ntx), (unsigned)cdiv(C * ts2, 1024));
         if (tw == 16) hipLaunchKernelGGL((k_lc_tile_gather<TILE + 2, 18>), grid, dim3(256), 0, st, g);
         else hipLaunchKernelGGL((k_lc_tile_gather<TILE + 2, TILE + 2>), grid, dim3(256), 0, st, g);
@@ -1303,21 +1262,14 @@ void atari_rep_bwd(mzlc_learner* h, int B, const float* gs0, hipStream_t st) {
     }
 }
 
-}  // namespace
-
-// =================================================================================================================================
-int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner** out, std::string& err) {
-    mzlc_learner* h = new mzlc_learner();
-    h->cfg = *cfg; h->device = device_id; h->num_cus = num_cus > 0 ? num_cus : 256;
-    h->P = cfg->num_planes; h->C0 = cfg->in_channels; h->A = cfg->num_actions; h->R = cfg->num_res_blocks; h->K = cfg->unroll_steps;
-    h->atari = cfg->net_kind == MZL_NET_ATARI;
-    h->maxB = cfg->max_batch;
+// every environment switch of the conv learner (include/mzlearner.h lists them), read ONCE: mzlc_create calls this and nothing else asks the environment
+void read_switches(mzlc_learner* h) {
     h->paired = !getenv("MZLC_NO_PAIR");
-    h->split = cfg->conv_precision == MZL_CONV_BF16X3;
     h->allow_side = !getenv("MZLC_NO_SIDE");
     h->fuse_apply = !getenv("MZLC_NO_FUSE_APPLY");
     h->xcd_remap = !getenv("MZLC_NO_XCD_REMAP");
     h->par_compact = !getenv("MZLC_NO_TAPSETS");
+    h->wide_tiles = !getenv("MZLC_NO_WIDE_TILES");
     h->halo_in = !getenv("MZLC_NO_HALO_IN");
     h->ring_rows = !getenv("MZLC_NO_RING_ROWS");
     h->keep_tiles = !getenv("MZLC_NO_KEEP_TILES");
@@ -1328,6 +1280,41 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
     h->skip_h1 = h->out_plane && h->fuse_entry && h->keep_tiles && !getenv("MZLC_KEEP_H1");
     h->act_sparse = !getenv("MZLC_ACT_MFMA") && h->A <= 256;
     if (const char* m = getenv("MZLC_WGRAD_MIN_IPW")) h->wgrad_min_ipw = atoi(m) > 0 ? atoi(m) : 1;
+    CreateSwitches& s = h->sw;
+    s.dense_tiling = getenv("MZLC_DENSE_TILING") != nullptr;
+    s.wgrad_stack = !getenv("MZLC_NO_WGRAD_STACK");
+    s.gather_xcd = !getenv("MZLC_NO_GATHER_XCD");
+    if (const char* m = getenv("MZLC_DEFER_WGRAD")) s.defer_wgrad = atoi(m) != 0 ? 1 : 0;
+    s.pick.stack_rows = getenv("MZLC_STACK_ROWS") != nullptr;
+    if (const char* m = getenv("MZLC_WGRAD_SG")) s.pick.sg_cap = atoi(m);
+    s.pick.sg_max = getenv("MZLC_WGRAD_SG_MAX") != nullptr;
+}
+
+// The geometry of bh x bw images on the towers' path (the hidden state; a hook's own image) as the handle's creation-time switches make it:
+// make_geom for `images` (0: no batch, the densest packing -- CreateSwitches::images(batch) follows MZLC_DENSE_TILING) and a layer of cout x cin
+// channels (its workgroups per image group, paired, and its weight-gradient blocks), then -- wsplit -- make_geom_wsplit's weight-gradient fields
+// over it.  `pick`: the handle's (h->sw.pick) or a hook's override of it; with wsplit a forced SG is judged by the split planes' budget alone,
+// not by the float32 planes' that make_geom fills first.  0: fits; 1: make_geom refused; 2: make_geom_wsplit refused
+int hidden_geom(const mzlc_learner* h, Geom& g, int bh, int bw, int images, bool allow_side, const WgradPick& pick, int cout, int cin, bool wsplit) {
+    const int wgrad_blocks = cdiv(cdiv(cout, 16), 2) * cdiv(cdiv(cin, 16), 2);
+    WgradPick pick32 = pick;
+    if (wsplit) pick32.sg_force = 0;
+    if (!make_geom(g, bh, bw, allow_side, pick32, images, cdiv(cdiv(cout, 16), 4) * 2, h->num_cus, h->sw.wgrad_stack, false, wgrad_blocks)) return 1;
+    if (wsplit && !make_geom_wsplit(g, pick, images, h->num_cus, h->sw.wgrad_stack, wgrad_blocks)) return 2;
+    return 0;
+}
+
+}  // namespace
+
+// =================================================================================================================================
+int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner** out, std::string& err) {
+    mzlc_learner* h = new mzlc_learner();
+    h->cfg = *cfg; h->device = device_id; h->num_cus = num_cus > 0 ? num_cus : 256;
+    h->P = cfg->num_planes; h->C0 = cfg->in_channels; h->A = cfg->num_actions; h->R = cfg->num_res_blocks; h->K = cfg->unroll_steps;
+    h->atari = cfg->net_kind == MZL_NET_ATARI;
+    h->maxB = cfg->max_batch;
+    h->split = cfg->conv_precision == MZL_CONV_BF16X3;
+    read_switches(h);
     auto bad = [&](const std::string& m) { err = m; mzlc_destroy(h); return MZL_E_INVALID; };
     if (h->atari) {  // the observation is board_h x board_w (96 x 96 in every reference configuration); the hidden state 1 / 16 of it
         h->obsH = cfg->board_h; h->obsW = cfg->board_w;
@@ -1347,13 +1334,11 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
         return bad("support sizes must be odd (or 1): the kernels take the expectation over the support with unit spacing, which linspace(-half, half, size) has at odd sizes only");
     if (h->hw > 240 || h->P > 1024) return bad("conv learner: boards up to 240 points and 1024 planes (larger nets train through muzero_amd.learner.train_step)");
     if (h->split && h->atari) return bad("conv_precision MZL_CONV_BF16X3 needs net_kind MZL_NET_BOARD: MZL_NET_ATARI has no split-bf16 builds");
-    if (!make_geom(h->gm, h->h, h->w, h->allow_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, cdiv(cdiv(h->P, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
-                   cdiv(cdiv(h->P, 16), 2) * cdiv(cdiv(h->P, 16), 2))) return bad("board does not fit the conv kernels' tiling");
+    if (hidden_geom(h, h->gm, h->h, h->w, h->sw.images(h->maxB), h->allow_side, h->sw.pick, h->P, h->P, false)) return bad("board does not fit the conv kernels' tiling");
     if (wgrad_lds(h->gm) > 160 * 1024 || conv_lds(h->gm.qstride, pad16(h->P + h->A)) > 160 * 1024) return bad("board too large for the conv learner's LDS layout");
     if (h->split && conv_split_lds(h->gm.G, h->h, h->w, pad16(h->P + h->A)) > 160 * 1024) return bad("conv_precision MZL_CONV_BF16X3: board too large for the split conv's LDS slab");
-    h->wide_tiles = !getenv("MZLC_NO_WIDE_TILES");
-    if (h->atari && (!make_geom(h->gt, TILE + 2, TILE + 2, false, wgrad_pick_env()) || !make_geom(h->g12, TILE, TILE, false, wgrad_pick_env()) ||
-                     !make_geom(h->gt16, TILE + 2, 18, false, wgrad_pick_env(), 0, 1, 256, true, true)))
+    if (h->atari && (!make_geom(h->gt, TILE + 2, TILE + 2, false, h->sw.pick) || !make_geom(h->g12, TILE, TILE, false, h->sw.pick) ||
+                     !make_geom(h->gt16, TILE + 2, 18, false, h->sw.pick, 0, 1, 256, true, true)))
         return bad("internal: tile geometry");
     if (h->atari && (wgrad_lds(h->gt16) > 80 * 1024 || h->gt16.npt != 16)) h->wide_tiles = false;  // (two weight-gradient workgroups per CU need their LDS)
     // ---- parameter / buffer tables in state_dict order (network.py:312-498) ----
@@ -1440,7 +1425,7 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
         chunks = chunks < 1 ? 1 : (chunks > h->maxB ? h->maxB : chunks);
         const int rounds = cdiv(cdiv(h->maxB, chunks), h->gm.SG);
         h->defer_wgrad = h->K > 1 && rounds <= 4 && h->tower[1].R > 0;
-        if (const char* m = getenv("MZLC_DEFER_WGRAD")) h->defer_wgrad = atoi(m) != 0 && h->K > 1 && h->tower[1].R > 0;
+        if (h->sw.defer_wgrad >= 0) h->defer_wgrad = h->sw.defer_wgrad != 0 && h->K > 1 && h->tower[1].R > 0;
     }
     for (int t = 0; t < h->K; t++)
         ok = ok && alloc_app(h, h->tower[1], h->app_dyn[t], h->T, h->defer_wgrad) && alloc_app(h, h->tower[2], h->app_pred[t], h->T, h->defer_wgrad);
@@ -1576,49 +1561,11 @@ int mzlc_create(const mzl_config* cfg, int device_id, int num_cus, mzlc_learner*
         mzlc_destroy(h);
         return MZL_E_HIP;
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<false, true, 0x010>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<false, true, 0x018>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<false, true, 0x012>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad<false, true, 0x01b>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = conv_attr<15, 15>();
-    if (e == hipSuccess) e = conv_attr<15, 0>();
-    if (e == hipSuccess) e = conv_attr<9, 0>();
-    if (e == hipSuccess) e = conv_attr<6, 0>();
-    if (e == hipSuccess) e = conv_attr<5, 0>();
-    if (e == hipSuccess) e = conv_attr<13, 0>();
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<9, IN_IDENT, 0, 0x1ff, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_conv<12, IN_IDENT, 0, 0x1ff, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x010>();
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x018>();
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x012>();
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x01b>();
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x030>();
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x090>();
-    if (e == hipSuccess) e = conv_taps_attr<13, 0x1b0>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x010>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x018>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x012>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x01b>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x030>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x090>();
-    if (e == hipSuccess) e = conv_taps_attr<15, 0x1b0>();
-    if (e == hipSuccess) e = conv_taps_attr<16, 0x1ff>();
-    if (e == hipSuccess) e = conv_taps_attr<12, 0x1ff>();
-    if (e == hipSuccess) e = conv_taps_attr<16, 0x010>();
-    if (e == hipSuccess) e = conv_taps_attr<16, 0x018>();
-    if (e == hipSuccess) e = conv_taps_attr<16, 0x012>();
-    if (e == hipSuccess) e = conv_taps_attr<16, 0x01b>();
-    if (h->split) {
-        if (e == hipSuccess) e = conv_split_attr<15, 15>();
-        if (e == hipSuccess) e = conv_split_attr<15, 0>();
-        if (e == hipSuccess) e = conv_split_attr<13, 0>();
-        if (e == hipSuccess) e = conv_split_attr<9, 0>();
-        if (e == hipSuccess) e = conv_split_attr<6, 0>();
-        if (e == hipSuccess) e = conv_split_attr<5, 0>();
-    }
+    // the dynamic-LDS limit of every build of the two tables (the split ones too: mzlc_set_wgrad_precision / mzlc_set_atari_precision may ask for them later)
+    hipError_t e = hipSuccess;
+    auto raise_lds = [&](const void* fn) { if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
+    for (const ConvBuild& b : kConvBuilds) raise_lds(b.fn);
+    for (const WgradBuild& b : kWgradBuilds) raise_lds(b.fn);
     if (e == hipSuccess) e = hipDeviceSynchronize();  // (dalloc's fills run on the NULL stream)
     if (e != hipSuccess) {
         err = std::string("conv learner init: ") + hipGetErrorString(e);
@@ -1667,41 +1614,14 @@ int mzlc_set_wgrad_precision(mzlc_learner* h, int precision, std::string& err) {
     if (h->atari) { err = "wgrad_precision: MZL_NET_ATARI has no split-bf16 weight gradient (its ring and tap-set builds are float32 only); the setter needs net_kind MZL_NET_BOARD"; return MZL_E_INVALID; }
     if (h->params) { err = "wgrad_precision is set after mzl_create and before mzl_bind"; return MZL_E_STATE; }
     Geom g;
-    if (!make_geom(g, h->h, h->w, h->allow_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, cdiv(cdiv(h->P, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
-                   cdiv(cdiv(h->P, 16), 2) * cdiv(cdiv(h->P, 16), 2))) { err = "wgrad_precision: internal: board geometry"; return MZL_E_INVALID; }
-    if (precision == MZL_WGRAD_BF16X3) {
-        if (!make_geom_wsplit(g, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : h->maxB, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), cdiv(cdiv(h->P, 16), 2) * cdiv(cdiv(h->P, 16), 2))) {
-            err = "wgrad_precision MZL_WGRAD_BF16X3: the split planes of this board do not fit the LDS";
-            return MZL_E_INVALID;
-        }
-        if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad_bf16x3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lc_wgrad_bf16x3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e); return MZL_E_HIP; }
-    }
+    const int fit = hidden_geom(h, g, h->h, h->w, h->sw.images(h->maxB), h->allow_side, h->sw.pick, h->P, h->P, precision == MZL_WGRAD_BF16X3);
+    if (fit == 1) { err = "wgrad_precision: internal: board geometry"; return MZL_E_INVALID; }
+    if (fit == 2) { err = "wgrad_precision MZL_WGRAD_BF16X3: the split planes of this board do not fit the LDS"; return MZL_E_INVALID; }
     h->gm = g;
     h->wsplit = precision == MZL_WGRAD_BF16X3;
     return MZL_OK;
 }
 int mzlc_wgrad_precision(const mzlc_learner* h) { return h->wsplit ? MZL_WGRAD_BF16X3 : MZL_WGRAD_F32; }
-
-namespace {
-// the dynamic-LDS limit of the split builds an Atari handle dispatches (towers: whole images at the tilings of gm and g12; tile path: HALO / PLANE builds)
-hipError_t atari_split_attrs() {
-    hipError_t e = conv_split_attr<9, 0>();
-    if (e == hipSuccess) e = conv_split_attr<6, 0>();
-    if (e == hipSuccess) e = conv_split_attr<5, 0>();
-    if (e == hipSuccess) e = conv_split_attr<13, 0>();
-    if (e == hipSuccess) e = conv_split_attr<15, 0>();
-    auto attr = [](const void* f) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
-    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<16, IN_IDENT, 0>));
-    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<12, IN_IDENT, 0, true, false>));
-    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<12, IN_IDENT, 0, true, true>));
-    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<9, IN_IDENT, 0, true, false>));
-    if (e == hipSuccess) e = attr(reinterpret_cast<const void*>(&k_lc_conv_bf16x3<9, IN_IDENT, 0, true, true>));
-    return e;
-}
-}  // namespace
 
 // The conv arithmetic of an Atari handle, per group of layers (before mzlc_bind): tower_precision -- res_blocks_3 (12 x 12) and the dynamics / prediction
 // towers (6 x 6), whole images; stage_precision -- res_blocks_1 / res_blocks_2, the tile path's stride-1 convs.  Forward convs and data gradients of
@@ -1751,7 +1671,6 @@ int mzlc_set_atari_precision(mzlc_learner* h, int tower_precision, int stage_pre
         hipError_t e = dalloc(h, &p3, words);
         if (e == hipSuccess) e = dalloc(h, &dj, jobs.size());
         if (e == hipSuccess) e = hipMemcpy(dj, jobs.data(), jobs.size() * sizeof(LcPackSplitJob), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = atari_split_attrs();
         if (e == hipSuccess) e = hipDeviceSynchronize();  // (dalloc's fills run on the NULL stream)
         if (e != hipSuccess) { err = std::string("mzl_set_atari_precision: ") + hipGetErrorString(e); return MZL_E_HIP; }
     }

@@ -181,7 +181,7 @@ int mzlc_debug_conv(mzlc_learner* h, int direction, int batch, int cin_real, int
     if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
     const int k_in = direction == 0 ? cin : cout, c_in_mem = direction == 0 ? cin_real : cout, c_out = direction == 0 ? cout : cin;
     Geom g;
-    if (!make_geom(g, bh, bw, h->allow_side, wgrad_pick_env(), batch, cdiv(cdiv(c_out, 16), 4), h->num_cus)) { err = "image does not fit the conv kernels' tiling"; return MZL_E_INVALID; }
+    if (!make_geom(g, bh, bw, h->allow_side, h->sw.pick, batch, cdiv(cdiv(c_out, 16), 4), h->num_cus)) { err = "image does not fit the conv kernels' tiling"; return MZL_E_INVALID; }
     const size_t lds = h->split ? conv_split_lds(g.G, bh, bw, pad16(c_in_mem)) : conv_lds(g.qstride, pad16(c_in_mem));
     if (lds > 160 * 1024) { err = "image too large for the conv kernel's LDS layout"; return MZL_E_INVALID; }
     const int hw = bh * bw, co_tiles = cdiv(c_out, 16), n_cb = cdiv(k_in, h->split ? 32 : 16);
@@ -269,7 +269,6 @@ int mzlc_debug_conv_tile(mzlc_learner* h, mzl_tile_call* c, const char** build_n
     if (c->mcoef) ok = ok && dc.up_rows(&d_mcoef, c->mcoef, c_out, cpo, 2, 2);
     if (c->part) ok = ok && dc.nanbuf(&d_part, (size_t)groups * cpo * 4);
     if (!ok) return dc.fail(MZL_E_HIP, "hipMalloc / hipMemcpy failed");
-    if (split && atari_split_attrs() != hipSuccess) return dc.fail(MZL_E_HIP, "hipFuncSetAttribute failed");
     if (!pack_one_layer(d_job, split, dg, c->cout, c->cin, n_cb, co_tiles, d_w, d_packed, st)) return dc.fail(MZL_E_HIP, "hipMemcpy failed");
     R.gather(d_in, nullptr, nullptr, IN_IDENT, c_in, H, W, H, W, 1, 1, 0, 0, 0, d_tiles);
     Op o = c->route == 0 ? R.conv_tiles_plane_op(L, dg, H, W, d_tiles, d_out, d_skip, d_part, d_mask, d_partner, d_mcoef) : R.conv_tiles_op(L, dg, H, W, d_tiles, d_tb);
@@ -376,7 +375,7 @@ int mzlc_debug_atari_stage(mzlc_learner* h, mzl_stage_call* c, const char** buil
         }
         const int npt = R.tgeom(W).npt;
         if (!built || h->bad_dispatch) {
-            dc.name(nullptr, "no kernel build: launch_conv_tapmask has none for NPT=%d (tile 12x%d) and the %s tap sets in the compact form", npt, tw, dg ? "data-gradient" : "forward");
+            dc.name(nullptr, "no kernel build: kConvBuilds has none for NPT=%d (tile 12x%d) and the %s tap sets in the compact form", npt, tw, dg ? "data-gradient" : "forward");
             return dc.fail(MZL_E_INVALID, h->debug_name.c_str());
         }
         if (!dc.ran()) return dc.fail(MZL_E_HIP, "the stride-2 conv failed to launch or run");
@@ -443,9 +442,8 @@ int mzlc_debug_atari_stage(mzlc_learner* h, mzl_stage_call* c, const char** buil
         if (!dc.ran()) return dc.fail(MZL_E_HIP, "k_lc_tile_gather failed to launch or run");
         if (!dc.down(c->out, d_out, n_t)) return dc.fail(MZL_E_HIP, "hipMemcpy failed");
         c->groups = B * nt;
-        static const bool xcd = !getenv("MZLC_NO_GATHER_XCD");
         dc.name(build_name, "k_lc_tile_gather tile=12x%d tiles=%d mode=%d stride=%d origin=(%d,%d) inner_only=%d remap=%d chunks=%d", tw, B * nt, c->mode, stride, c->py, c->px,
-                c->inner_only ? 1 : 0, (xcd && (B * nt) % 8 == 0) ? 1 : 0, cdiv(C * (int)ts2, 1024));
+                c->inner_only ? 1 : 0, (h->sw.gather_xcd && (B * nt) % 8 == 0) ? 1 : 0, cdiv(C * (int)ts2, 1024));
     } else {  // MZL_STAGE_SCATTER
         const size_t n_dst = n_plane * stride * stride, n_t = (size_t)B * nt * C * (c->src_inner ? (size_t)TILE * tw : ts2), n_stat = (size_t)B * cdiv(hw, 32) * cpad * 4;
         bool ok = dc.up(&d_in0, c->in0, n_t) && dc.nanbuf(&d_out, n_dst);
@@ -505,21 +503,17 @@ int mzlc_debug_wgrad(mzlc_learner* h, const mzl_wgrad_call* c, const char** buil
     } else if (c->ring_rows > 0 || (c->tapmask && c->tapmask != 0x1ff)) { err = "ring_rows / tap masks belong to mode ring"; return MZL_E_INVALID; }
     if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
 
-    // ---- geometry: make_geom as mzlc_create calls it (board: for this batch and this layer's block grid; ring: the tile geometries, no batch) ----
+    // ---- geometry: as mzlc_create builds it (board: hidden_geom for this batch and this layer's block grid; ring: the tile geometries, no batch) ----
     const mzl_wgrad_layer& J0 = c->layer[0];
-    WgradPick pick = wgrad_pick_env();
+    WgradPick pick = h->sw.pick;
     if (c->sg > 0) pick.sg_force = c->sg;
     if (c->layout) pick.stack_rows = c->layout == 2;
     Geom g;
-    bool fits;
-    WgradPick pick32 = pick;
-    if (h->wsplit) pick32.sg_force = 0;  // (the override is judged by the split planes' budget below, not by the float32 planes' that make_geom fills first)
-    if (mode == MZL_WGRAD_RING) fits = make_geom(g, bh, bw, false, pick, 0, 1, 256, true, bh * bw > 240);
-    else fits = make_geom(g, bh, bw, h->allow_side, pick32, B, cdiv(cdiv(J0.cout, 16), 4) * 2, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), false,
-                          cdiv(cdiv(J0.cout, 16), 2) * cdiv(cdiv(J0.cin_real, 16), 2));
-    if (!fits) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of two workgroups per CU do not hold that many images per round" : "image does not fit the kernels' geometry"; return MZL_E_INVALID; }
-    if (fits && h->wsplit) fits = make_geom_wsplit(g, pick, B, h->num_cus, !getenv("MZLC_NO_WGRAD_STACK"), cdiv(cdiv(J0.cout, 16), 2) * cdiv(cdiv(J0.cin_real, 16), 2));
-    if (!fits) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of one workgroup (160 KB of split planes) do not hold that many images per round" : "image does not fit the split weight gradient's planes"; return MZL_E_INVALID; }
+    int fit;
+    if (mode == MZL_WGRAD_RING) fit = make_geom(g, bh, bw, false, pick, 0, 1, 256, true, bh * bw > 240) ? 0 : 1;  // (an Atari handle: never wsplit)
+    else fit = hidden_geom(h, g, bh, bw, B, h->allow_side, pick, J0.cout, J0.cin_real, h->wsplit);
+    if (fit == 1) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of two workgroups per CU do not hold that many images per round" : "image does not fit the kernels' geometry"; return MZL_E_INVALID; }
+    if (fit == 2) { err = c->sg > 0 ? "SG override: the staging lanes (SG quads-per-image <= 64) or the LDS of one workgroup (160 KB of split planes) do not hold that many images per round" : "image does not fit the split weight gradient's planes"; return MZL_E_INVALID; }
     if ((h->wsplit ? wgrad_split_lds(g.SPY, g.SPX) : wgrad_lds(g)) > 160 * 1024) { err = "the weight-gradient planes of this geometry exceed the LDS"; return MZL_E_INVALID; }
 
     // ---- device buffers ----
@@ -662,10 +656,9 @@ int mzlc_debug_conv_fused(mzlc_learner* h, mzl_fused_call* c, const char** build
     if (nj == 2 && (c->conv[0].in_mode != c->conv[1].in_mode || c->conv[0].finalize != c->conv[1].finalize)) { err = "mode pair: the two jobs share in_mode and finalize (one kernel build per launch)"; return MZL_E_INVALID; }
     if (hipSetDevice(h->device) != hipSuccess) { err = "hipSetDevice"; return MZL_E_HIP; }
 
-    // ---- geometry: make_geom as mzlc_create calls it, for this batch and the first job's layer ----
+    // ---- geometry: as mzlc_create builds it (hidden_geom), for this batch and the first job's layer ----
     Geom g;
-    if (!make_geom(g, bh, bw, h->allow_side && !c->no_side, wgrad_pick_env(), getenv("MZLC_DENSE_TILING") ? 0 : B, cdiv(cdiv(c->conv[0].cout, 16), 4) * 2, h->num_cus,
-                   !getenv("MZLC_NO_WGRAD_STACK"), false, cdiv(cdiv(c->conv[0].cout, 16), 2) * cdiv(cdiv(c->conv[0].cout, 16), 2))) {
+    if (hidden_geom(h, g, bh, bw, h->sw.images(B), h->allow_side && !c->no_side, h->sw.pick, c->conv[0].cout, c->conv[0].cout, false)) {
         err = "image does not fit the conv kernels' tiling";
         return MZL_E_INVALID;
     }

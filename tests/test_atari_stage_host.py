@@ -46,7 +46,7 @@ def test_tap_masks_are_the_dispatchers():
     assert ac.DGRAD_MASKS == (0x010, 0x030, 0x090, 0x1b0)
     src = open(os.path.join(REPO, 'muzero_amd', 'csrc', 'learner_conv.hip')).read()
     for m in set(ac.FWD_MASKS + ac.DGRAD_MASKS):
-        assert 'case 0x%03x: launch_conv_taps<15, 0x%03x>' % (m, m) in src
+        assert 'MZ_CT(15, 0x%03x)' % m in src  # (the table of builds, kConvBuilds: one entry per tap set at NPT 15)
 
 
 def test_s2_references_agree_with_torch_float64():

@@ -123,7 +123,7 @@ def test_s2_dgrad_on_wide_tiles_is_refused_in_the_compact_form_and_exact_in_the_
     for cls in ac.S2_CLASSES:
         dy, ws = ac.s2_case(cls, ac.S2_DGRAD_WIDE, dgrad=True)
         ref = ac.s2_dgrad_direct(dy, ws[0]).astype(np.float32)
-        with pytest.raises(LearnerError, match=r'no kernel build: launch_conv_tapmask has none for NPT=16 \(tile 12x16\) and the data-gradient tap sets'):
+        with pytest.raises(LearnerError, match=r'no kernel build: kConvBuilds has none for NPT=16 \(tile 12x16\) and the data-gradient tap sets'):
             atari.debug_atari_stage('s2_dgrad', weight=ws[0], dy=dy)
         dx, name = nine_tap.debug_atari_stage('s2_dgrad', weight=ws[0], dy=dy)
         _same(dx, ref, f'{cls} {name}')

@@ -85,6 +85,47 @@ def test_atari_hooks_leave_the_handle_as_they_found_it():
         hl.close()
 
 
+def test_a_hook_builds_its_geometry_from_the_switches_the_handle_was_created_under():
+    """MZLC_DENSE_TILING is read once, at create, into the handle: a hook called after the variable is gone tiles as that handle does.  5 x 5 images
+    (25 pixels, 7 pixel quads), batch 8, a 16-channel layer -- two workgroups per image group, paired -- on more than 6 CUs.  By launch time (make_geom's
+    cost: rounds of workgroups over the CUs x tiles per workgroup; every tiling is one round here) the smallest tiling wins: NPT 5, 3 images in 80
+    slots.  By density: NPT 13, 8 images in 208 slots (200 / 208 against 75 / 80, 75 / 96, 125 / 144 and 225 / 240).  The first pair is the
+    precondition that checks this arithmetic; a library that asked the environment again at the call would give it for both handles."""
+    import os
+
+    from muzero_amd.hip_learner import HipLearner
+
+    dev = torch.device('cuda', 0)
+    case = ('board5x16', 'board', (5, 5, 5), 26, 1, 16, 1, 1, 23)  # (CONV_CASES' layout: 5 x 5 board, one block, 16 planes)
+
+    def learner(env=None):  # (the variable is gone again when the constructor has returned)
+        net = build_conv(case).to(dev)
+        net.train()
+        if env:
+            assert env not in os.environ
+            os.environ[env] = '1'
+        try:
+            return HipLearner(net, dev, 1, 8, lr=1e-3)
+        finally:
+            if env:
+                del os.environ[env]
+
+    rs = np.random.RandomState(7)
+    job = dict(weight=rs.randn(16, 16, 3, 3).astype(np.float32), in0=rs.randn(8, 16, 5, 5).astype(np.float32))
+    plain, dense = learner(), learner('MZLC_DENSE_TILING')
+    try:
+        assert 'MZLC_DENSE_TILING' not in os.environ
+        out_p, name_p = plain.debug_conv_fused(job)
+        out_d, name_d = dense.debug_conv_fused(job)
+        assert ' NPT=5 ' in name_p and ' G=3 ' in name_p, name_p
+        assert ' NPT=13 ' in name_d and ' G=8 ' in name_d, name_d
+        assert float(np.abs(out_p['out']).max()) > 0
+        assert np.array_equal(out_p['out'], out_d['out']), 'a conv output depends on the pixel tiling'  # (the summation order is per output element)
+    finally:
+        plain.close()
+        dense.close()
+
+
 def test_board_hooks_leave_the_handle_as_they_found_it():
     from muzero_amd.hip_learner import LearnerError
 
