@@ -9,7 +9,9 @@ it are in the replay, so a seed gives one learning curve.
 
 Evaluation: `--eval-envs` host `games.CatchEnv` objects play one lock-step batch with deterministic `Planner.search` (no root noise, the
 most-visited action); the ball columns cover every column equally often.  One JSON line per evaluation with the mean return, its standard
-error, the catch rate, and the uniformly random policy's exact expected return (`games.catch_random_policy_return`) for comparison."""
+error, the catch rate, and the uniformly random policy's exact expected return (`games.catch_random_policy_return`) for comparison.
+`--arena-eval N` (N > 0) plays the evaluations on the device instead: `pipeline.play_match` on the Catch arena, N games rounded up to a
+multiple of the columns, nothing crossing PCIe; the same fields are reported."""
 import argparse
 import json
 import os
@@ -39,6 +41,8 @@ def main():
     ap.add_argument('--report-every', type=int, default=200)
     ap.add_argument('--eval-every', type=int, default=500, help='evaluate every N training steps (and at the end); 0: only at the end')
     ap.add_argument('--eval-envs', type=int, default=96, help='evaluation episodes, rounded up to a multiple of the 12 columns')
+    ap.add_argument('--arena-eval', type=int, default=0, help='N > 0: evaluate with N games (rounded up to a multiple of the 12 columns) on the device '
+                    'Catch arena instead of the --eval-envs host envs')
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--tower-precision', choices=('f32', 'bf16x3'), default='f32', help='planner and learner: the fused residual towers')
     ap.add_argument('--stage-precision', choices=('f32', 'bf16x3'), default='f32', help='learner: the tile path\'s stride-1 convs')
@@ -70,13 +74,28 @@ def main():
     p.selfplay_reset_catch(rows, cols, record_format=args.record_format)
     sampler = replay.device_sampler(seed=args.seed)
 
-    n_eval = -(-args.eval_envs // cols) * cols
-    pe = pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=n_eval, seed=args.seed + 1), 0, tower_precision=args.tower_precision)
+    arena = args.arena_eval > 0
+    n_eval = -(-(args.arena_eval if arena else args.eval_envs) // cols) * cols
+    pe = None if arena else pl.Planner(pl.make_mz_config(net.planner_spec(), cfg, num_envs=n_eval, seed=args.seed + 1), 0, tower_precision=args.tower_precision)
     random_return = games.catch_random_policy_return(rows, cols)
+
+    def evaluate_arena():
+        """n_eval games in lock-step on the device Catch arena, ball column i % cols: the same greedy search, no host env."""
+        import types
+
+        from muzero_amd import pipeline
+
+        cfg.planner_seed, cfg.tower_precision = args.seed + 1, args.tower_precision
+        weights = types.SimpleNamespace(planner_spec=net.planner_spec, state_dict=hl.planner_weights)  # the learner's weights, still on the GPU
+        rets = pipeline.play_match(cfg, weights, None, dev, games.CatchEnv(rows, cols, H // rows, W // cols), n_eval, tag='train_catch').ret
+        return dict(eval_mean_return=float(rets.mean()), eval_standard_error=float(rets.std(ddof=1) / np.sqrt(n_eval)),
+                    eval_catch_rate=float((rets > 0).mean()), eval_episodes=n_eval, random_policy_return=random_return)
 
     def evaluate():
         """n_eval host envs in one lock-step batch, ball column i % cols: greedy search, no noise."""
         net.eval()
+        if arena:
+            return evaluate_arena()
         pe.reload(hl.planner_weights())
         envs = [games.make_catch_env(rows, cols, H // rows, W // cols, stack_history=S) for _ in range(n_eval)]
         obs = np.stack([e.reset(ball_col=i % cols) for i, e in enumerate(envs)])
@@ -130,7 +149,8 @@ def main():
     if args.out:
         json.dump(dict(args=vars(args), log=log, evals=evals, summary=summary), open(args.out, 'w'), indent=1)
     p.close()
-    pe.close()
+    if pe is not None:
+        pe.close()
 
 
 if __name__ == '__main__':

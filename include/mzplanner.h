@@ -317,7 +317,7 @@ int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint
  * or MZ_STATE_FRAMES_U8.  After this reset mz_selfplay_step(p, T, n) plays n moves with nothing crossing PCIe and no host synchronisation
  * (with a replay attached: one at the end of the call, which reads back the record ring's capacity check and the search kernels' error
  * word once per call); mz_selfplay_read, _counters, _record_info and _attach_replay work as on the other kinds;
- * mz_selfplay_external_act / _commit return MZ_E_STATE; mz_arena_reset refuses the kind. */
+ * mz_selfplay_external_act / _commit return MZ_E_STATE; mz_arena_reset refuses the kind (its arena is mz_arena_reset_catch's). */
 typedef struct {
     int32_t rows, cols;     /* the grid; rows = cols = 0: 12 x 12 */
     int32_t record_format;  /* MZ_RECORD_F32 or MZ_RECORD_FRAMES_U8 */
@@ -341,9 +341,16 @@ int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env);
  *   envs) from a Philox stream of their own: both games of a pair start from the same position with colours swapped.
  *   Random moves (openings, MZ_ARENA_RANDOM): legal[floor(u * n_legal)], u one Philox double per (pair or env, ply), recorded.
  *   Game length is capped by the env: 500 steps (CartPole), the point count (boards).
- * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC, MZ_ENV_EXTERNAL, MZ_ENV_CATCH: MZ_E_INVALID); h_init_state as
- * mz_selfplay_reset (CartPole only).  Arena and self-play exclude each other on a handle: mz_selfplay_step during an arena is MZ_E_STATE,
- * mz_arena_step without mz_arena_reset (e.g. during self-play) is MZ_E_STATE; each mode's reset enters it. */
+ * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC: MZ_E_INVALID; MZ_ENV_CATCH and MZ_ENV_EXTERNAL:
+ * MZ_E_INVALID naming the reset that plays them, below); h_init_state as mz_selfplay_reset (CartPole only).  Arena and self-play exclude
+ * each other on a handle: mz_selfplay_step and mz_selfplay_external_act / _commit during an arena are MZ_E_STATE, mz_arena_step without an
+ * arena reset (e.g. during self-play) is MZ_E_STATE; each mode's reset enters it and frees what the other left.
+ *   Image and frame games: mz_arena_reset_catch (the device Catch env) and mz_arena_reset_external (envs the host steps) start a
+ *   one-player arena (MZ_ARENA_NONE semantics) whose roots are built on the device from the frame history of the host-stepped path,
+ *   StackFrameAndAction over the newest frame: at the first ply every frame plane is the first frame and every action plane 0, afterwards
+ *   plane 0 is the newest frame with the action plane float32((a_prev + 1) / A) and the history shifts.  A frozen env's history and root
+ *   no longer change.  mz_arena_read_ply and mz_arena_result report them with the fields above (h_side always MZ_ARENA_SIDE_CHALLENGER,
+ *   h_u 0, a finished game's h_winner MZ_ARENA_DRAW); the arena has no record ring, so record_format must be MZ_RECORD_F32. */
 #define MZ_ARENA_NONE 0
 #define MZ_ARENA_RANDOM 1
 #define MZ_ARENA_PLANNER 2
@@ -361,6 +368,26 @@ int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_kind, mz_pl
  * synchronisation inside; the two planners' streams are ordered with events.  Replaces the `while not done` loops of pipeline.py:289-397
  * (:370-377) and pipeline.py:400-488 (:463-473). */
 int mz_arena_step(mz_planner* p, int32_t n_plies);
+/* Catch in the arena.  Geometry and refusals are mz_selfplay_reset_catch's (3 actions, not a board game, obs_c = 2 S, rows and cols divide
+ * the frame); record_format must be MZ_RECORD_F32.  Env e starts with the paddle at cols / 2, the ball in column h_ball_col[e] (NULL:
+ * e % cols, every column equally often) and row h_start_row[e] (NULL: 0; 0 .. rows - 2, so games may end on different plies); an entry out
+ * of range is MZ_E_INVALID naming the array and the env.  No Philox draw is used.  mz_arena_step(p, n) then plays n plies with nothing
+ * crossing PCIe and no host synchronisation: roots from the frames, one deterministic search of all num_envs roots, the env's step without
+ * restart, the next frame.  A game ends when the ball reaches the last row: ret +1.0 or -1.0, length the plies played. */
+int mz_arena_reset_catch(mz_planner* p, const mz_catch_env* env, const int32_t* h_ball_col_or_null, const int32_t* h_start_row_or_null);
+/* The same ply for envs the host steps, cut where it steps them.  `env` describes the frames as for mz_selfplay_reset_external (stacked
+ * uint8 or float images, stacked vectors, stack_history = 0 for whole observations); max_episode_steps and temp_switch_steps are not used.
+ *   mz_arena_external_act    -- uploads every env's newest frame, mask and player ids (arguments as mz_selfplay_external_act's; the entries
+ *                               of frozen envs are ignored), searches deterministically, returns h_action int32 [B] and h_live uint8 [B]:
+ *                               1 where the host must step the env with its action (a frozen env's h_action is its last move);
+ *   mz_arena_external_commit -- h_reward float32 [B], h_done uint8 [B] of the live envs (frozen envs' entries are ignored): the reward is
+ *                               added to the env's float64 return in ply order, the length grows by one, a done env freezes and is tallied.
+ * mz_arena_read_ply and mz_arena_result report the plies committed so far.  MZ_E_STATE, naming the call to make instead: mz_arena_step on
+ * this arena, these two calls on any other arena or before the reset, two acts without a commit, a commit without an act. */
+int mz_arena_reset_external(mz_planner* p, const mz_external_env* env);
+int mz_arena_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur, const int32_t* h_opp,
+                          int32_t* h_action, uint8_t* h_live);
+int mz_arena_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done);
 /* The last ply, per env; any pointer may be NULL.  h_obs float32 [B, obs], h_mask uint8 [B, A], h_player int32 [B] (side to move, 1 / 2):
  * the root before the move.  h_side int32 [B] (MZ_ARENA_SIDE_*), h_pi float64 [B, A] and h_root float64 [B] (zeros for a random move),
  * h_action int32 [B], h_u float64 [B] (the uniform of a random move, else 0), h_live uint8 [B]: 1 where the env was live when the ply

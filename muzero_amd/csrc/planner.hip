@@ -15,6 +15,7 @@
 #include "../../include/mzplanner.h"
 #include "mz_env.h"
 #include "mz_arena.h"
+#include "mz_arena_image.h"
 #include "mz_extenv.h"
 #include "mz_catch.h"
 #include "mz_search.h"
@@ -221,6 +222,9 @@ struct mz_planner {
     bool arena_open = false;
     int arena_ply = 0;
     mz_planner* arena_q = nullptr;  // the borrowed opponent planner (MZ_ARENA_PLANNER)
+    int arena_img = 0;              // IMGARENA_CATCH / IMGARENA_EXTERNAL: the roots come from ext's frame history (mz_arena_image.h)
+    bool arena_pending = false;     // host-stepped arena: an act is waiting for its commit
+    std::vector<unsigned char> arena_live_h;  // host-stepped arena: the live flags (the host uploads every done flag, so it knows them)
     hipEvent_t ev_arena_pre = nullptr, ev_arena_q = nullptr;  // order the two planners' streams within a ply
 
     // weights bound in device memory (mz_planner_bind_param_device / mz_planner_refresh_params; mz_pack.h)
@@ -1690,10 +1694,8 @@ static ExtLaunch ext_launch(mz_planner* p, double temperature) {
     return L;
 }
 
-// The reset of both kinds that run on ExtEnv: host-stepped envs (`sname` "mz_external_env") and the device Catch env, which describes its
-// frames with the same struct ("mz_catch_env": its refusals name that struct's record_format).
-static int ext_reset(mz_planner* p, const mz_external_env* x, int env_kind, const std::string& sname) {
-    HIPCHK(hipSetDevice(p->device));
+// the frames an mz_external_env describes must stack to the network's observation
+static int ext_check_frames(mz_planner* p, const mz_external_env* x) {
     const mz_config& c = p->cfg;
     const int S = x->stack_history;
     if (S < 0 || x->frame_c < 1 || x->frame_h < 1 || x->frame_w < 1 || x->max_episode_steps < 0 || x->temp_switch_steps < 0)
@@ -1706,6 +1708,52 @@ static int ext_reset(mz_planner* p, const mz_external_env* x, int env_kind, cons
         return fail(MZ_E_INVALID, "mz_external_env: the stacked observation has " + std::to_string(stacked) + " values, the network's (obs_c*obs_h*obs_w) " +
                                       std::to_string(obs_dim(c)));
     if (S == 0 && x->frame_u8) return fail(MZ_E_INVALID, "mz_external_env: frame_u8 needs stack_history > 0 (whole observations are float32)");
+    return MZ_OK;
+}
+
+// ExtEnv's geometry and device buffers, and the pinned staging of every upload and download (after ext_free)
+static int ext_alloc(mz_planner* p, const mz_external_env* x) {
+    const mz_config& c = p->cfg;
+    const int S = x->stack_history;
+    const long long FE = (long long)x->frame_c * x->frame_h * x->frame_w;
+    ExtEnv& X = p->ext;
+    X.S = S; X.image = x->is_obs_image ? 1 : 0; X.C = x->frame_c; X.HW = x->frame_h * x->frame_w; X.FE = (int)FE; X.u8 = x->frame_u8 ? 1 : 0;
+    X.temp_steps = x->temp_switch_steps > 0 ? x->temp_switch_steps : (c.num_actions <= 10 ? 6 : 30);
+    p->ext_od = obs_dim(c);
+    const size_t B = (size_t)c.num_envs, fbytes = (size_t)FE * (X.u8 ? 1 : 4);
+    HIPCHK(hipMalloc(&X.frames, (B * fbytes + 15) / 16 * 16));  // (whole 16-byte runs: k_catch_render stores nothing narrower)
+    if (S > 0) {
+        HIPCHK(hipMalloc(&X.hist, B * S * fbytes));
+        HIPCHK(hipMalloc(&X.hist_act, B * S * sizeof(int)));
+        HIPCHK(hipMalloc(&X.head, 2 * B * sizeof(int)));
+        HIPCHK(hipMemsetAsync(X.head, 0, 2 * B * sizeof(int), p->stream));
+    }
+    HIPCHK(hipMalloc(&X.reward, B * sizeof(float)));
+    HIPCHK(hipMalloc(&X.done, B));
+    HIPCHK(hipMalloc(&X.err, sizeof(int)));
+    HIPCHK(hipHostMalloc(&p->h_ext_frames, B * fbytes, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_mask), B * c.num_actions, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_cur), B * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_opp), B * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_action), B * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_reward), B * sizeof(float), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_done), B, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_err), sizeof(int), hipHostMallocDefault));
+    const int none = INT_MAX;
+    HIPCHK(hipMemcpyAsync(X.err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+// The reset of both kinds that run on ExtEnv: host-stepped envs (`sname` "mz_external_env") and the device Catch env, which describes its
+// frames with the same struct ("mz_catch_env": its refusals name that struct's record_format).
+static int ext_reset(mz_planner* p, const mz_external_env* x, int env_kind, const std::string& sname) {
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    const int S = x->stack_history;
+    int rc = ext_check_frames(p, x);
+    if (rc) return rc;
+    const long long FE = (long long)x->frame_c * x->frame_h * x->frame_w;
     const int fmt = p->has_replay ? p->replay.state_format : STATE_F32;
     if (fmt == STATE_FRAMES_U8) {
         if (S == 0 || !x->is_obs_image || !x->frame_u8)
@@ -1747,43 +1795,22 @@ static int ext_reset(mz_planner* p, const mz_external_env* x, int env_kind, cons
             return fail(MZ_E_HIP, std::string("compact record ring: ") + hipGetErrorString(r));
         }
     }
+    rc = ext_alloc(p, x);
+    if (rc) return rc;
     ExtEnv& X = p->ext;
-    X.S = S; X.image = x->is_obs_image ? 1 : 0; X.C = x->frame_c; X.HW = x->frame_h * x->frame_w; X.FE = (int)FE; X.u8 = x->frame_u8 ? 1 : 0;
-    X.temp_steps = x->temp_switch_steps > 0 ? x->temp_switch_steps : (c.num_actions <= 10 ? 6 : 30);
-    p->ext_od = obs_dim(c);
-    const size_t B = (size_t)c.num_envs, fbytes = (size_t)FE * (X.u8 ? 1 : 4);
-    HIPCHK(hipMalloc(&X.frames, (B * fbytes + 15) / 16 * 16));  // (whole 16-byte runs: k_catch_render stores nothing narrower)
-    if (S > 0) {
-        HIPCHK(hipMalloc(&X.hist, B * S * fbytes));
-        HIPCHK(hipMalloc(&X.hist_act, B * S * sizeof(int)));
-        HIPCHK(hipMalloc(&X.head, 2 * B * sizeof(int)));
-        HIPCHK(hipMemsetAsync(X.head, 0, 2 * B * sizeof(int), p->stream));
-    }
-    HIPCHK(hipMalloc(&X.reward, B * sizeof(float)));
-    HIPCHK(hipMalloc(&X.done, B));
-    HIPCHK(hipMalloc(&X.err, sizeof(int)));
     if (fmt != STATE_F32) {
         ReplayRing& R = p->replay;
         R.fS = S; R.fC = X.C; R.fHW = X.HW; R.fP = S * X.FE;
         R.row_bytes = fmt == STATE_I8 ? obs_dim(c) : (R.fP + S + 15) / 16 * 16;
         R.enc_err = nullptr;
         if (fmt == STATE_I8) {  // whole observations of any env: every emitted state is checked
+            const int none = INT_MAX;
             HIPCHK(hipMalloc(&X.enc_err, sizeof(int)));
             R.enc_err = X.enc_err;
+            HIPCHK(hipMemcpyAsync(X.enc_err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
+            HIPCHK(hipStreamSynchronize(p->stream));
         }
     }
-    HIPCHK(hipHostMalloc(&p->h_ext_frames, B * fbytes, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_mask), B * c.num_actions, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_cur), B * sizeof(int), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_opp), B * sizeof(int), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_action), B * sizeof(int), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_reward), B * sizeof(float), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_done), B, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&p->h_ext_err), sizeof(int), hipHostMallocDefault));
-    const int none = INT_MAX;
-    HIPCHK(hipMemcpyAsync(X.err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
-    if (X.enc_err) HIPCHK(hipMemcpyAsync(X.enc_err, &none, sizeof(int), hipMemcpyHostToDevice, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
     return MZ_OK;
 }
 
@@ -1824,6 +1851,7 @@ static int ext_enqueue_commit(mz_planner* p, const ExtLaunch& L) {
 extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur, const int32_t* h_opp,
                                         double temperature, int32_t* h_action) {
     if (!p || !h_frames || !h_mask || !h_cur || !h_opp || !h_action) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_act");
+    if (p->arena_open) return fail(MZ_E_STATE, "mz_selfplay_external_act during an arena: call mz_selfplay_reset_external first");
     if (p->env_kind != MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "call mz_selfplay_reset_external first");
     if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory or a state its replay format cannot hold: call mz_selfplay_reset_external");
     if (p->ext_pending) return fail(MZ_E_STATE, "mz_selfplay_external_act twice: commit the last act's outcome first");
@@ -1858,6 +1886,7 @@ extern "C" int mz_selfplay_external_act(mz_planner* p, const void* h_frames, con
 
 extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done) {
     if (!p || !h_reward || !h_done) return fail(MZ_E_INVALID, "null argument to mz_selfplay_external_commit");
+    if (p->arena_open) return fail(MZ_E_STATE, "mz_selfplay_external_commit during an arena: call mz_selfplay_reset_external first");
     if (p->env_kind != MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "call mz_selfplay_reset_external first");
     if (p->ext_broken) return fail(MZ_E_STATE, "a commit found an over-long trajectory or a state its replay format cannot hold: call mz_selfplay_reset_external");
     if (!p->ext_pending) return fail(MZ_E_STATE, "mz_selfplay_external_commit without an mz_selfplay_external_act");
@@ -1909,32 +1938,51 @@ static void catch_render(mz_planner* p, const CatchLaunch& G) {
     hipLaunchKernelGGL(k_catch_render, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, G);
 }
 
-extern "C" int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env) {
-    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_catch");
+// Catch's geometry off the planner's mz_config, for the reset `fn` (self-play or arena): the grid, and the frames as an mz_external_env
+static int catch_geometry(mz_planner* p, const mz_catch_env* env, const std::string& fn, int& rows, int& cols, mz_external_env& x) {
     const mz_config& c = p->cfg;
-    const int rows = env->rows == 0 && env->cols == 0 ? 12 : env->rows, cols = env->rows == 0 && env->cols == 0 ? 12 : env->cols;
-    if (c.is_board_game) return fail(MZ_E_INVALID, "mz_selfplay_reset_catch: is_board_game must be 0 (Catch is a one-player game)");
-    if (c.num_actions != 3) return fail(MZ_E_INVALID, "mz_selfplay_reset_catch: num_actions must be 3 (left, stay, right), not " + std::to_string(c.num_actions));
+    rows = env->rows == 0 && env->cols == 0 ? 12 : env->rows;
+    cols = env->rows == 0 && env->cols == 0 ? 12 : env->cols;
+    if (c.is_board_game) return fail(MZ_E_INVALID, fn + ": is_board_game must be 0 (Catch is a one-player game)");
+    if (c.num_actions != 3) return fail(MZ_E_INVALID, fn + ": num_actions must be 3 (left, stay, right), not " + std::to_string(c.num_actions));
     if (c.obs_c < 2 || (c.obs_c & 1))
-        return fail(MZ_E_INVALID, "mz_selfplay_reset_catch: obs_c must be 2 * stack_history (S one-channel frames and S action planes), not " + std::to_string(c.obs_c));
+        return fail(MZ_E_INVALID, fn + ": obs_c must be 2 * stack_history (S one-channel frames and S action planes), not " + std::to_string(c.obs_c));
     if (rows < 2 || c.obs_h % rows != 0)
         return fail(MZ_E_INVALID, "mz_catch_env.rows must be >= 2 and divide obs_h = " + std::to_string(c.obs_h) + ", not " + std::to_string(rows));
     if (cols < 1 || c.obs_w % cols != 0)
         return fail(MZ_E_INVALID, "mz_catch_env.cols must be >= 1 and divide obs_w = " + std::to_string(c.obs_w) + ", not " + std::to_string(cols));
-    if (p->has_replay && p->replay.state_format == STATE_I8)
-        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: Catch observations (action planes of 1/3, 2/3) are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
-    mz_external_env x{};
+    x = mz_external_env{};
     x.stack_history = c.obs_c / 2; x.is_obs_image = 1; x.frame_c = 1; x.frame_h = c.obs_h; x.frame_w = c.obs_w; x.frame_u8 = 1;
     x.max_episode_steps = rows - 1;  // (an episode's length: the record ring always holds an open trajectory)
     x.record_format = env->record_format;
-    int rc = ext_reset(p, &x, MZ_ENV_CATCH, "mz_catch_env");
-    if (rc) return rc;
+    return MZ_OK;
+}
+
+// the game's state arrays (after ext_free)
+static int catch_alloc(mz_planner* p, int rows, int cols) {
+    const mz_config& c = p->cfg;
     CatchEnv& K = p->catch_env;
     K.rows = rows; K.cols = cols; K.ch = c.obs_h / rows; K.cw = c.obs_w / cols; K.H = c.obs_h; K.W = c.obs_w; K.FE = c.obs_h * c.obs_w;
     const size_t B = (size_t)c.num_envs;
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.br), B * sizeof(int)));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.bc), B * sizeof(int)));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.pc), B * sizeof(int)));
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_catch");
+    const mz_config& c = p->cfg;
+    int rows, cols;
+    mz_external_env x;
+    int rc = catch_geometry(p, env, "mz_selfplay_reset_catch", rows, cols, x);
+    if (rc) return rc;
+    if (p->has_replay && p->replay.state_format == STATE_I8)
+        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: Catch observations (action planes of 1/3, 2/3) are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
+    rc = ext_reset(p, &x, MZ_ENV_CATCH, "mz_catch_env");
+    if (rc) return rc;
+    rc = catch_alloc(p, rows, cols);
+    if (rc) return rc;
     const CatchLaunch G = catch_launch(p);
     hipLaunchKernelGGL(k_catch_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
     catch_render(p, G);
@@ -2147,9 +2195,11 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
         board_n = c.obs_h;
         num_to_win = 5;
     } else if (env_kind == MZ_ENV_CATCH) {
-        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_CATCH is a self-play env only (the arena plays CartPole, TicTacToe and Gomoku)");
+        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_CATCH has its own arena reset: mz_arena_reset_catch");
+    } else if (env_kind == MZ_ENV_EXTERNAL) {
+        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_EXTERNAL has its own arena reset: mz_arena_reset_external");
     } else {
-        return fail(MZ_E_INVALID, "the arena plays the device envs CartPole, TicTacToe and Gomoku (not the synthetic or host-stepped kinds)");
+        return fail(MZ_E_INVALID, "the arena plays the device envs CartPole, TicTacToe and Gomoku (not the synthetic kind)");
     }
     const bool two = env_kind != MZ_ENV_CARTPOLE;
     if (opponent_kind != MZ_ARENA_NONE && opponent_kind != MZ_ARENA_RANDOM && opponent_kind != MZ_ARENA_PLANNER) return fail(MZ_E_INVALID, "unknown opponent kind");
@@ -2186,6 +2236,7 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
     p->arena.opening_plies = opening_plies;
     p->arena_q = opponent_kind == MZ_ARENA_PLANNER ? q : nullptr;
     p->arena_ply = 0;
+    p->arena_img = 0;
     if (h_init_state) HIPCHK(hipMemcpyAsync(p->env.init_state, h_init_state, (size_t)c.num_envs * 4 * sizeof(double), hipMemcpyHostToDevice, p->stream));
     ArenaLaunch R = arena_launch(p);
     R.L.use_init = h_init_state != nullptr;
@@ -2196,12 +2247,16 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
     return MZ_OK;
 }
 
+static int imgarena_catch_plies(mz_planner* p, int n_plies);
+
 extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     if (!p || n_plies < 1) return fail(MZ_E_INVALID, "bad argument to mz_arena_step");
     if (!p->arena_open) return fail(MZ_E_STATE, "call mz_arena_reset first");
+    if (p->arena_img == IMGARENA_EXTERNAL) return fail(MZ_E_STATE, "mz_arena_step on a host-stepped arena: use mz_arena_external_act / _commit");
     mz_planner* q = p->arena_q;
     if (!p->committed || (q && !q->committed)) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
+    if (p->arena_img == IMGARENA_CATCH) return imgarena_catch_plies(p, n_plies);
     const mz_config& c = p->cfg;
     const int B = c.num_envs, half = p->arena.half;
     const dim3 waves((B + 3) / 4), block(256);
@@ -2303,6 +2358,196 @@ extern "C" int mz_arena_result(mz_planner* p, int32_t* h_winner, int32_t* h_leng
         for (int i = 0; i < 4; i++) totals[i] = (int64_t)t[i];
     }
     if (n_live) HIPCHK(hipMemcpy(n_live, a.n_live, sizeof(int), hipMemcpyDeviceToHost));
+    return MZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// arena on image and frame games (mz_arena_image.h): device Catch, and envs the host steps
+// ---------------------------------------------------------------------------------------------------------
+static ImgArenaLaunch imgarena_launch(mz_planner* p) {
+    const mz_config& c = p->cfg;
+    ImgArenaLaunch R{};
+    R.L.env = p->env; R.L.x = p->ext; R.L.B = c.num_envs; R.L.A = c.num_actions; R.L.OD = p->ext_od;
+    R.L.first = p->arena_ply == 0; R.L.parity = p->arena_ply & 1; R.L.obs = p->arena.obs;
+    R.a = p->arena;
+    R.c = p->catch_env;
+    R.action = p->d_action; R.pi = p->d_pi; R.root = p->d_root;
+    return R;
+}
+
+// What both resets share: `x` describes the frames (checked as the self-play reset checks it; `sname` names the struct in refusals).
+// Leaves the handle in an image arena of `mode` at ply 0 with every buffer allocated; the caller fills the env's state and launches
+// k_imgarena_reset.
+static int imgarena_reset(mz_planner* p, const mz_external_env* x, int env_kind, int mode, const std::string& sname) {
+    const mz_config& c = p->cfg;
+    int rc = ext_check_frames(p, x);
+    if (rc) return rc;
+    if (x->record_format != MZ_RECORD_F32) return fail(MZ_E_INVALID, sname + ".record_format must be MZ_RECORD_F32 (0): the arena has no record ring");
+    if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    ext_free(p);
+    p->env_kind = env_kind;
+    p->arena_open = false;  // (until every buffer is there)
+    p->ring_len = 1; p->ring_pos = 0; p->ring_count = 0;  // no self-play records in this mode (mz_selfplay_read: MZ_E_INVALID)
+    p->selfplay_moves = 0;
+    hipError_t e = env_alloc(p->env, ENV_EXTERNAL, c.num_envs, c.num_actions, obs_dim(c), 1, 3, 3, false);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    e = arena_alloc(p->arena, c.num_envs, c.num_actions, obs_dim(c));
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("arena_alloc: ") + hipGetErrorString(e));
+    rc = ext_alloc(p, x);
+    if (rc) return rc;
+    p->arena.half = 0;
+    p->arena.opponent = MZ_ARENA_NONE;
+    p->arena.opening_plies = 0;
+    p->arena_q = nullptr;
+    p->arena_ply = 0;
+    p->arena_img = mode;
+    p->arena_pending = false;
+    p->arena_live_h.assign((size_t)c.num_envs, 1);
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_reset_catch(mz_planner* p, const mz_catch_env* env, const int32_t* h_ball_col, const int32_t* h_start_row) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_catch");
+    const mz_config& c = p->cfg;
+    int rows, cols;
+    mz_external_env x;
+    int rc = catch_geometry(p, env, "mz_arena_reset_catch", rows, cols, x);
+    if (rc) return rc;
+    const int B = c.num_envs;
+    std::vector<int> bc((size_t)B), br((size_t)B);
+    for (int e = 0; e < B; e++) {
+        bc[e] = h_ball_col ? h_ball_col[e] : e % cols;
+        br[e] = h_start_row ? h_start_row[e] : 0;
+        if (bc[e] < 0 || bc[e] >= cols)
+            return fail(MZ_E_INVALID, "mz_arena_reset_catch: h_ball_col[" + std::to_string(e) + "] = " + std::to_string(bc[e]) + " is outside the " + std::to_string(cols) + " columns");
+        if (br[e] < 0 || br[e] > rows - 2)
+            return fail(MZ_E_INVALID, "mz_arena_reset_catch: h_start_row[" + std::to_string(e) + "] = " + std::to_string(br[e]) + " is outside 0 .. rows - 2 = " + std::to_string(rows - 2));
+    }
+    rc = imgarena_reset(p, &x, MZ_ENV_CATCH, IMGARENA_CATCH, "mz_catch_env");
+    if (rc) return rc;
+    rc = catch_alloc(p, rows, cols);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(p->catch_env.bc, bc.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->catch_env.br, br.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    const ImgArenaLaunch R = imgarena_launch(p);
+    hipLaunchKernelGGL(k_imgarena_reset, dim3((B + 255) / 256), dim3(256), 0, p->stream, R);
+    catch_render(p, catch_launch(p));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->arena_open = true;
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_reset_external(mz_planner* p, const mz_external_env* env) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_external");
+    int rc = imgarena_reset(p, env, MZ_ENV_EXTERNAL, IMGARENA_EXTERNAL, "mz_external_env");
+    if (rc) return rc;
+    ImgArenaLaunch R = imgarena_launch(p);
+    R.c = CatchEnv{};
+    hipLaunchKernelGGL(k_imgarena_reset, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, R);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->arena_open = true;
+    return MZ_OK;
+}
+
+// The front half of a ply, shared by both front ends: the roots of the live envs from ext.frames (k_imgarena_ingest), k_arena_pre's
+// staging and "before acting" record, one deterministic search of all B roots.
+static int imgarena_enqueue_search(mz_planner* p, const ImgArenaLaunch& R) {
+    const mz_config& c = p->cfg;
+    const int B = c.num_envs, OD = p->ext_od;
+    const bool vec4 = (p->ext.S > 0 && p->ext.image && p->ext.HW % 4 == 0) || (p->ext.S == 0 && OD % 4 == 0);  // (as ext_enqueue_act)
+    if (vec4) hipLaunchKernelGGL(k_imgarena_ingest<4>, dim3((OD / 4 + 256 * EXT_ITER - 1) / (256 * EXT_ITER), B), dim3(256), 0, p->stream, R);
+    else hipLaunchKernelGGL(k_imgarena_ingest<1>, dim3((OD + 63) / 64, B), dim3(64), 0, p->stream, R);
+    ArenaLaunch Q = arena_launch(p);
+    Q.nseg = 1;
+    Q.seg[0].lo = 0; Q.seg[0].n = B; Q.seg[0].side = SIDE_CHALLENGER;
+    arena_seg_searched(Q.seg[0], p);
+    const size_t work = (size_t)B * obs_dim(c) / 4 + 1;
+    const int pre_blocks = (int)((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_arena_pre, dim3(pre_blocks), dim3(256), 0, p->stream, Q);
+    HIPCHK(hipGetLastError());
+    return launch_search(p, B, 1, true, false, false);
+}
+
+// mz_arena_step on a Catch arena: nothing is copied and nothing waits
+static int imgarena_catch_plies(mz_planner* p, int n_plies) {
+    const int B = p->cfg.num_envs;
+    const CatchLaunch G = catch_launch(p);
+    for (int m = 0; m < n_plies; m++) {
+        const ImgArenaLaunch R = imgarena_launch(p);
+        int rc = imgarena_enqueue_search(p, R);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_imgarena_catch_step, dim3((B + 255) / 256), dim3(256), 0, p->stream, R);
+        catch_render(p, G);
+        HIPCHK(hipGetLastError());
+        p->arena_ply++;
+    }
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur, const int32_t* h_opp,
+                                     int32_t* h_action, uint8_t* h_live) {
+    if (!p || !h_frames || !h_mask || !h_cur || !h_opp || !h_action || !h_live) return fail(MZ_E_INVALID, "null argument to mz_arena_external_act");
+    if (!p->arena_open || p->arena_img != IMGARENA_EXTERNAL) return fail(MZ_E_STATE, "mz_arena_external_act: call mz_arena_reset_external first");
+    if (p->arena_pending) return fail(MZ_E_STATE, "mz_arena_external_act twice: report the last act's outcome with mz_arena_external_commit first");
+    if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    const size_t B = (size_t)c.num_envs, A = (size_t)c.num_actions, fb = (size_t)p->ext.FE * (p->ext.u8 ? 1 : 4);
+    // pinned staging, live envs only: a frozen env's entries are not read, so its staged frame, mask and player ids stay its last ones
+    for (size_t e = 0; e < B; e++) {
+        if (!p->arena_live_h[e]) continue;
+        std::memcpy(static_cast<unsigned char*>(p->h_ext_frames) + e * fb, static_cast<const unsigned char*>(h_frames) + e * fb, fb);
+        std::memcpy(p->h_ext_mask + e * A, h_mask + e * A, A);
+        p->h_ext_cur[e] = h_cur[e];
+        p->h_ext_opp[e] = h_opp[e];
+    }
+    HIPCHK(hipMemcpyAsync(p->ext.frames, p->h_ext_frames, B * fb, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->arena.mask, p->h_ext_mask, B * A, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->arena.cur, p->h_ext_cur, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->arena.opp, p->h_ext_opp, B * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    const ImgArenaLaunch R = imgarena_launch(p);
+    int rc = imgarena_enqueue_search(p, R);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_imgarena_record, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, R);
+    HIPCHK(hipGetLastError());
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(p->h_ext_action, p->arena.r_action, B * sizeof(int), hipMemcpyDeviceToHost, p->stream));  // (a frozen env: its last move)
+    HIPCHK(hipMemcpyAsync(&err, p->d_err, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (err) {
+        HIPCHK(hipMemsetAsync(p->d_err, 0, sizeof(int), p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        return fail(MZ_E_INVALID, "search kernel reported error " + std::to_string(err));
+    }
+    std::memcpy(h_action, p->h_ext_action, B * sizeof(int));
+    std::memcpy(h_live, p->arena_live_h.data(), B);
+    p->arena_pending = true;
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_external_commit(mz_planner* p, const float* h_reward, const uint8_t* h_done) {
+    if (!p || !h_reward || !h_done) return fail(MZ_E_INVALID, "null argument to mz_arena_external_commit");
+    if (!p->arena_open || p->arena_img != IMGARENA_EXTERNAL) return fail(MZ_E_STATE, "mz_arena_external_commit: call mz_arena_reset_external first");
+    if (!p->arena_pending) return fail(MZ_E_STATE, "mz_arena_external_commit without an mz_arena_external_act");
+    HIPCHK(hipSetDevice(p->device));
+    const size_t B = (size_t)p->cfg.num_envs;
+    for (size_t e = 0; e < B; e++) {
+        const bool live = p->arena_live_h[e] != 0;
+        p->h_ext_reward[e] = live ? h_reward[e] : 0.0f;
+        p->h_ext_done[e] = live && h_done[e] ? 1 : 0;
+    }
+    HIPCHK(hipMemcpyAsync(p->ext.reward, p->h_ext_reward, B * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->ext.done, p->h_ext_done, B, hipMemcpyHostToDevice, p->stream));
+    hipLaunchKernelGGL(k_imgarena_commit, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, imgarena_launch(p));
+    HIPCHK(hipGetLastError());
+    for (size_t e = 0; e < B; e++)
+        if (p->h_ext_done[e]) p->arena_live_h[e] = 0;
+    p->arena_ply++;
+    p->arena_pending = false;
     return MZ_OK;
 }
 

@@ -452,7 +452,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
 # ------------------------------------------------------------------------------------------------------------------
 # evaluation matches on the device arena (Planner.arena_*)
 # ------------------------------------------------------------------------------------------------------------------
-ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku')
+ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Catch')
 _UNFINISHED, _WIN_CHALLENGER, _WIN_OPPONENT, _DRAW = 0, 1, 2, 3  # planner.ARENA_* (kept here so this module imports without the library)
 
 
@@ -532,13 +532,21 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
                init_state=None) -> MatchResult:
     """`num_games` evaluation games in lock-step on the GPU (Planner.arena_*), every searched move a deterministic search
     (pipeline.py:374, 468).  `opponent`: a network (two-player envs), 'random' (two-player envs), or None (one-player envs).  `env`: a
-    device-env name ('TicTacToe', 'Gomoku', 'CartPole-v1') or an env object with a device twin.  Two-player envs: `num_games` must be
+    device-env name ('TicTacToe', 'Gomoku', 'CartPole-v1', 'Catch') or an env object with a device twin.  Two-player envs: `num_games` must be
     even -- the challenger plays black in the first half and white in the second, game i and game i + num_games / 2 share their
     `opening_plies` random opening plies (default: 2 against a network, 0 otherwise; deterministic play from one opening would repeat one
-    game).  `init_state`: CartPole start states [num_games, 4].  `tag` names the match in error messages."""
+    game).  `init_state`: CartPole start states [num_games, 4].  `tag` names the match in error messages.
+
+    'Catch' (or a `games.CatchEnv` / `games.make_catch_env` object, whose grid is used): game e has its ball in column e % cols, row 0.
+    Host-stepped envs: `env` may also be a list / tuple of env objects or a factory `i -> env` (called `num_games` times), as
+    `run_self_play` takes them: each is reset once and played to its end through the host-stepped arena (`Planner.arena_external_act` /
+    `_commit`), live envs stepped on the calling thread; envs that are `games.StackFrameAndAction` have their stacking done on the
+    device.  Both are one-player matches: any opponent is a ValueError."""
     what = f'play_match({tag})' if tag else 'play_match'
+    if isinstance(env, (list, tuple)) or (callable(env) and not hasattr(env, 'step')):  # what resolve_self_play_envs calls 'host'
+        return _play_match_host(config, challenger_network, opponent, device, env, int(num_games), opening_plies, init_state, what)
     name = resolve_arena_env(env)
-    two = name != 'CartPole-v1'
+    two = name not in ('CartPole-v1', 'Catch')
     num_games = int(num_games)
     if num_games < 1:
         raise ValueError(f'{what}: num_games must be >= 1, got {num_games}')
@@ -566,15 +574,21 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU}
     idx = device.index if getattr(device, 'index', None) is not None else 0
     seed = int(getattr(config, 'planner_seed', 1))
-    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
+    rows = int(getattr(env, 'rows', 12))
+    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729, keep_shape=name == 'Catch'), idx,
+                   tower_precision=getattr(config, 'tower_precision', 'f32'))
     q = None
     try:
         p.reload(challenger_network.state_dict())
         if is_net:
             q = pl.Planner(pl.make_mz_config(opponent.planner_spec(), config, num_envs=num_games, seed=seed + 130003), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
             q.reload(opponent.state_dict())
-        p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
-        cap = 500 if not two else p.A - 1  # the env's own cap: CartPole's TimeLimit, a board's point count
+        if name == 'Catch':
+            p.arena_reset_catch(rows, int(getattr(env, 'cols', 12)))
+        else:
+            p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
+        # the env's own cap: CartPole's TimeLimit, a Catch ball's fall, a board's point count
+        cap = (rows - 1 if name == 'Catch' else 500) if not two else p.A - 1
         res = p.arena_result()
         played = 0
         while res['live'] > 0 and played < cap:
@@ -589,6 +603,57 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
         p.close()  # (the challenger first: it borrows the opponent's planner)
         if q is not None:
             q.close()
+
+
+def _play_match_host(config, network, opponent, device, env, num_games, opening_plies, init_state, what) -> MatchResult:
+    """play_match over host-stepped env objects (see there)."""
+    if num_games < 1:
+        raise ValueError(f'{what}: num_games must be >= 1, got {num_games}')
+    if opponent is not None:
+        raise ValueError(f'{what}: host-stepped envs are played as one-player matches, opponent must be None')
+    if opening_plies or init_state is not None:
+        raise ValueError(f'{what}: host-stepped envs take no opening plies and no init_state')
+    kind, envs = resolve_self_play_envs(env, num_games)
+    if kind != 'host':
+        raise ValueError(f'{what}: expected env objects, got {env!r}')
+    if len(envs) != num_games:
+        raise ValueError(f'{what}: {len(envs)} env objects for num_games = {num_games}')
+    from muzero_amd import planner as pl
+
+    B = num_games
+    parts = [device_stack_parts(e) for e in envs]
+    stacked = all(pt is not None for pt in parts)
+    if stacked and len({pt[1:] for pt in parts}) != 1:
+        raise ValueError(f'{what}: all envs must stack the same way (stack_history, is_obs_image, ScaledFloatFrame)')
+    step_envs = [pt[0] for pt in parts] if stacked else list(envs)
+    S, image, u8 = parts[0][1:] if stacked else (0, False, False)
+    frames = [np.asarray(e.reset()) for e in step_envs]
+    frame_dtype = np.uint8 if u8 else np.float32
+    idx = device.index if getattr(device, 'index', None) is not None else 0
+    seed = int(getattr(config, 'planner_seed', 1))
+    p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=B, seed=seed + 104729), idx,
+                   tower_precision=getattr(config, 'tower_precision', 'f32'))
+    try:
+        p.reload(network.state_dict())
+        p.arena_reset_external(stack_history=S, is_obs_image=image, frame_shape=frames[0].shape, frame_u8=u8)
+        ones = np.ones((B, p.A), np.uint8)
+        rewards, dones = np.zeros(B, np.float32), np.zeros(B, np.uint8)
+        res = p.arena_result()
+        while res['live'] > 0:
+            mask = np.stack([np.asarray(m, np.uint8).reshape(-1) for m in (getattr(e, 'actions_mask', None) for e in envs)]) \
+                if all(getattr(e, 'actions_mask', None) is not None for e in envs) else ones
+            cur = np.array([getattr(e, 'current_player', 1) for e in envs], np.int32)
+            opp = np.array([getattr(e, 'opponent_player', 1) for e in envs], np.int32)
+            actions, live = p.arena_external_act(np.stack(frames).astype(frame_dtype, copy=False), mask, cur, opp)
+            for i in np.flatnonzero(live):
+                obs, r, d, _ = step_envs[i].step(int(actions[i]))
+                frames[i], rewards[i], dones[i] = np.asarray(obs), r, 1 if d else 0
+            p.arena_external_commit(rewards, dones)
+            if dones[live != 0].any():
+                res = p.arena_result()
+        return MatchResult(res['winner'].copy(), res['length'].copy(), res['ret'].copy(), False)
+    finally:
+        p.close()
 
 
 def run_board_game_evaluator(config, old_checkpoint_network, new_ckpt_network, device, env, temperature, checkpoint_files, stop_event,
@@ -663,7 +728,8 @@ def run_evaluator(config, new_ckpt_network, device, env, temperature, checkpoint
     triples is returned.
 
     `device_episodes` > 0: each checkpoint plays that many episodes in lock-step on the device twin of `env` instead (`play_match`
-    with no opponent); the same tracker calls receive their returns and lengths."""
+    with no opponent; CartPole, or Catch on the device arena), or, when `env` is a list or a factory `i -> env` of host env objects,
+    through the host-stepped arena; the same tracker calls receive their returns and lengths."""
     from muzero_amd import mcts
 
     for p in new_ckpt_network.parameters():

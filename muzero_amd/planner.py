@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
     'mz_selfplay_reset_catch',
     'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
+    'mz_arena_reset_catch', 'mz_arena_reset_external', 'mz_arena_external_act', 'mz_arena_external_commit',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
 ]
 
@@ -117,6 +118,10 @@ def load_library():
     L.mz_arena_step.argtypes = [vp, i32]
     L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
     L.mz_arena_result.argtypes = [vp, vp, vp, vp, i64p, vp]
+    L.mz_arena_reset_catch.argtypes = [vp, C.POINTER(MzCatchEnv), vp, vp]
+    L.mz_arena_reset_external.argtypes = [vp, C.POINTER(MzExternalEnv)]
+    L.mz_arena_external_act.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.mz_arena_external_commit.argtypes = [vp, vp, vp]
     L.mz_profile_begin.argtypes = [vp]
     L.mz_profile_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mz_planner_synchronize.argtypes = [vp]
@@ -625,6 +630,56 @@ class Planner:
         init = None if init_state is None else np.ascontiguousarray(init_state, np.float64).reshape(self.B, 4)
         _chk(self.lib.mz_arena_reset(self.h, int(env_kind), kind, q.h if q is not None else None, int(opening_plies), _p(init)))
         self._arena_opponent = q
+
+    def arena_reset_catch(self, rows=12, cols=12, ball_cols=None, start_rows=None):
+        """Start `num_envs` evaluation games of the device Catch env (mz_arena_reset_catch; geometry as `selfplay_reset_catch`).  Env e
+        starts with the paddle at cols // 2 and the ball in column `ball_cols[e]` (default e % cols: every column equally often) and row
+        `start_rows[e]` (default 0; 0 .. rows - 2).  `arena_step` then plays whole plies on the device."""
+        bc = None if ball_cols is None else np.ascontiguousarray(ball_cols, np.int32).reshape(self.B)
+        sr = None if start_rows is None else np.ascontiguousarray(start_rows, np.int32).reshape(self.B)
+        x = MzCatchEnv(int(rows), int(cols), 0)
+        _chk(self.lib.mz_arena_reset_catch(self.h, C.byref(x), _p(bc), _p(sr)))
+        self._arena_opponent = None
+
+    def arena_reset_external(self, stack_history=0, is_obs_image=False, frame_shape=None, frame_u8=False, max_episode_steps=0):
+        """Start `num_envs` evaluation games on envs stepped by the caller (mz_arena_reset_external).  The frames are described as for
+        `selfplay_reset_external`; `arena_external_act` / `arena_external_commit` play a ply around the caller's env.step."""
+        if frame_shape is None:
+            frame_shape = (self.obs_dim,)
+        fs = tuple(int(d) for d in frame_shape)
+        if is_obs_image:
+            if len(fs) != 3:
+                raise ValueError(f'image frames are [C, H, W], got {fs}')
+            c, h, w = fs
+        else:
+            c, h, w = int(np.prod(fs)), 1, 1
+        x = MzExternalEnv(int(stack_history), int(bool(is_obs_image)), c, h, w, int(bool(frame_u8)), int(max_episode_steps), 0, 0)
+        _chk(self.lib.mz_arena_reset_external(self.h, C.byref(x)))
+        self._arena_frame = (fs, np.uint8 if frame_u8 else np.float32)
+        self._arena_opponent = None
+
+    def arena_external_act(self, frames, mask, cur, opp):
+        """One deterministic search over every env's newest frame (see arena_reset_external): frames [B, ...], mask [B, A], cur / opp [B]
+        player ids; the entries of finished (frozen) envs are ignored.  Returns (actions int32 [B], live uint8 [B]): step env e with
+        actions[e] where live[e] is 1."""
+        shape, dt = self._arena_frame
+        B = self.B
+        f = np.ascontiguousarray(frames, dt)
+        if f.size != B * int(np.prod(shape)):
+            raise ValueError(f'frames: expected {B} frames of shape {shape}, got an array of shape {f.shape}')
+        m = np.ascontiguousarray(mask, np.uint8).reshape(B, self.A)
+        c = np.ascontiguousarray(np.broadcast_to(cur, (B,)), np.int32)
+        o = np.ascontiguousarray(np.broadcast_to(opp, (B,)), np.int32)
+        action, live = np.empty(B, np.int32), np.empty(B, np.uint8)
+        _chk(self.lib.mz_arena_external_act(self.h, _p(f), _p(m), _p(c), _p(o), _p(action), _p(live)))
+        return action, live
+
+    def arena_external_commit(self, reward, done):
+        """The outcome of the last `arena_external_act`'s actions on the live envs: reward [B] (float32), done [B] (frozen envs' entries
+        are ignored).  A done env is frozen and tallied."""
+        r = np.ascontiguousarray(np.broadcast_to(reward, (self.B,)), np.float32)
+        d = np.ascontiguousarray(np.broadcast_to(done, (self.B,)), np.uint8)
+        _chk(self.lib.mz_arena_external_commit(self.h, _p(r), _p(d)))
 
     def arena_step(self, n_plies=1):
         """`n_plies` lock-step plies, enqueued without a host synchronisation."""
