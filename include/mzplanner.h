@@ -36,6 +36,7 @@ extern "C" {
 #define MZ_ENV_SYNTHETIC 4 /* stand-in for the Atari emulator (absent dependency): fresh U[0,1) frames, reward 0, 1000-step episodes */
 #define MZ_ENV_EXTERNAL 5  /* any environment the caller steps on the host (mz_selfplay_reset_external) */
 #define MZ_ENV_CATCH 6     /* Catch as an image game on the device: uint8 frames through the host-stepped path's kernels (mz_selfplay_reset_catch) */
+#define MZ_ENV_BREAKOUT 7  /* a brick-breaking image game on the device, rewards during the episode (mz_selfplay_reset_breakout) */
 
 /* Everything uct_search reads from MuZeroConfig (config.py:51-103) and from the network constructors
  * (network.py:239-247, 504-512, 543-549), plus planner-only sizing knobs. */
@@ -324,6 +325,32 @@ typedef struct {
 } mz_catch_env;
 int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env);
 
+/* Breakout (MZ_ENV_BREAKOUT): the second device image game, on Catch's pattern, with what Catch lacks: a reward during the episode (1 per
+ * brick), episodes that end on a miss or on a move cap, and lengths that differ from env to env.  muzero_amd.games.BreakoutEnv is the
+ * specification: a rows x cols grid (cols <= 32); bricks fill rows 1 .. brick_rows, row 0 is empty, the paddle lives in the last row; the
+ * ball moves diagonally (d: 0 up-left, 1 up-right, 2 down-right, 3 down-left).  A move: the paddle moves left / stays / right (actions
+ * 0 / 1 / 2, clipped at the walls); the ball's next cell is computed, a side wall clamps the column and flips d horizontally; then exactly
+ * one of: above the grid -> row 0, d flips vertically | a brick there -> it is removed, reward 1, the ball keeps its row, d flips
+ * vertically | the paddle's row -> the bricks are refilled if none is left, then the ball bounces (ball column == paddle: d flips
+ * vertically; next column == paddle: d flips both ways; the ball keeps its row) or the episode ends with reward 0 | nothing.  The move
+ * count reaching max_moves ends the episode too (a brick reward may fall on that move).  Frame: background 0, bricks 96, the ball's last
+ * cell 64, paddle 160, ball 255; priority ball, paddle, trail, brick.  Mask all legal, players 1 / 1.  A finished env restarts at once from
+ * start code k = min(2 cols - 1, floor(u * 2 cols)), u the first double of Philox(seed, e, episode, 0x71000000): ball column k >> 1, row
+ * brick_rows + 1, d = 2 + (k & 1), paddle at cols / 2, all bricks.  There is no stagger.
+ * Geometry comes from the planner's mz_config as for Catch: obs_c = 2 S, frames [1, obs_h, obs_w], cells of obs_h / rows x obs_w / cols
+ * (both must divide), num_actions == 3, is_board_game == 0.  Refusals (MZ_E_INVALID) name the field: cols > 32 or < 3, rows <
+ * brick_rows + 3, brick_rows outside 1..3, max_moves < 1.  record_format and the attached replay's state_format follow mz_external_env's
+ * rules (MZ_STATE_I8 is refused).  Afterwards the handle behaves as after mz_selfplay_reset_catch: mz_selfplay_step plays whole moves on
+ * the device; mz_selfplay_external_act / _commit return MZ_E_STATE; mz_selfplay_reset and mz_arena_reset refuse the kind by naming the
+ * right reset. */
+typedef struct {
+    int32_t rows, cols;     /* the grid; rows = cols = 0: 12 x 12 */
+    int32_t brick_rows;     /* 1..3; 0: 3 */
+    int32_t max_moves;      /* the move cap; 0: 200 */
+    int32_t record_format;  /* MZ_RECORD_F32 or MZ_RECORD_FRAMES_U8 */
+} mz_breakout_env;
+int mz_selfplay_reset_breakout(mz_planner* p, const mz_breakout_env* env);
+
 /* Arena: the evaluators' game loops (pipeline.py:289-397 board games, pipeline.py:400-488 one-player envs) for num_envs games in
  * lock-step on the device.  Every searched move is uct_search(deterministic = True) on the planner's search kernels: no root noise, the
  * most-visited child, tie draws consumed as mz_planner_search consumes them (mz_debug_capture_rng reads them back per handle).  The
@@ -341,7 +368,7 @@ int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env);
  *   envs) from a Philox stream of their own: both games of a pair start from the same position with colours swapped.
  *   Random moves (openings, MZ_ARENA_RANDOM): legal[floor(u * n_legal)], u one Philox double per (pair or env, ply), recorded.
  *   Game length is capped by the env: 500 steps (CartPole), the point count (boards).
- * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC: MZ_E_INVALID; MZ_ENV_CATCH and MZ_ENV_EXTERNAL:
+ * mz_arena_reset: env_kind MZ_ENV_CARTPOLE / _TICTACTOE / _GOMOKU (MZ_ENV_SYNTHETIC: MZ_E_INVALID; MZ_ENV_CATCH, MZ_ENV_BREAKOUT and MZ_ENV_EXTERNAL:
  * MZ_E_INVALID naming the reset that plays them, below); h_init_state as mz_selfplay_reset (CartPole only).  Arena and self-play exclude
  * each other on a handle: mz_selfplay_step and mz_selfplay_external_act / _commit during an arena are MZ_E_STATE, mz_arena_step without an
  * arena reset (e.g. during self-play) is MZ_E_STATE; each mode's reset enters it and frees what the other left.
@@ -375,6 +402,11 @@ int mz_arena_step(mz_planner* p, int32_t n_plies);
  * crossing PCIe and no host synchronisation: roots from the frames, one deterministic search of all num_envs roots, the env's step without
  * restart, the next frame.  A game ends when the ball reaches the last row: ret +1.0 or -1.0, length the plies played. */
 int mz_arena_reset_catch(mz_planner* p, const mz_catch_env* env, const int32_t* h_ball_col_or_null, const int32_t* h_start_row_or_null);
+/* Breakout in the arena.  Geometry and refusals are mz_selfplay_reset_breakout's; record_format must be MZ_RECORD_F32.  Env e starts from
+ * start code h_start_code[e] (NULL: e % (2 * cols)); an entry outside 0 .. 2 * cols - 1 is MZ_E_INVALID naming the array and the env.  No
+ * Philox draw is used.  mz_arena_step plays plies as for Catch; a game ends on a miss or at max_moves: ret is the number of bricks broken,
+ * length the plies played. */
+int mz_arena_reset_breakout(mz_planner* p, const mz_breakout_env* env, const int32_t* h_start_code_or_null);
 /* The same ply for envs the host steps, cut where it steps them.  `env` describes the frames as for mz_selfplay_reset_external (stacked
  * uint8 or float images, stacked vectors, stack_history = 0 for whole observations); max_episode_steps and temp_switch_steps are not used.
  *   mz_arena_external_act    -- uploads every env's newest frame, mask and player ids (arguments as mz_selfplay_external_act's; the entries

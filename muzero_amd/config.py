@@ -158,3 +158,20 @@ def make_catch_config(num_training_steps=3000, batch_size=128, min_replay_size=2
     cfg.num_actions, cfg.stack_history, cfg.rows, cfg.cols = 3, stack_history, rows, cols
     cfg.input_shape = (2 * stack_history, rows * cell, cols * cell)
     return cfg
+
+
+def make_breakout_config(num_training_steps=3000, batch_size=128, min_replay_size=2000, rows=12, cols=12, cell=8, stack_history=4, brick_rows=3,
+                         max_moves=200, use_tensorboard=False, clip_grad=False) -> MuZeroConfig:
+    """Breakout (`games.BreakoutEnv`, the device env 'Breakout') for `MuZeroAtariNet`: Catch's small net and schedule on a game that pays a
+    reward per brick during episodes of up to `max_moves` moves.  td_steps = 10 with discount 0.997 is the Atari config's bootstrapped
+    n-step value target; acc_seq_length = 16 cuts the long episodes into sequences, so the step cap, the reward head and the bootstrap all
+    carry signal here.  Not in the reference; the extra attributes describe the env."""
+    cfg = MuZeroConfig(
+        discount=0.997, dirichlet_alpha=0.25, num_simulations=25, batch_size=batch_size, td_steps=10, lr_init=0.002,
+        lr_milestones=[100e3], visit_softmax_temperature_fn=catch_visit_softmax_temperature_fn, num_training_steps=num_training_steps,
+        num_planes=32, num_res_blocks=2, hidden_dim=0, value_support_size=11, reward_support_size=11, min_replay_size=min_replay_size,
+        checkpoint_interval=100, acc_seq_length=16, train_delay=0.0, clip_grad=clip_grad, use_tensorboard=use_tensorboard, is_board_game=False,
+    )
+    cfg.num_actions, cfg.stack_history, cfg.rows, cfg.cols, cfg.brick_rows, cfg.max_moves = 3, stack_history, rows, cols, brick_rows, max_moves
+    cfg.input_shape = (2 * stack_history, rows * cell, cols * cell)
+    return cfg

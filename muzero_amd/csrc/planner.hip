@@ -18,6 +18,7 @@
 #include "mz_arena_image.h"
 #include "mz_extenv.h"
 #include "mz_catch.h"
+#include "mz_breakout.h"
 #include "mz_search.h"
 #include "mz_search_fast.h"
 #include "mz_convnet.h"
@@ -216,13 +217,14 @@ struct mz_planner {
     int rec_S = 0;                 // its stack_history
     float* d_rec_stage = nullptr;  // [B][obs] one move of decoded observations (mz_selfplay_read, allocated by the first read)
     CatchEnv catch_env{};          // MZ_ENV_CATCH (mz_catch.h): the game's state; frames, rewards and done flags are ext's buffers
+    BreakoutEnv breakout_env{};    // MZ_ENV_BREAKOUT (mz_breakout.h): likewise
 
     // arena (mz_arena.h): evaluation games in lock-step on this handle's env state
     ArenaState arena{};
     bool arena_open = false;
     int arena_ply = 0;
     mz_planner* arena_q = nullptr;  // the borrowed opponent planner (MZ_ARENA_PLANNER)
-    int arena_img = 0;              // IMGARENA_CATCH / IMGARENA_EXTERNAL: the roots come from ext's frame history (mz_arena_image.h)
+    int arena_img = 0;              // IMGARENA_CATCH / _BREAKOUT / _EXTERNAL: the roots come from ext's frame history (mz_arena_image.h)
     bool arena_pending = false;     // host-stepped arena: an act is waiting for its commit
     std::vector<unsigned char> arena_live_h;  // host-stepped arena: the live flags (the host uploads every done flag, so it knows them)
     hipEvent_t ev_arena_pre = nullptr, ev_arena_q = nullptr;  // order the two planners' streams within a ply
@@ -596,7 +598,10 @@ static int planner_init(mz_planner* p, bool conv) {
 }
 
 static void ext_free(mz_planner* p);
-static int catch_moves(mz_planner* p, double temperature, int n_moves);
+struct ImageGame;
+static const ImageGame* image_game(int env_kind);
+static int image_game_moves(mz_planner* p, const ImageGame& g, double temperature, int n_moves);
+static int image_game_plies(mz_planner* p, const ImageGame& g, int n_plies);
 
 extern "C" int mz_planner_destroy(mz_planner* p) {
     if (!p) return MZ_OK;
@@ -1595,6 +1600,8 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         if (h_init_state) return fail(MZ_E_INVALID, "the synthetic env takes no initial state");
     } else if (env_kind == MZ_ENV_CATCH) {
         return fail(MZ_E_INVALID, "MZ_ENV_CATCH has its own reset: mz_selfplay_reset_catch");
+    } else if (env_kind == MZ_ENV_BREAKOUT) {
+        return fail(MZ_E_INVALID, "MZ_ENV_BREAKOUT has its own reset: mz_selfplay_reset_breakout");
     } else {
         return fail(MZ_E_INVALID, "unknown env kind");
     }
@@ -1632,7 +1639,7 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
     if (p->env_kind == MZ_ENV_EXTERNAL) return fail(MZ_E_STATE, "mz_selfplay_step on host-stepped envs: use mz_selfplay_external_act / _commit");
     if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
-    if (p->env_kind == MZ_ENV_CATCH) return catch_moves(p, temperature, n_moves);
+    if (const ImageGame* g = image_game(p->env_kind)) return image_game_moves(p, *g, temperature, n_moves);
     const mz_config& c = p->cfg;
     for (int m = 0; m < n_moves; m++) {
         EnvLaunch L{};
@@ -1678,6 +1685,8 @@ static void ext_free(mz_planner* p) {
     for (void* b : cbufs)
         if (b) (void)hipFree(b);
     p->catch_env = CatchEnv{};
+    if (p->breakout_env.s) (void)hipFree(p->breakout_env.s);
+    p->breakout_env = BreakoutEnv{};
     p->h_ext_frames = nullptr; p->h_ext_mask = p->h_ext_done = nullptr;
     p->h_ext_cur = p->h_ext_opp = p->h_ext_action = p->h_ext_err = nullptr;
     p->h_ext_reward = nullptr;
@@ -1721,7 +1730,7 @@ static int ext_alloc(mz_planner* p, const mz_external_env* x) {
     X.temp_steps = x->temp_switch_steps > 0 ? x->temp_switch_steps : (c.num_actions <= 10 ? 6 : 30);
     p->ext_od = obs_dim(c);
     const size_t B = (size_t)c.num_envs, fbytes = (size_t)FE * (X.u8 ? 1 : 4);
-    HIPCHK(hipMalloc(&X.frames, (B * fbytes + 15) / 16 * 16));  // (whole 16-byte runs: k_catch_render stores nothing narrower)
+    HIPCHK(hipMalloc(&X.frames, (B * fbytes + 15) / 16 * 16));  // (whole 16-byte runs: the device games' renderers store nothing narrower)
     if (S > 0) {
         HIPCHK(hipMalloc(&X.hist, B * S * fbytes));
         HIPCHK(hipMalloc(&X.hist_act, B * S * sizeof(int)));
@@ -1991,20 +2000,130 @@ extern "C" int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env) {
     return MZ_OK;
 }
 
-// mz_selfplay_step on Catch: per move the act's device work, the env's step and next frame, the commit's device work, the epilogue.
-// Nothing is copied and nothing waits inside the loop.  What the host-stepped path reads back per commit is read back once per call, and
-// only with a replay attached (one synchronisation at the end of the call): the record ring's capacity check -- a guard here, the reset
-// sized the ring for the game's fixed episode length, so the moves of this call already ran their epilogues when it is read -- and the
+// ---------------------------------------------------------------------------------------------------------
+// Breakout (mz_breakout.h): the second device image game
+// ---------------------------------------------------------------------------------------------------------
+static BreakoutLaunch breakout_launch(mz_planner* p) {
+    BreakoutLaunch G{};
+    G.c = p->breakout_env; G.B = p->cfg.num_envs; G.seed = p->cfg.seed;
+    G.action = p->d_action; G.episode = p->env.episode; G.reward = p->ext.reward; G.done = p->ext.done;
+    G.frames = static_cast<unsigned char*>(p->ext.frames); G.mask = p->d_mask; G.cur = p->d_cur; G.opp = p->d_opp;
+    return G;
+}
+
+static void breakout_render(mz_planner* p) {
+    const BreakoutLaunch G = breakout_launch(p);
+    const size_t runs = ((size_t)G.B * G.c.FE + 15) / 16;
+    hipLaunchKernelGGL(k_breakout_render, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, G);
+}
+
+// Breakout's geometry off the planner's mz_config, for the reset `fn`: the grid with its defaults filled in, and the frames as an
+// mz_external_env
+static int breakout_geometry(mz_planner* p, const mz_breakout_env* env, const std::string& fn, mz_breakout_env& g, mz_external_env& x) {
+    const mz_config& c = p->cfg;
+    g = *env;
+    if (g.rows == 0 && g.cols == 0) g.rows = g.cols = 12;
+    if (g.brick_rows == 0) g.brick_rows = 3;
+    if (g.max_moves == 0) g.max_moves = 200;
+    if (c.is_board_game) return fail(MZ_E_INVALID, fn + ": is_board_game must be 0 (Breakout is a one-player game)");
+    if (c.num_actions != 3) return fail(MZ_E_INVALID, fn + ": num_actions must be 3 (left, stay, right), not " + std::to_string(c.num_actions));
+    if (c.obs_c < 2 || (c.obs_c & 1))
+        return fail(MZ_E_INVALID, fn + ": obs_c must be 2 * stack_history (S one-channel frames and S action planes), not " + std::to_string(c.obs_c));
+    if (g.brick_rows < 1 || g.brick_rows > 3) return fail(MZ_E_INVALID, "mz_breakout_env.brick_rows must be 1, 2 or 3, not " + std::to_string(g.brick_rows));
+    if (g.max_moves < 1) return fail(MZ_E_INVALID, "mz_breakout_env.max_moves must be >= 1, not " + std::to_string(g.max_moves));
+    if (g.cols > 32) return fail(MZ_E_INVALID, "mz_breakout_env.cols must be <= 32 (a brick row is one 32-bit mask), not " + std::to_string(g.cols));
+    if (g.rows < g.brick_rows + 3 || c.obs_h % g.rows != 0)
+        return fail(MZ_E_INVALID, "mz_breakout_env.rows must be >= brick_rows + 3 = " + std::to_string(g.brick_rows + 3) + " and divide obs_h = " +
+                                      std::to_string(c.obs_h) + ", not " + std::to_string(g.rows));
+    if (g.cols < 3 || c.obs_w % g.cols != 0)
+        return fail(MZ_E_INVALID, "mz_breakout_env.cols must be >= 3 and divide obs_w = " + std::to_string(c.obs_w) + ", not " + std::to_string(g.cols));
+    x = mz_external_env{};
+    x.stack_history = c.obs_c / 2; x.is_obs_image = 1; x.frame_c = 1; x.frame_h = c.obs_h; x.frame_w = c.obs_w; x.frame_u8 = 1;
+    x.max_episode_steps = g.max_moves;  // (an episode's longest: the record ring always holds an open trajectory)
+    x.record_format = g.record_format;
+    return MZ_OK;
+}
+
+// the game's state array (after ext_free)
+static int breakout_alloc(mz_planner* p, const mz_breakout_env& g) {
+    const mz_config& c = p->cfg;
+    BreakoutEnv& K = p->breakout_env;
+    K.rows = g.rows; K.cols = g.cols; K.K = g.brick_rows; K.max_moves = g.max_moves;
+    K.ch = c.obs_h / g.rows; K.cw = c.obs_w / g.cols; K.H = c.obs_h; K.W = c.obs_w; K.FE = c.obs_h * c.obs_w; K.B = c.num_envs;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.s), (size_t)BREAKOUT_FIELDS * c.num_envs * sizeof(int)));
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_reset_breakout(mz_planner* p, const mz_breakout_env* env) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_breakout");
+    const mz_config& c = p->cfg;
+    mz_breakout_env g;
+    mz_external_env x;
+    int rc = breakout_geometry(p, env, "mz_selfplay_reset_breakout", g, x);
+    if (rc) return rc;
+    if (p->has_replay && p->replay.state_format == STATE_I8)
+        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: Breakout observations (frame bytes / 255, action planes of 1/3, 2/3) are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
+    rc = ext_reset(p, &x, MZ_ENV_BREAKOUT, "mz_breakout_env");
+    if (rc) return rc;
+    rc = breakout_alloc(p, g);
+    if (rc) return rc;
+    const BreakoutLaunch G = breakout_launch(p);
+    hipLaunchKernelGGL(k_breakout_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
+    breakout_render(p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Device image games behind one table: what differs between them is the env's step (self-play: with restart; arena: with the ply record
+// and the freeze) and its renderer; their resets (own entry points: the env structs differ) share ext_reset / imgarena_reset.  A game is
+// one header and one row here.
+// ---------------------------------------------------------------------------------------------------------
+struct ImageGame {
+    int env_kind;
+    const char* reset_name;                                   // the self-play reset, named in refusals
+    void (*step)(mz_planner*);                                // self-play: ext.reward / ext.done, restart on done
+    void (*render)(mz_planner*);                              // every env's next frame into ext.frames
+    void (*arena_step)(mz_planner*, const ImgArenaLaunch&);   // arena: ply record, step, outcome, freeze
+};
+
+static const ImageGame IMAGE_GAMES[] = {
+    {MZ_ENV_CATCH, "mz_selfplay_reset_catch",
+     [](mz_planner* p) { hipLaunchKernelGGL(k_catch_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, catch_launch(p)); },
+     [](mz_planner* p) { catch_render(p, catch_launch(p)); },
+     [](mz_planner* p, const ImgArenaLaunch& R) {
+         hipLaunchKernelGGL(k_imgarena_catch_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, R);
+     }},
+    {MZ_ENV_BREAKOUT, "mz_selfplay_reset_breakout",
+     [](mz_planner* p) { hipLaunchKernelGGL(k_breakout_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, breakout_launch(p)); },
+     breakout_render,
+     [](mz_planner* p, const ImgArenaLaunch& R) {
+         BreakoutArenaLaunch Q{R, p->breakout_env};
+         hipLaunchKernelGGL(k_breakout_arena_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, Q);
+     }},
+};
+
+static const ImageGame* image_game(int env_kind) {
+    for (const ImageGame& g : IMAGE_GAMES)
+        if (g.env_kind == env_kind) return &g;
+    return nullptr;
+}
+
+// mz_selfplay_step on a device image game: per move the act's device work, the env's step and next frame, the commit's device work, the
+// epilogue.  Nothing is copied and nothing waits inside the loop.  What the host-stepped path reads back per commit is read back once per
+// call, and only with a replay attached (one synchronisation at the end of the call): the record ring's capacity check -- a guard here, the
+// reset sized the ring for the game's longest episode, so the moves of this call already ran their epilogues when it is read -- and the
 // search kernels' error word.
-static int catch_moves(mz_planner* p, double temperature, int n_moves) {
-    if (p->ext_broken) return fail(MZ_E_STATE, "an earlier mz_selfplay_step found an over-long trajectory or a search error: call mz_selfplay_reset_catch");
-    const CatchLaunch G = catch_launch(p);
+static int image_game_moves(mz_planner* p, const ImageGame& g, double temperature, int n_moves) {
+    if (p->ext_broken)
+        return fail(MZ_E_STATE, std::string("an earlier mz_selfplay_step found an over-long trajectory or a search error: call ") + g.reset_name);
     for (int m = 0; m < n_moves; m++) {
         const ExtLaunch L = ext_launch(p, temperature);
         int rc = ext_enqueue_act(p, L);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_catch_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
-        catch_render(p, G);
+        g.step(p);
+        g.render(p);
         rc = ext_enqueue_commit(p, L);
         if (rc) return rc;
         rc = ring_finish_move(p);
@@ -2196,6 +2315,8 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
         num_to_win = 5;
     } else if (env_kind == MZ_ENV_CATCH) {
         return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_CATCH has its own arena reset: mz_arena_reset_catch");
+    } else if (env_kind == MZ_ENV_BREAKOUT) {
+        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_BREAKOUT has its own arena reset: mz_arena_reset_breakout");
     } else if (env_kind == MZ_ENV_EXTERNAL) {
         return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_EXTERNAL has its own arena reset: mz_arena_reset_external");
     } else {
@@ -2247,8 +2368,6 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
     return MZ_OK;
 }
 
-static int imgarena_catch_plies(mz_planner* p, int n_plies);
-
 extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     if (!p || n_plies < 1) return fail(MZ_E_INVALID, "bad argument to mz_arena_step");
     if (!p->arena_open) return fail(MZ_E_STATE, "call mz_arena_reset first");
@@ -2256,7 +2375,7 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     mz_planner* q = p->arena_q;
     if (!p->committed || (q && !q->committed)) return fail(MZ_E_STATE, "weights not committed");
     HIPCHK(hipSetDevice(p->device));
-    if (p->arena_img == IMGARENA_CATCH) return imgarena_catch_plies(p, n_plies);
+    if (p->arena_img) return image_game_plies(p, *image_game(p->env_kind), n_plies);  // (a device image game: the host-stepped arena left above)
     const mz_config& c = p->cfg;
     const int B = c.num_envs, half = p->arena.half;
     const dim3 waves((B + 3) / 4), block(256);
@@ -2472,19 +2591,56 @@ static int imgarena_enqueue_search(mz_planner* p, const ImgArenaLaunch& R) {
     return launch_search(p, B, 1, true, false, false);
 }
 
-// mz_arena_step on a Catch arena: nothing is copied and nothing waits
-static int imgarena_catch_plies(mz_planner* p, int n_plies) {
-    const int B = p->cfg.num_envs;
-    const CatchLaunch G = catch_launch(p);
+// mz_arena_step on a device image game's arena: nothing is copied and nothing waits
+static int image_game_plies(mz_planner* p, const ImageGame& g, int n_plies) {
     for (int m = 0; m < n_plies; m++) {
         const ImgArenaLaunch R = imgarena_launch(p);
         int rc = imgarena_enqueue_search(p, R);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_imgarena_catch_step, dim3((B + 255) / 256), dim3(256), 0, p->stream, R);
-        catch_render(p, G);
+        g.arena_step(p, R);
+        g.render(p);
         HIPCHK(hipGetLastError());
         p->arena_ply++;
     }
+    return MZ_OK;
+}
+
+extern "C" int mz_arena_reset_breakout(mz_planner* p, const mz_breakout_env* env, const int32_t* h_start_code) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_breakout");
+    const mz_config& c = p->cfg;
+    mz_breakout_env g;
+    mz_external_env x;
+    int rc = breakout_geometry(p, env, "mz_arena_reset_breakout", g, x);
+    if (rc) return rc;
+    const int B = c.num_envs;
+    std::vector<int> code((size_t)B);
+    for (int e = 0; e < B; e++) {
+        code[e] = h_start_code ? h_start_code[e] : e % (2 * g.cols);
+        if (code[e] < 0 || code[e] >= 2 * g.cols)
+            return fail(MZ_E_INVALID, "mz_arena_reset_breakout: h_start_code[" + std::to_string(e) + "] = " + std::to_string(code[e]) + " is outside 0 .. 2 * cols - 1 = " +
+                                          std::to_string(2 * g.cols - 1));
+    }
+    rc = imgarena_reset(p, &x, MZ_ENV_BREAKOUT, IMGARENA_BREAKOUT, "mz_breakout_env");
+    if (rc) return rc;
+    rc = breakout_alloc(p, g);
+    if (rc) return rc;
+    int* d_code = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_code), (size_t)B * sizeof(int)));
+    hipError_t he = hipMemcpy(d_code, code.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        const ImgArenaLaunch R = imgarena_launch(p);
+        // (R.c.pc is null: k_imgarena_reset writes the arena state only; mask and player ids come from k_breakout_reset)
+        hipLaunchKernelGGL(k_imgarena_reset, dim3((B + 255) / 256), dim3(256), 0, p->stream, R);
+        BreakoutLaunch G = breakout_launch(p);
+        G.start = d_code; G.mask = p->arena.mask; G.cur = p->arena.cur; G.opp = p->arena.opp;
+        hipLaunchKernelGGL(k_breakout_reset, dim3((B + 255) / 256), dim3(256), 0, p->stream, G);
+        breakout_render(p);
+        he = hipGetLastError();
+        if (he == hipSuccess) he = hipStreamSynchronize(p->stream);
+    }
+    (void)hipFree(d_code);
+    HIPCHK(he);
+    p->arena_open = true;
     return MZ_OK;
 }
 

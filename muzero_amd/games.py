@@ -351,3 +351,130 @@ def catch_random_policy_return(rows: int = 12, cols: int = 12, start_row: int = 
             v = (left + v + right) / 3.0
         total += v[cols // 2]
     return float(total / cols)
+
+
+class BreakoutEnv:
+    """A brick-breaking game rendered as an image; the specification of the device env MZ_ENV_BREAKOUT (`csrc/mz_breakout.h`, same rules).
+    A `rows` x `cols` grid (cols <= 32) of `cell_h` x `cell_w` pixel cells on a uint8 frame [1, rows * cell_h, cols * cell_w].  Bricks fill
+    rows 1 .. K (`brick_rows`, 1 to 3; one bitmask per row, bit c = column c), row 0 is empty, the paddle lives in row rows - 1.  The ball
+    at (bx, by) moves diagonally, direction d in (0 up-left, 1 up-right, 2 down-right, 3 down-left).
+
+    reset with start code k in 0 .. 2 cols - 1 (the `start_code` given, else the next of `start_codes`, else a draw from the env's own
+    RandomState): bx = k >> 1, by = K + 1, d = 2 + (k & 1), px = cols // 2, trail (lx, ly) = (bx, by), all bricks, t = 0.
+
+    step(a), a in (0 left, 1 stay, 2 right), in this order: px = clip(px + a - 1, 0, cols - 1); (nx, ny) = (bx, by) + delta[d]; nx off the
+    grid is clamped and d flips horizontally; then exactly one of: ny < 0 -> ny = 0, d flips vertically | a brick at (ny, nx) -> it is
+    removed, reward 1, ny = by, d flips vertically | ny == rows - 1 -> first the bricks are refilled if none is left, then bx == px: d flips
+    vertically, ny = by; else nx == px: d flips both ways, ny = by; else the episode ends with reward 0 | nothing.  Then the trail becomes
+    the old ball cell, the ball moves, t += 1, and t == max_moves ends the episode (a brick reward and the cap may fall on one move).
+
+    Frame: background 0, bricks 96, trail cell 64, paddle cell 160, ball cell 255; where cells coincide ball > paddle > trail > brick."""
+
+    name = 'Breakout'
+    num_actions = 3
+    DX, DY = (-1, 1, 1, -1), (-1, -1, 1, 1)
+    FLIPX, FLIPY, FLIPBOTH = (1, 0, 3, 2), (3, 2, 1, 0), (2, 3, 0, 1)
+    BRICK, TRAIL, PADDLE, BALL = 96, 64, 160, 255
+
+    def __init__(self, rows: int = 12, cols: int = 12, cell_h: int = 8, cell_w: int = 8, brick_rows: int = 3, max_moves: int = 200, seed: int = 1,
+                 start_codes=None) -> None:
+        if not 1 <= brick_rows <= 3 or rows < brick_rows + 3 or not 3 <= cols <= 32 or cell_h < 1 or cell_w < 1 or max_moves < 1:
+            raise ValueError('BreakoutEnv needs brick_rows in 1..3, rows >= brick_rows + 3, 3 <= cols <= 32, cells of at least one pixel and max_moves >= 1')
+        self.rows, self.cols, self.cell_h, self.cell_w, self.brick_rows, self.max_moves = rows, cols, cell_h, cell_w, brick_rows, max_moves
+        self.observation_shape = (1, rows * cell_h, cols * cell_w)
+        self.max_episode_steps = max_moves
+        self._rs = np.random.RandomState(seed)
+        self._codes = None if start_codes is None else iter(start_codes)
+        self.bx = self.by = self.d = self.px = self.lx = self.ly = self.t = 0
+        self.bricks = [0] * brick_rows
+        self.done = True
+
+    def reset(self, start_code: Optional[int] = None) -> np.ndarray:
+        if start_code is None:
+            start_code = next(self._codes) if self._codes is not None else self._rs.randint(2 * self.cols)
+        if not 0 <= start_code < 2 * self.cols:
+            raise ValueError(f'start code {start_code} outside 0 .. {2 * self.cols - 1}')
+        k = int(start_code)
+        self.bx, self.by, self.d, self.px = k >> 1, self.brick_rows + 1, 2 + (k & 1), self.cols // 2
+        self.lx, self.ly, self.t, self.done = self.bx, self.by, 0, False
+        self.bricks = [(1 << self.cols) - 1] * self.brick_rows
+        return self.render()
+
+    def step(self, action: int):
+        if self.done:
+            raise RuntimeError('Episode is over, call reset before using step method.')
+        if action not in (0, 1, 2):
+            raise ValueError(f'Invalid action {action}')
+        self.px = min(max(self.px + int(action) - 1, 0), self.cols - 1)
+        d = self.d
+        nx, ny, reward = self.bx + self.DX[d], self.by + self.DY[d], 0.0
+        if nx < 0 or nx > self.cols - 1:
+            nx, d = min(max(nx, 0), self.cols - 1), self.FLIPX[d]
+        if ny < 0:
+            ny, d = 0, self.FLIPY[d]
+        elif 1 <= ny <= self.brick_rows and (self.bricks[ny - 1] >> nx) & 1:
+            self.bricks[ny - 1] &= ~(1 << nx)
+            reward, ny, d = 1.0, self.by, self.FLIPY[d]
+        elif ny == self.rows - 1:
+            if not any(self.bricks):
+                self.bricks = [(1 << self.cols) - 1] * self.brick_rows
+            if self.bx == self.px:
+                d, ny = self.FLIPY[d], self.by
+            elif nx == self.px:
+                d, ny = self.FLIPBOTH[d], self.by
+            else:
+                self.done = True
+        self.lx, self.ly, self.bx, self.by, self.d = self.bx, self.by, nx, ny, d
+        self.t += 1
+        if self.t == self.max_moves:
+            self.done = True
+        return self.render(), reward, self.done, {}
+
+    def render(self) -> np.ndarray:
+        h, w = self.cell_h, self.cell_w
+        frame = np.zeros(self.observation_shape, np.uint8)
+
+        def paint(r, c, v):
+            frame[0, r * h:(r + 1) * h, c * w:(c + 1) * w] = v
+
+        for k, m in enumerate(self.bricks):
+            for c in range(self.cols):
+                if (m >> c) & 1:
+                    paint(k + 1, c, self.BRICK)
+        paint(self.ly, self.lx, self.TRAIL)
+        paint(self.rows - 1, self.px, self.PADDLE)
+        paint(self.by, self.bx, self.BALL)
+        return frame
+
+
+def make_breakout_env(rows: int = 12, cols: int = 12, cell_h: int = 8, cell_w: int = 8, stack_history: int = 4, **kwargs):
+    """`BreakoutEnv` as the Atari nets see it: PlayerIdAndActionMaskWrapper(StackFrameAndAction(ScaledFloatFrame(env), stack_history, True)),
+    observations float32 [2 * stack_history, rows * cell_h, cols * cell_w]."""
+    return PlayerIdAndActionMaskWrapper(StackFrameAndAction(ScaledFloatFrame(BreakoutEnv(rows, cols, cell_h, cell_w, **kwargs)), stack_history, True))
+
+
+BREAKOUT_STREAM = 0x71000000  # the start code's Philox stream (mz_breakout.h BREAKOUT_STREAM)
+
+
+def _philox_uniform(seed: int, c1: int, c2: int, c3: int) -> float:
+    """The first double of the device stream Philox(seed, c1, c2, c3) (Philox4x32-10 as `csrc/mz_device.h` keys it: counter (0, c1, c2,
+    c3), key (seed low, seed high); uniform = ((r0 >> 5) * 2^26 + (r1 >> 6)) / 2^53)."""
+    M = 0xFFFFFFFF
+    c = [0, c1 & M, c2 & M, c3 & M]
+    k0, k1 = seed & M, (seed >> 32) & M
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [((p1 >> 32) ^ c[1] ^ k0) & M, p1 & M, ((p0 >> 32) ^ c[3] ^ k1) & M, p0 & M]
+        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    return ((c[0] >> 5) * 67108864.0 + (c[1] >> 6)) / 9007199254740992.0
+
+
+def breakout_start_code(seed: int, env: int, episode: int, cols: int) -> int:
+    """The start code the device Breakout env draws for episode `episode` of env `env` in self-play on a planner seeded `seed`:
+    min(2 cols - 1, floor(u * 2 cols)), u the first double of Philox(seed, env, episode, 0x71000000)."""
+    return min(2 * cols - 1, int(np.floor(_philox_uniform(int(seed), int(env), int(episode), BREAKOUT_STREAM) * (2 * cols))))
+
+
+def breakout_track_action(env) -> int:
+    """The scripted policy that tracks the ball: move the paddle towards the column the ball is in (a `BreakoutEnv`, or a wrapper of one)."""
+    return 1 + int(np.sign(env.bx - env.px))

@@ -214,7 +214,15 @@ class EpisodeAssembler:
         del self.open[b][:n]
 
 
-DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari', 'Catch')
+DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari', 'Catch', 'Breakout')
+IMAGE_GAMES = ('Catch', 'Breakout')  # device envs drawn on the network's own frame: the planner keeps the [C, H, W] input shape
+
+
+def _breakout_args(env) -> dict:
+    """The grid of a `games.BreakoutEnv` (or a wrapper of one) as the planner's Breakout resets take it; the defaults for a name."""
+    return dict(rows=int(getattr(env, 'rows', 12)), cols=int(getattr(env, 'cols', 12)), brick_rows=int(getattr(env, 'brick_rows', 3)),
+                max_moves=int(getattr(env, 'max_moves', 200)))
+
 MAX_ENV_THREADS = 16
 
 
@@ -286,7 +294,8 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
                   record_format: str = 'f32') -> int:
     """Self-play until `stop_event` is set (pipeline.py:41-167).  `env` names a device environment ('CartPole-v1',
     'TicTacToe', 'Gomoku', 'Synthetic-Atari': random frames standing in for the absent emulator, or 'Catch': `games.CatchEnv` on the
-    device, its grid read off `env` when that is a CatchEnv object, else 12 x 12 on the network's frame); `config.num_envs` of them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
+    device, its grid read off `env` when that is a CatchEnv object, else 12 x 12 on the network's frame, or 'Breakout': `games.BreakoutEnv`
+    likewise, with its brick rows and move cap); `config.num_envs` of them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
     `(Transition, priority)` tuples, assembled on the host from the device records -- or a
     `muzero_amd.replay.PrioritizedReplay(device='cuda')`: then the planner's DEVICE EPILOGUE builds the items on the GPU and
     writes them straight into that replay (no host assembly, no queue, no data collector thread); only rewards and done
@@ -299,7 +308,7 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     is reset on the host.  Envs that are `games.StackFrameAndAction` (directly or inside `games.PlayerIdAndActionMaskWrapper`)
     have their stacking done on the device from the newest frame (`device_stack=False`: on the host).  The actor owns the env
     objects while it runs: it may step an inner env of a wrapper, leaving the wrapper's own state stale.  `env_threads` (1 to 16)
-    host threads step the envs.  `record_format` 'frames_u8' (host-stepped envs whose uint8 image frames the device stacks, and 'Catch';
+    host threads step the envs.  `record_format` 'frames_u8' (host-stepped envs whose uint8 image frames the device stacks, 'Catch' and 'Breakout';
     the other device envs ignore it): the planner's record ring keeps one uint8 frame per move instead of the float32 observation
     (`Planner.selfplay_reset_external`); what reaches `data_queue` is the same."""
     kind, target = resolve_self_play_envs(env, int(getattr(config, 'num_envs', 1)))
@@ -310,12 +319,12 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
 
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU, 'Synthetic-Atari': pl.ENV_SYNTHETIC}
     name = target
-    if name == 'Catch':
+    if name in IMAGE_GAMES:
         pl._record_format(record_format)  # (an unknown name: before any GPU work)
     num_envs = int(getattr(config, 'num_envs', 1))
     idx = device.index if getattr(device, 'index', None) is not None else 0
     p = pl.Planner(pl.make_mz_config(network.planner_spec(), config, num_envs=num_envs, seed=int(getattr(config, 'planner_seed', 1)) + 7919 * rank,
-                                     keep_shape=name == 'Catch'), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
+                                     keep_shape=name in IMAGE_GAMES), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
     p.reload(network.state_dict())
     from muzero_amd.replay import PrioritizedReplay
 
@@ -324,6 +333,8 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
         p.attach_replay(data_queue, config, obs_shape=getattr(network, 'input_shape', None))
     if name == 'Catch':
         p.selfplay_reset_catch(int(getattr(env, 'rows', 12)), int(getattr(env, 'cols', 12)), record_format=record_format)
+    elif name == 'Breakout':
+        p.selfplay_reset_breakout(record_format=record_format, **_breakout_args(env))
     else:
         p.selfplay_reset(kinds[name])
     asm = EpisodeAssembler(config, num_envs, getattr(network, 'input_shape', None))
@@ -452,7 +463,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
 # ------------------------------------------------------------------------------------------------------------------
 # evaluation matches on the device arena (Planner.arena_*)
 # ------------------------------------------------------------------------------------------------------------------
-ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Catch')
+ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Catch', 'Breakout')
 _UNFINISHED, _WIN_CHALLENGER, _WIN_OPPONENT, _DRAW = 0, 1, 2, 3  # planner.ARENA_* (kept here so this module imports without the library)
 
 
@@ -532,12 +543,14 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
                init_state=None) -> MatchResult:
     """`num_games` evaluation games in lock-step on the GPU (Planner.arena_*), every searched move a deterministic search
     (pipeline.py:374, 468).  `opponent`: a network (two-player envs), 'random' (two-player envs), or None (one-player envs).  `env`: a
-    device-env name ('TicTacToe', 'Gomoku', 'CartPole-v1', 'Catch') or an env object with a device twin.  Two-player envs: `num_games` must be
+    device-env name ('TicTacToe', 'Gomoku', 'CartPole-v1', 'Catch', 'Breakout') or an env object with a device twin.  Two-player envs: `num_games` must be
     even -- the challenger plays black in the first half and white in the second, game i and game i + num_games / 2 share their
     `opening_plies` random opening plies (default: 2 against a network, 0 otherwise; deterministic play from one opening would repeat one
     game).  `init_state`: CartPole start states [num_games, 4].  `tag` names the match in error messages.
 
     'Catch' (or a `games.CatchEnv` / `games.make_catch_env` object, whose grid is used): game e has its ball in column e % cols, row 0.
+    'Breakout' (or a `games.BreakoutEnv` / `games.make_breakout_env` object, whose grid, brick rows and move cap are used): game e starts from
+    start code e % (2 * cols); a game's `ret` is the number of bricks it broke.
     Host-stepped envs: `env` may also be a list / tuple of env objects or a factory `i -> env` (called `num_games` times), as
     `run_self_play` takes them: each is reset once and played to its end through the host-stepped arena (`Planner.arena_external_act` /
     `_commit`), live envs stepped on the calling thread; envs that are `games.StackFrameAndAction` have their stacking done on the
@@ -546,7 +559,7 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     if isinstance(env, (list, tuple)) or (callable(env) and not hasattr(env, 'step')):  # what resolve_self_play_envs calls 'host'
         return _play_match_host(config, challenger_network, opponent, device, env, int(num_games), opening_plies, init_state, what)
     name = resolve_arena_env(env)
-    two = name not in ('CartPole-v1', 'Catch')
+    two = name not in ('CartPole-v1',) + IMAGE_GAMES
     num_games = int(num_games)
     if num_games < 1:
         raise ValueError(f'{what}: num_games must be >= 1, got {num_games}')
@@ -575,7 +588,7 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     idx = device.index if getattr(device, 'index', None) is not None else 0
     seed = int(getattr(config, 'planner_seed', 1))
     rows = int(getattr(env, 'rows', 12))
-    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729, keep_shape=name == 'Catch'), idx,
+    p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729, keep_shape=name in IMAGE_GAMES), idx,
                    tower_precision=getattr(config, 'tower_precision', 'f32'))
     q = None
     try:
@@ -585,10 +598,12 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
             q.reload(opponent.state_dict())
         if name == 'Catch':
             p.arena_reset_catch(rows, int(getattr(env, 'cols', 12)))
+        elif name == 'Breakout':
+            p.arena_reset_breakout(**_breakout_args(env))
         else:
             p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
-        # the env's own cap: CartPole's TimeLimit, a Catch ball's fall, a board's point count
-        cap = (rows - 1 if name == 'Catch' else 500) if not two else p.A - 1
+        # the env's own cap: CartPole's TimeLimit, a Catch ball's fall, Breakout's move cap, a board's point count
+        cap = (rows - 1 if name == 'Catch' else (_breakout_args(env)['max_moves'] if name == 'Breakout' else 500)) if not two else p.A - 1
         res = p.arena_result()
         played = 0
         while res['live'] > 0 and played < cap:
@@ -728,7 +743,7 @@ def run_evaluator(config, new_ckpt_network, device, env, temperature, checkpoint
     triples is returned.
 
     `device_episodes` > 0: each checkpoint plays that many episodes in lock-step on the device twin of `env` instead (`play_match`
-    with no opponent; CartPole, or Catch on the device arena), or, when `env` is a list or a factory `i -> env` of host env objects,
+    with no opponent; CartPole, or Catch and Breakout on the device arena), or, when `env` is a list or a factory `i -> env` of host env objects,
     through the host-stepped arena; the same tracker calls receive their returns and lengths."""
     from muzero_amd import mcts
 

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libmzplanner_hip.so')
 
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
-ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_CATCH = 0, 1, 2, 3, 4, 5, 6
+ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_CATCH, ENV_BREAKOUT = 0, 1, 2, 3, 4, 5, 6, 7
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
 ARENA_NONE, ARENA_RANDOM, ARENA_PLANNER = 0, 1, 2  # opponent kinds of mz_arena_reset
 SIDE_CHALLENGER, SIDE_OPPONENT, SIDE_RANDOM, SIDE_OPENING = 0, 1, 2, 3  # who chose a ply's move (arena_read_ply 'side')
@@ -26,9 +26,9 @@ ABI_SYMBOLS = [
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
     'mz_selfplay_record_info',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
-    'mz_selfplay_reset_catch',
+    'mz_selfplay_reset_catch', 'mz_selfplay_reset_breakout',
     'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
-    'mz_arena_reset_catch', 'mz_arena_reset_external', 'mz_arena_external_act', 'mz_arena_external_commit',
+    'mz_arena_reset_catch', 'mz_arena_reset_breakout', 'mz_arena_reset_external', 'mz_arena_external_act', 'mz_arena_external_commit',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
 ]
 
@@ -66,6 +66,10 @@ class MzExternalEnv(C.Structure):
 
 class MzCatchEnv(C.Structure):
     _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('record_format', C.c_int32)]
+
+
+class MzBreakoutEnv(C.Structure):
+    _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('brick_rows', C.c_int32), ('max_moves', C.c_int32), ('record_format', C.c_int32)]
 
 
 _lib = None
@@ -114,6 +118,8 @@ def load_library():
     L.mz_selfplay_external_act.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp]
     L.mz_selfplay_external_commit.argtypes = [vp, vp, vp]
     L.mz_selfplay_reset_catch.argtypes = [vp, C.POINTER(MzCatchEnv)]
+    L.mz_selfplay_reset_breakout.argtypes = [vp, C.POINTER(MzBreakoutEnv)]
+    L.mz_arena_reset_breakout.argtypes = [vp, C.POINTER(MzBreakoutEnv), vp]
     L.mz_arena_reset.argtypes = [vp, i32, i32, vp, i32, vp]
     L.mz_arena_step.argtypes = [vp, i32]
     L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
@@ -533,19 +539,41 @@ class Planner:
         d = np.ascontiguousarray(np.broadcast_to(done, (self.B,)), np.uint8)
         _chk(self.lib.mz_selfplay_external_commit(self.h, _p(r), _p(d)))
 
-    def selfplay_reset_catch(self, rows=12, cols=12, record_format='f32'):
-        """Start self-play on the device Catch env (mz_selfplay_reset_catch; `games.CatchEnv` is the same game on the host): a `rows` x
-        `cols` grid drawn on the planner's own frame (obs_c = 2 * stack_history, obs_h x obs_w pixels, cells of obs_h / rows x obs_w / cols),
-        3 actions.  `selfplay_step` then plays whole moves on the device.  `record_format` as in `selfplay_reset_external`."""
-        rfmt = _record_format(record_format)
+    def _check_image_game_replay(self):
+        """An attached frames_u8 replay must hold this planner's own frames: the kernel sizes a row from the env, so a ring built for other
+        frames would be written out of bounds."""
         cfg = self.cfg
         keep = getattr(self, '_replay_keepalive', None)
         ring = None if keep is None else keep[0]._ring
         if ring is not None and getattr(ring, 'state_format', 'f32') == 'frames_u8' and cfg.obs_c % 2 == 0 and \
                 tuple(ring.frame_spec[:4]) != (cfg.obs_c // 2, 1, cfg.obs_h, cfg.obs_w):
-            # (the kernel sizes a row from the env: a ring built for other frames would be written out of bounds)
             raise PlannerError(f'the attached replay\'s frame_spec {tuple(ring.frame_spec)} is not this env\'s (stack_history, C, H, W) = '
                                f'{(cfg.obs_c // 2, 1, cfg.obs_h, cfg.obs_w)}')
+
+    def selfplay_reset_breakout(self, rows=12, cols=12, brick_rows=3, max_moves=200, record_format='f32'):
+        """Start self-play on the device Breakout env (mz_selfplay_reset_breakout; `games.BreakoutEnv` is the same game on the host): a
+        `rows` x `cols` grid drawn on the planner's own frame as for `selfplay_reset_catch`, `brick_rows` rows of bricks, episodes of at
+        most `max_moves` moves, 3 actions, reward 1 per brick.  `selfplay_step` then plays whole moves on the device."""
+        rfmt = _record_format(record_format)
+        self._check_image_game_replay()
+        x = MzBreakoutEnv(int(rows), int(cols), int(brick_rows), int(max_moves), rfmt)
+        _chk(self.lib.mz_selfplay_reset_breakout(self.h, C.byref(x)))
+
+    def arena_reset_breakout(self, rows=12, cols=12, brick_rows=3, max_moves=200, start_codes=None):
+        """Start `num_envs` evaluation games of the device Breakout env (mz_arena_reset_breakout; geometry as `selfplay_reset_breakout`).
+        Env e starts from start code `start_codes[e]` (default e % (2 * cols): every ball column and both directions equally often).
+        `arena_step` then plays whole plies on the device; a game's return is the number of bricks it broke."""
+        sc = None if start_codes is None else np.ascontiguousarray(start_codes, np.int32).reshape(self.B)
+        x = MzBreakoutEnv(int(rows), int(cols), int(brick_rows), int(max_moves), 0)
+        _chk(self.lib.mz_arena_reset_breakout(self.h, C.byref(x), _p(sc)))
+        self._arena_opponent = None
+
+    def selfplay_reset_catch(self, rows=12, cols=12, record_format='f32'):
+        """Start self-play on the device Catch env (mz_selfplay_reset_catch; `games.CatchEnv` is the same game on the host): a `rows` x
+        `cols` grid drawn on the planner's own frame (obs_c = 2 * stack_history, obs_h x obs_w pixels, cells of obs_h / rows x obs_w / cols),
+        3 actions.  `selfplay_step` then plays whole moves on the device.  `record_format` as in `selfplay_reset_external`."""
+        rfmt = _record_format(record_format)
+        self._check_image_game_replay()
         x = MzCatchEnv(int(rows), int(cols), rfmt)
         _chk(self.lib.mz_selfplay_reset_catch(self.h, C.byref(x)))
 

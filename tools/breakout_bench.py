@@ -1,0 +1,213 @@
+#!/usr/bin/env python3
+"""Measurements of the device Breakout env (MZ_ENV_BREAKOUT); each mode writes one JSON file under profiles/breakout/ (or --out).
+
+    python tools/breakout_bench.py move      [--steps 8 --warmup 2]     # one self-play move at C4 shape, three ways, same process
+    python tools/breakout_bench.py trace                                # the env kernels' own time from a kernel trace (Breakout and Catch)
+    python tools/breakout_bench.py random    [--episodes 2000]          # the random and the ball-tracking policy on the host (no GPU)
+    python tools/breakout_bench.py learning --seeds 1 2 3 [--train-steps N ...]   # examples/train_breakout.py per seed, curves collected
+    python tools/breakout_bench.py bench --parent-tree DIR                        # bench.py beside a built checkout of the parent commit
+
+`move`: 512 envs, the C4 net (MuZeroAtariNet 8 x 96 x 96, 8 blocks, 128 planes, supports 61) with 3 actions, 50 simulations.  Device
+Breakout (float32 and compact records) and device Catch are timed with HIP events on the planner's stream (Planner.profile_*); the
+host-stepped path over 512 host BreakoutEnv objects is wall time (it synchronises every move).  `trace` runs `move --trace-child` under
+rocprofv3 --kernel-trace --stats and reads the env kernels' rows from the statistics."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, 'tests'))
+OUT_DIR = os.path.join(REPO, 'profiles', 'breakout')
+B, SIMS = 512, 50
+NET = ('c4_breakout', 'atari', (8, 96, 96), 3, 8, 128, 61, 61, 41)  # bench.py's C4 net with 3 actions
+
+
+def _planner(net):
+    from muzero_amd import planner as pl
+
+    p = pl.Planner(pl.make_mz_config(net.planner_spec(), None, num_envs=B, seed=2000, num_simulations=SIMS, discount=0.997, root_dirichlet_alpha=0.25), 0)
+    p.load_state_dict(net.state_dict())
+    return p
+
+
+def _timed(p, steps, warmup):
+    p.selfplay_step(1.0, warmup)
+    p.synchronize()
+    p.profile_begin()
+    t0 = time.perf_counter()
+    p.selfplay_step(1.0, steps)
+    p.synchronize()
+    wall = time.perf_counter() - t0
+    prof = p.profile_end()
+    return dict(ms_per_move_hip_events=prof['elapsed_ms'] / steps, ms_per_move_wall=1e3 * wall / steps,
+                search_kernel_ms_per_launch=prof['search_kernel_ms'] / max(1, prof['search_kernel_launches']), steps=steps, warmup=warmup)
+
+
+def move(args):
+    import numpy as np
+    from helpers import build_conv
+    from muzero_amd import build as mz_build
+    from muzero_amd import games
+    from muzero_amd import planner as pl
+
+    net = build_conv(NET)
+    legs = {}
+    for rec in ('f32', 'frames_u8'):
+        p = _planner(net)
+        p.selfplay_reset_breakout(12, 12, 3, 200, record_format=rec)
+        legs[f'device_breakout_{rec}'] = dict(_timed(p, args.steps, args.warmup), record_info=p.record_info(), counters={k: int(v) for k, v in p.selfplay_counters().items()})
+        p.close()
+    p = _planner(net)
+    p.selfplay_reset_catch(12, 12, record_format='frames_u8')
+    legs['device_catch_frames_u8'] = _timed(p, args.steps, args.warmup)
+    p.close()
+    if args.trace_child:
+        return None
+    for rec in ('frames_u8',):
+        p = _planner(net)
+        p.selfplay_reset_external(stack_history=4, is_obs_image=True, frame_shape=(1, 96, 96), frame_u8=True, max_episode_steps=200, record_format=rec)
+        envs = [games.BreakoutEnv(start_codes=[games.breakout_start_code(2000, e, k, 12) for k in range(args.warmup + args.steps + 1)]) for e in range(B)]
+        frames = np.stack([e.reset() for e in envs])
+        ones, rew, done = np.ones((B, 3), np.uint8), np.zeros(B, np.float32), np.zeros(B, np.uint8)
+        t_env = 0.0
+        for m in range(args.warmup + args.steps):
+            if m == args.warmup:
+                p.synchronize()
+                t0, t_env = time.perf_counter(), 0.0
+            act = p.external_act(frames, ones, 1, 1, 1.0)
+            t1 = time.perf_counter()
+            for i, e in enumerate(envs):
+                f, rew[i], d, _ = e.step(int(act[i]))
+                done[i] = 1 if d else 0
+                frames[i] = e.reset() if d else f
+            t_env += time.perf_counter() - t1
+            p.external_commit(rew, done)
+        p.synchronize()
+        wall = time.perf_counter() - t0
+        legs[f'host_stepped_breakout_{rec}'] = dict(ms_per_move_wall=1e3 * wall / args.steps, of_which_host_env_step_ms=1e3 * t_env / args.steps, steps=args.steps,
+                                                    warmup=args.warmup)
+        p.close()
+    return dict(what=f'one self-play move, {B} envs x {SIMS} simulations, MuZeroAtariNet 8x96x96 / 8 blocks / 128 planes / supports 61 / 3 actions',
+                legs=legs, _source_fingerprint=mz_build.source_fingerprint())
+
+
+def trace(args):
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', tmp, '-o', 't', '--', sys.executable, os.path.abspath(__file__), 'move',
+               '--trace-child', '--steps', str(args.steps), '--warmup', str(args.warmup)]
+        subprocess.run(cmd, check=True, cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=500)
+        stats = glob.glob(os.path.join(tmp, '**', '*kernel_stats.csv'), recursive=True)
+        rows = list(csv.DictReader(open(stats[0])))
+    moves = args.steps + args.warmup  # per planner: two Breakout planners (both record formats) and one Catch planner
+    out, total = {}, 0.0
+    for r in rows:
+        name, ns, calls = r['Name'], float(r['TotalDurationNs']), int(r['Calls'])
+        total += ns
+        for k in ('k_breakout_step', 'k_breakout_render', 'k_breakout_reset', 'k_catch_step', 'k_catch_render', 'k_ext_ingest', 'k_ext_commit', 'k_ext_record'):
+            if k in name:
+                d = out.setdefault(k, dict(calls=0, total_us=0.0))
+                d['calls'] += calls
+                d['total_us'] += ns / 1e3
+    for d in out.values():
+        d['us_per_call'] = d['total_us'] / d['calls']
+    return dict(what=f'rocprofv3 --kernel-trace --stats over 2 x {moves} device Breakout moves and {moves} device Catch moves at C4 shape ({B} envs): the env '
+                     'kernels\' own time', kernels=out, all_kernels_ms_per_move=total / 1e6 / (3 * moves), moves_per_planner=moves)
+
+
+def random_policy(args):
+    """Monte Carlo on the host: the uniformly random policy and the policy that tracks the ball, `--episodes` each, start codes uniform."""
+    import numpy as np
+    from muzero_amd import games
+
+    out = {}
+    for name in ('random', 'track_ball'):
+        rs = np.random.RandomState(12345)
+        rets, lens = [], []
+        for i in range(args.episodes):
+            env = games.BreakoutEnv(12, 12, 1, 1)
+            env.reset(start_code=int(rs.randint(24)))
+            ret, done = 0.0, False
+            while not done:
+                _, r, done, _ = env.step(int(rs.randint(3)) if name == 'random' else games.breakout_track_action(env))
+                ret += r
+            rets.append(ret)
+            lens.append(env.t)
+        rets = np.array(rets)
+        out[name] = dict(mean_return=float(rets.mean()), standard_error=float(rets.std(ddof=1) / np.sqrt(len(rets))), mean_length=float(np.mean(lens)),
+                         episodes=args.episodes)
+    return dict(what='mean undiscounted return (bricks broken) of two scripted policies on games.BreakoutEnv, 12 x 12 grid, 3 brick rows, cap 200: Monte Carlo '
+                     'on the host, start codes uniform', policies=out)
+
+
+def learning(args):
+    rnd = json.load(open(os.path.join(OUT_DIR, 'random_policy.json')))['policies']
+    runs = []
+    for seed in args.seeds:
+        with tempfile.NamedTemporaryFile(suffix='.json') as f:
+            cmd = [sys.executable, os.path.join(REPO, 'examples', 'train_breakout.py'), '--seed', str(seed), '--train-steps', str(args.train_steps), '--envs',
+                   str(args.envs), '--eval-every', str(args.eval_every), '--arena-eval', str(args.arena_eval), '--random-return',
+                   str(rnd['random']['mean_return']), '--random-se', str(rnd['random']['standard_error']), '--out', f.name] + args.extra
+            t0 = time.time()
+            subprocess.run(cmd, check=True, timeout=args.timeout)
+            doc = json.load(open(f.name))
+        runs.append(dict(seed=seed, seconds=round(time.time() - t0, 1), evals=doc['evals'], summary=doc['summary'], args={k: v for k, v in doc['args'].items() if k != 'out'}))
+        json.dump(dict(partial=True, runs=runs), open(args.out or os.path.join(OUT_DIR, 'learning.json'), 'w'), indent=1)  # (kept if a later seed is cut)
+    return dict(what='examples/train_breakout.py per seed: greedy evaluation curves on the device Breakout arena (mean bricks broken, every start code equally often)',
+                random_policy=rnd['random'], track_ball_policy=rnd['track_ball'],
+                criterion='final eval mean return exceeds the random policy\'s mean return by more than 3 standard errors (of the evaluation mean and of the '
+                          'Monte Carlo estimate, combined), on every seed',
+                learned_on_every_seed=all(r['summary']['learned'] for r in runs), runs=runs)
+
+
+def bench(args):
+    """bench.py --gpus 1 in this tree and the parent's, alternating, two runs each (tools/split_atari_learner_bench.py's bench_vs_parent), then the
+    parent's own run-to-run spread beside the difference."""
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
+    import split_atari_learner_bench as sab
+
+    out = os.path.dirname(args.out) if args.out else OUT_DIR
+    sab.bench_vs_parent(os.path.abspath(args.parent_tree), out, 2)
+    path = os.path.join(out, 'bench_vs_parent.json')
+    doc = json.load(open(path))
+    os.remove(path)
+    new, par = [doc[f'new_{i}']['value'] for i in (1, 2)], [doc[f'parent_{i}']['value'] for i in (1, 2)]
+    doc['headline'] = dict(metric=doc['new_1']['metric'], new=new, parent=par, parent_run_to_run_spread=abs(par[0] - par[1]),
+                           new_mean_minus_parent_mean=sum(new) / 2 - sum(par) / 2)
+    return doc
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('mode', choices=('move', 'trace', 'random', 'learning', 'bench'))
+    ap.add_argument('--parent-tree', default='')
+    ap.add_argument('--steps', type=int, default=8)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--trace-child', action='store_true')
+    ap.add_argument('--seeds', type=int, nargs='+', default=[1, 2, 3])
+    ap.add_argument('--train-steps', type=int, default=2000)
+    ap.add_argument('--envs', type=int, default=256)
+    ap.add_argument('--eval-every', type=int, default=500)
+    ap.add_argument('--arena-eval', type=int, default=96)
+    ap.add_argument('--episodes', type=int, default=2000)
+    ap.add_argument('--timeout', type=int, default=900)
+    ap.add_argument('--out', default='')
+    ap.add_argument('extra', nargs='*', help='after --: passed on to examples/train_breakout.py')
+    args = ap.parse_args()
+    doc = dict(move=move, trace=trace, random=random_policy, learning=learning, bench=bench)[args.mode](args)
+    if doc is None:
+        return
+    out = args.out or os.path.join(OUT_DIR, {'move': 'move_time.json', 'trace': 'env_kernels.json', 'random': 'random_policy.json', 'learning': 'learning.json', 'bench': 'bench_vs_parent.json'}[args.mode])
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    json.dump(doc, open(out, 'w'), indent=1)
+    print(json.dumps(doc))
+
+
+if __name__ == '__main__':
+    main()
