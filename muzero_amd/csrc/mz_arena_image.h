@@ -1,13 +1,12 @@
 // mz_arena_image.h -- the arena (mz_arena.h) for image and frame games: a one-player arena (ARENA_NONE: the challenger plays every move)
 // whose roots come from the host-stepped path's frame history (mz_extenv.h: ExtEnv) instead of a device board or CartPole state.  Two
 // front ends share one ply:
-//   device Catch (mz_catch.h)   : root builder, k_arena_pre, search, record + env step (k_imgarena_catch_step), k_catch_render -- nothing
-//                                 crosses PCIe and nothing waits inside mz_arena_step;
+//   device image games          : root builder, k_arena_pre, search, record + env step (mz_grid_game.h: k_game_arena_step), k_game_render
+//   (mz_catch.h, mz_breakout.h)   -- nothing crosses PCIe and nothing waits inside mz_arena_step;
 //   host-stepped (act / commit) : the same ply cut where the host steps: upload, root builder, k_arena_pre, search, k_imgarena_record |
 //                                 host env.step | upload, k_imgarena_commit.
 //
-//   k_imgarena_reset      : the arena state of k_arena_reset; for Catch also the paddle, the all-legal mask and the player ids (the
-//                           ball's column and start row are uploaded: no Philox draw)
+//   k_imgarena_reset      : the arena state of k_arena_reset (a device game's state, mask and player ids: its own k_game_reset)
 //   k_imgarena_ingest     : the root builder, a frozen-aware k_ext_ingest: StackFrameAndAction over the newest frame into
 //                           ArenaState::obs, the frame filed in the history ring.  Geometry and values are k_ext_ingest's own (ext_source,
 //                           ext_frame_value, ext_action_value).  No record ring, no temperature, no r_done: the reset flag is "first ply",
@@ -15,12 +14,11 @@
 //                           so its history, head and root stay as they were.  The only kernel here that moves real bytes (C4: 512 envs x
 //                           8 planes x 96 x 96 float32, 151 MB written per ply): one workgroup per (env, chunk), 16-byte stores.
 //   k_imgarena_record     : the "after acting" half of the ply record of every LIVE env (host-stepped arenas: the act)
-//   k_imgarena_catch_step : that record, then Catch's step without restart: paddle, ball, return, length, freeze, totals
 //   k_imgarena_commit     : host-stepped arenas: the uploaded reward and done flag of every LIVE env into return, length, freeze, totals
 // One thread per env in all but the root builder: these move a few bytes per env.
 #pragma once
 #include "mz_arena.h"
-#include "mz_catch.h"
+#include "mz_extenv.h"
 
 namespace mz {
 
@@ -29,7 +27,6 @@ constexpr int IMGARENA_CATCH = 1, IMGARENA_EXTERNAL = 2;  // which front end an 
 struct ImgArenaLaunch {
     ExtLaunch L;  // the frames' geometry and history: x, B, A, OD, first (first ply), parity (ply & 1); obs = ArenaState::obs
     ArenaState a;
-    CatchEnv c;   // Catch arenas (c.pc null otherwise)
     const int* action;   // the search's outputs
     const double* pi;
     const double* root;
@@ -42,12 +39,6 @@ __global__ void k_imgarena_reset(const ImgArenaLaunch R) {
         *R.a.n_live = R.L.B;
     }
     if (e >= R.L.B) return;
-    if (R.c.pc) {  // Catch: ball row and column are already there
-        R.c.pc[e] = R.c.cols / 2;
-        for (int k = 0; k < R.L.A; k++) R.a.mask[(size_t)e * R.L.A + k] = 1;
-        R.a.cur[e] = 1;
-        R.a.opp[e] = 1;
-    }
     R.a.live[e] = 1;
     R.a.winner[e] = WIN_UNFINISHED;
     R.a.length[e] = 0;
@@ -168,24 +159,6 @@ __global__ void k_imgarena_record(const ImgArenaLaunch R) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= R.L.B || !R.a.live[e]) return;  // a frozen env's searched output is discarded
     (void)imgarena_record(R, e);
-}
-
-// k_catch_step's rules with the finished game frozen instead of restarted: its ball and paddle stay where they were, so k_catch_render
-// (which paints every env) repeats its last frame, which the root builder no longer reads
-__global__ void k_imgarena_catch_step(const ImgArenaLaunch R) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= R.L.B || !R.a.live[e]) return;
-    const CatchEnv& c = R.c;
-    const int a = imgarena_record(R, e);
-    int pc = c.pc[e] + a - 1;
-    pc = pc < 0 ? 0 : (pc > c.cols - 1 ? c.cols - 1 : pc);
-    const int br = c.br[e] + 1;
-    const bool done = br == c.rows - 1;
-    if (!done) {
-        c.br[e] = br;
-        c.pc[e] = pc;
-    }
-    imgarena_outcome(R, e, done ? (c.bc[e] == pc ? 1.0f : -1.0f) : 0.0f, done);
 }
 
 __global__ void k_imgarena_commit(const ImgArenaLaunch R) {

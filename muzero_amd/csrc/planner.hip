@@ -10,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/mzplanner.h"
@@ -216,8 +217,7 @@ struct mz_planner {
     RecRing rr{};                  // compact record ring (MZ_RECORD_FRAMES_U8; rr.frames null: float32 records in env.r_obs)
     int rec_S = 0;                 // its stack_history
     float* d_rec_stage = nullptr;  // [B][obs] one move of decoded observations (mz_selfplay_read, allocated by the first read)
-    CatchEnv catch_env{};          // MZ_ENV_CATCH (mz_catch.h): the game's state; frames, rewards and done flags are ext's buffers
-    BreakoutEnv breakout_env{};    // MZ_ENV_BREAKOUT (mz_breakout.h): likewise
+    std::tuple<Catch, Breakout> games{};  // the device image games (mz_grid_game.h): the state of the one being played; frames, rewards and done flags are ext's buffers
 
     // arena (mz_arena.h): evaluation games in lock-step on this handle's env state
     ArenaState arena{};
@@ -1681,12 +1681,7 @@ static void ext_free(mz_planner* p) {
         if (b) (void)hipHostFree(b);
     p->ext = ExtEnv{};
     rec_free(p);
-    void* cbufs[] = {p->catch_env.br, p->catch_env.bc, p->catch_env.pc};
-    for (void* b : cbufs)
-        if (b) (void)hipFree(b);
-    p->catch_env = CatchEnv{};
-    if (p->breakout_env.s) (void)hipFree(p->breakout_env.s);
-    p->breakout_env = BreakoutEnv{};
+    std::apply([](auto&... g) { (((void)hipFree(g.s), g = {}), ...); }, p->games);  // (hipFree(nullptr) is a no-op)
     p->h_ext_frames = nullptr; p->h_ext_mask = p->h_ext_done = nullptr;
     p->h_ext_cur = p->h_ext_opp = p->h_ext_action = p->h_ext_err = nullptr;
     p->h_ext_reward = nullptr;
@@ -1932,153 +1927,126 @@ extern "C" int mz_selfplay_external_commit(mz_planner* p, const float* h_reward,
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Catch: the host-stepped path's device work around an env that lives on the device (mz_catch.h)
+// Device image games (mz_grid_game.h): the host-stepped path's device work around an env that lives on the device.  The host side is one
+// set of templates over the game type G; a game adds its geometry check (its defaults and its refusals), its reset entry points (a null
+// check, the arena's range checks of its start codes, one call) and its row in IMAGE_GAMES.
 // ---------------------------------------------------------------------------------------------------------
-static CatchLaunch catch_launch(mz_planner* p) {
-    CatchLaunch G{};
-    G.c = p->catch_env; G.B = p->cfg.num_envs; G.seed = p->cfg.seed;
-    G.action = p->d_action; G.episode = p->env.episode; G.reward = p->ext.reward; G.done = p->ext.done;
-    G.frames = static_cast<unsigned char*>(p->ext.frames); G.mask = p->d_mask; G.cur = p->d_cur; G.opp = p->d_opp;
-    return G;
+template <class G>
+static GameLaunch<G> game_launch(mz_planner* p) {
+    GameLaunch<G> L{};
+    L.g = std::get<G>(p->games); L.seed = p->cfg.seed;
+    L.action = p->d_action; L.episode = p->env.episode; L.reward = p->ext.reward; L.done = p->ext.done;
+    L.frames = static_cast<unsigned char*>(p->ext.frames); L.mask = p->d_mask; L.cur = p->d_cur; L.opp = p->d_opp;
+    return L;
 }
 
-static void catch_render(mz_planner* p, const CatchLaunch& G) {
-    const size_t runs = ((size_t)G.B * G.c.FE + 15) / 16;
-    hipLaunchKernelGGL(k_catch_render, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, G);
+static dim3 per_env(mz_planner* p) { return dim3((p->cfg.num_envs + 255) / 256); }
+
+template <class G>
+static void game_render(mz_planner* p) {
+    const GameLaunch<G> L = game_launch<G>(p);
+    const size_t runs = ((size_t)L.g.B * L.g.FE + 15) / 16;
+    hipLaunchKernelGGL(k_game_render<G>, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, L);
 }
 
-// Catch's geometry off the planner's mz_config, for the reset `fn` (self-play or arena): the grid, and the frames as an mz_external_env
-static int catch_geometry(mz_planner* p, const mz_catch_env* env, const std::string& fn, int& rows, int& cols, mz_external_env& x) {
+// What every grid game asks of the planner's mz_config, for the reset `fn` of the game `name`
+static int game_config_check(mz_planner* p, const std::string& fn, const char* name) {
     const mz_config& c = p->cfg;
-    rows = env->rows == 0 && env->cols == 0 ? 12 : env->rows;
-    cols = env->rows == 0 && env->cols == 0 ? 12 : env->cols;
-    if (c.is_board_game) return fail(MZ_E_INVALID, fn + ": is_board_game must be 0 (Catch is a one-player game)");
+    if (c.is_board_game) return fail(MZ_E_INVALID, fn + ": is_board_game must be 0 (" + name + " is a one-player game)");
     if (c.num_actions != 3) return fail(MZ_E_INVALID, fn + ": num_actions must be 3 (left, stay, right), not " + std::to_string(c.num_actions));
     if (c.obs_c < 2 || (c.obs_c & 1))
         return fail(MZ_E_INVALID, fn + ": obs_c must be 2 * stack_history (S one-channel frames and S action planes), not " + std::to_string(c.obs_c));
+    return MZ_OK;
+}
+
+// A checked rows x cols grid on the planner's frame: the game's geometry (its state array comes from game_alloc), and the frames as an
+// mz_external_env whose record ring holds an open trajectory of `longest` moves
+static void game_frames(mz_planner* p, int rows, int cols, int longest, int record_format, GridGame& g, mz_external_env& x) {
+    const mz_config& c = p->cfg;
+    g.rows = rows; g.cols = cols; g.ch = c.obs_h / rows; g.cw = c.obs_w / cols; g.H = c.obs_h; g.W = c.obs_w; g.FE = c.obs_h * c.obs_w; g.B = c.num_envs;
+    x = mz_external_env{};
+    x.stack_history = c.obs_c / 2; x.is_obs_image = 1; x.frame_c = 1; x.frame_h = c.obs_h; x.frame_w = c.obs_w; x.frame_u8 = 1;
+    x.max_episode_steps = longest;
+    x.record_format = record_format;
+}
+
+// Catch's geometry off the planner's mz_config, for the reset `fn` (self-play or arena)
+static int game_geometry(mz_planner* p, const mz_catch_env* env, const std::string& fn, Catch& g, mz_external_env& x) {
+    const mz_config& c = p->cfg;
+    const int rows = env->rows == 0 && env->cols == 0 ? 12 : env->rows, cols = env->rows == 0 && env->cols == 0 ? 12 : env->cols;
+    int rc = game_config_check(p, fn, Catch::NAME);
+    if (rc) return rc;
     if (rows < 2 || c.obs_h % rows != 0)
         return fail(MZ_E_INVALID, "mz_catch_env.rows must be >= 2 and divide obs_h = " + std::to_string(c.obs_h) + ", not " + std::to_string(rows));
     if (cols < 1 || c.obs_w % cols != 0)
         return fail(MZ_E_INVALID, "mz_catch_env.cols must be >= 1 and divide obs_w = " + std::to_string(c.obs_w) + ", not " + std::to_string(cols));
-    x = mz_external_env{};
-    x.stack_history = c.obs_c / 2; x.is_obs_image = 1; x.frame_c = 1; x.frame_h = c.obs_h; x.frame_w = c.obs_w; x.frame_u8 = 1;
-    x.max_episode_steps = rows - 1;  // (an episode's length: the record ring always holds an open trajectory)
-    x.record_format = env->record_format;
+    game_frames(p, rows, cols, rows - 1, env->record_format, g, x);  // (rows - 1: an episode's length)
     return MZ_OK;
 }
 
-// the game's state arrays (after ext_free)
-static int catch_alloc(mz_planner* p, int rows, int cols) {
+// Breakout's, with the defaults filled in
+static int game_geometry(mz_planner* p, const mz_breakout_env* env, const std::string& fn, Breakout& g, mz_external_env& x) {
     const mz_config& c = p->cfg;
-    CatchEnv& K = p->catch_env;
-    K.rows = rows; K.cols = cols; K.ch = c.obs_h / rows; K.cw = c.obs_w / cols; K.H = c.obs_h; K.W = c.obs_w; K.FE = c.obs_h * c.obs_w;
-    const size_t B = (size_t)c.num_envs;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.br), B * sizeof(int)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.bc), B * sizeof(int)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.pc), B * sizeof(int)));
+    mz_breakout_env v = *env;
+    if (v.rows == 0 && v.cols == 0) v.rows = v.cols = 12;
+    if (v.brick_rows == 0) v.brick_rows = 3;
+    if (v.max_moves == 0) v.max_moves = 200;
+    int rc = game_config_check(p, fn, Breakout::NAME);
+    if (rc) return rc;
+    if (v.brick_rows < 1 || v.brick_rows > 3) return fail(MZ_E_INVALID, "mz_breakout_env.brick_rows must be 1, 2 or 3, not " + std::to_string(v.brick_rows));
+    if (v.max_moves < 1) return fail(MZ_E_INVALID, "mz_breakout_env.max_moves must be >= 1, not " + std::to_string(v.max_moves));
+    if (v.cols > 32) return fail(MZ_E_INVALID, "mz_breakout_env.cols must be <= 32 (a brick row is one 32-bit mask), not " + std::to_string(v.cols));
+    if (v.rows < v.brick_rows + 3 || c.obs_h % v.rows != 0)
+        return fail(MZ_E_INVALID, "mz_breakout_env.rows must be >= brick_rows + 3 = " + std::to_string(v.brick_rows + 3) + " and divide obs_h = " +
+                                      std::to_string(c.obs_h) + ", not " + std::to_string(v.rows));
+    if (v.cols < 3 || c.obs_w % v.cols != 0)
+        return fail(MZ_E_INVALID, "mz_breakout_env.cols must be >= 3 and divide obs_w = " + std::to_string(c.obs_w) + ", not " + std::to_string(v.cols));
+    g.K = v.brick_rows; g.max_moves = v.max_moves;
+    game_frames(p, v.rows, v.cols, v.max_moves, v.record_format, g, x);  // (max_moves: an episode's longest)
+    return MZ_OK;
+}
+
+// the game's state array (after ext_free)
+template <class G>
+static int game_alloc(mz_planner* p, G g) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.s), (size_t)G::FIELDS * g.B * sizeof(int)));
+    std::get<G>(p->games) = g;
+    return MZ_OK;
+}
+
+template <class G, class Env>
+static int game_selfplay_reset(mz_planner* p, const Env* env, const std::string& fn) {
+    G g{};
+    mz_external_env x;
+    int rc = game_geometry(p, env, fn, g, x);
+    if (rc) return rc;
+    if (p->has_replay && p->replay.state_format == STATE_I8)
+        return fail(MZ_E_INVALID, std::string("mz_replay_ring.state_format: ") + G::NAME + " observations (" + G::OBS_VALUES +
+                                      ") are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
+    rc = ext_reset(p, &x, G::KIND, G::STRUCT);
+    if (rc) return rc;
+    rc = game_alloc(p, g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_game_reset<G>, per_env(p), dim3(256), 0, p->stream, game_launch<G>(p));
+    game_render<G>(p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
     return MZ_OK;
 }
 
 extern "C" int mz_selfplay_reset_catch(mz_planner* p, const mz_catch_env* env) {
     if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_catch");
-    const mz_config& c = p->cfg;
-    int rows, cols;
-    mz_external_env x;
-    int rc = catch_geometry(p, env, "mz_selfplay_reset_catch", rows, cols, x);
-    if (rc) return rc;
-    if (p->has_replay && p->replay.state_format == STATE_I8)
-        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: Catch observations (action planes of 1/3, 2/3) are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
-    rc = ext_reset(p, &x, MZ_ENV_CATCH, "mz_catch_env");
-    if (rc) return rc;
-    rc = catch_alloc(p, rows, cols);
-    if (rc) return rc;
-    const CatchLaunch G = catch_launch(p);
-    hipLaunchKernelGGL(k_catch_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
-    catch_render(p, G);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return MZ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Breakout (mz_breakout.h): the second device image game
-// ---------------------------------------------------------------------------------------------------------
-static BreakoutLaunch breakout_launch(mz_planner* p) {
-    BreakoutLaunch G{};
-    G.c = p->breakout_env; G.B = p->cfg.num_envs; G.seed = p->cfg.seed;
-    G.action = p->d_action; G.episode = p->env.episode; G.reward = p->ext.reward; G.done = p->ext.done;
-    G.frames = static_cast<unsigned char*>(p->ext.frames); G.mask = p->d_mask; G.cur = p->d_cur; G.opp = p->d_opp;
-    return G;
-}
-
-static void breakout_render(mz_planner* p) {
-    const BreakoutLaunch G = breakout_launch(p);
-    const size_t runs = ((size_t)G.B * G.c.FE + 15) / 16;
-    hipLaunchKernelGGL(k_breakout_render, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, p->stream, G);
-}
-
-// Breakout's geometry off the planner's mz_config, for the reset `fn`: the grid with its defaults filled in, and the frames as an
-// mz_external_env
-static int breakout_geometry(mz_planner* p, const mz_breakout_env* env, const std::string& fn, mz_breakout_env& g, mz_external_env& x) {
-    const mz_config& c = p->cfg;
-    g = *env;
-    if (g.rows == 0 && g.cols == 0) g.rows = g.cols = 12;
-    if (g.brick_rows == 0) g.brick_rows = 3;
-    if (g.max_moves == 0) g.max_moves = 200;
-    if (c.is_board_game) return fail(MZ_E_INVALID, fn + ": is_board_game must be 0 (Breakout is a one-player game)");
-    if (c.num_actions != 3) return fail(MZ_E_INVALID, fn + ": num_actions must be 3 (left, stay, right), not " + std::to_string(c.num_actions));
-    if (c.obs_c < 2 || (c.obs_c & 1))
-        return fail(MZ_E_INVALID, fn + ": obs_c must be 2 * stack_history (S one-channel frames and S action planes), not " + std::to_string(c.obs_c));
-    if (g.brick_rows < 1 || g.brick_rows > 3) return fail(MZ_E_INVALID, "mz_breakout_env.brick_rows must be 1, 2 or 3, not " + std::to_string(g.brick_rows));
-    if (g.max_moves < 1) return fail(MZ_E_INVALID, "mz_breakout_env.max_moves must be >= 1, not " + std::to_string(g.max_moves));
-    if (g.cols > 32) return fail(MZ_E_INVALID, "mz_breakout_env.cols must be <= 32 (a brick row is one 32-bit mask), not " + std::to_string(g.cols));
-    if (g.rows < g.brick_rows + 3 || c.obs_h % g.rows != 0)
-        return fail(MZ_E_INVALID, "mz_breakout_env.rows must be >= brick_rows + 3 = " + std::to_string(g.brick_rows + 3) + " and divide obs_h = " +
-                                      std::to_string(c.obs_h) + ", not " + std::to_string(g.rows));
-    if (g.cols < 3 || c.obs_w % g.cols != 0)
-        return fail(MZ_E_INVALID, "mz_breakout_env.cols must be >= 3 and divide obs_w = " + std::to_string(c.obs_w) + ", not " + std::to_string(g.cols));
-    x = mz_external_env{};
-    x.stack_history = c.obs_c / 2; x.is_obs_image = 1; x.frame_c = 1; x.frame_h = c.obs_h; x.frame_w = c.obs_w; x.frame_u8 = 1;
-    x.max_episode_steps = g.max_moves;  // (an episode's longest: the record ring always holds an open trajectory)
-    x.record_format = g.record_format;
-    return MZ_OK;
-}
-
-// the game's state array (after ext_free)
-static int breakout_alloc(mz_planner* p, const mz_breakout_env& g) {
-    const mz_config& c = p->cfg;
-    BreakoutEnv& K = p->breakout_env;
-    K.rows = g.rows; K.cols = g.cols; K.K = g.brick_rows; K.max_moves = g.max_moves;
-    K.ch = c.obs_h / g.rows; K.cw = c.obs_w / g.cols; K.H = c.obs_h; K.W = c.obs_w; K.FE = c.obs_h * c.obs_w; K.B = c.num_envs;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&K.s), (size_t)BREAKOUT_FIELDS * c.num_envs * sizeof(int)));
-    return MZ_OK;
+    return game_selfplay_reset<Catch>(p, env, "mz_selfplay_reset_catch");
 }
 
 extern "C" int mz_selfplay_reset_breakout(mz_planner* p, const mz_breakout_env* env) {
     if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_breakout");
-    const mz_config& c = p->cfg;
-    mz_breakout_env g;
-    mz_external_env x;
-    int rc = breakout_geometry(p, env, "mz_selfplay_reset_breakout", g, x);
-    if (rc) return rc;
-    if (p->has_replay && p->replay.state_format == STATE_I8)
-        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: Breakout observations (frame bytes / 255, action planes of 1/3, 2/3) are not int8 values; MZ_STATE_F32 or MZ_STATE_FRAMES_U8");
-    rc = ext_reset(p, &x, MZ_ENV_BREAKOUT, "mz_breakout_env");
-    if (rc) return rc;
-    rc = breakout_alloc(p, g);
-    if (rc) return rc;
-    const BreakoutLaunch G = breakout_launch(p);
-    hipLaunchKernelGGL(k_breakout_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, G);
-    breakout_render(p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return MZ_OK;
+    return game_selfplay_reset<Breakout>(p, env, "mz_selfplay_reset_breakout");
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // Device image games behind one table: what differs between them is the env's step (self-play: with restart; arena: with the ply record
-// and the freeze) and its renderer; their resets (own entry points: the env structs differ) share ext_reset / imgarena_reset.  A game is
-// one header and one row here.
+// and the freeze) and its renderer, all instances of mz_grid_game.h's kernels.  A game is one header and one row here.
 // ---------------------------------------------------------------------------------------------------------
 struct ImageGame {
     int env_kind;
@@ -2088,20 +2056,19 @@ struct ImageGame {
     void (*arena_step)(mz_planner*, const ImgArenaLaunch&);   // arena: ply record, step, outcome, freeze
 };
 
+template <class G>
+static constexpr ImageGame image_game_row(const char* reset_name) {
+    return {G::KIND, reset_name,
+            [](mz_planner* p) { hipLaunchKernelGGL(k_game_step<G>, per_env(p), dim3(256), 0, p->stream, game_launch<G>(p)); },
+            game_render<G>,
+            [](mz_planner* p, const ImgArenaLaunch& R) {
+                hipLaunchKernelGGL(k_game_arena_step<G>, per_env(p), dim3(256), 0, p->stream, R, std::get<G>(p->games));
+            }};
+}
+
 static const ImageGame IMAGE_GAMES[] = {
-    {MZ_ENV_CATCH, "mz_selfplay_reset_catch",
-     [](mz_planner* p) { hipLaunchKernelGGL(k_catch_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, catch_launch(p)); },
-     [](mz_planner* p) { catch_render(p, catch_launch(p)); },
-     [](mz_planner* p, const ImgArenaLaunch& R) {
-         hipLaunchKernelGGL(k_imgarena_catch_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, R);
-     }},
-    {MZ_ENV_BREAKOUT, "mz_selfplay_reset_breakout",
-     [](mz_planner* p) { hipLaunchKernelGGL(k_breakout_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, breakout_launch(p)); },
-     breakout_render,
-     [](mz_planner* p, const ImgArenaLaunch& R) {
-         BreakoutArenaLaunch Q{R, p->breakout_env};
-         hipLaunchKernelGGL(k_breakout_arena_step, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, Q);
-     }},
+    image_game_row<Catch>("mz_selfplay_reset_catch"),
+    image_game_row<Breakout>("mz_selfplay_reset_breakout"),
 };
 
 static const ImageGame* image_game(int env_kind) {
@@ -2481,7 +2448,7 @@ extern "C" int mz_arena_result(mz_planner* p, int32_t* h_winner, int32_t* h_leng
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// arena on image and frame games (mz_arena_image.h): device Catch, and envs the host steps
+// arena on image and frame games (mz_arena_image.h): the device image games, and envs the host steps
 // ---------------------------------------------------------------------------------------------------------
 static ImgArenaLaunch imgarena_launch(mz_planner* p) {
     const mz_config& c = p->cfg;
@@ -2489,7 +2456,6 @@ static ImgArenaLaunch imgarena_launch(mz_planner* p) {
     R.L.env = p->env; R.L.x = p->ext; R.L.B = c.num_envs; R.L.A = c.num_actions; R.L.OD = p->ext_od;
     R.L.first = p->arena_ply == 0; R.L.parity = p->arena_ply & 1; R.L.obs = p->arena.obs;
     R.a = p->arena;
-    R.c = p->catch_env;
     R.action = p->d_action; R.pi = p->d_pi; R.root = p->d_root;
     return R;
 }
@@ -2527,45 +2493,55 @@ static int imgarena_reset(mz_planner* p, const mz_external_env* x, int env_kind,
     return MZ_OK;
 }
 
-extern "C" int mz_arena_reset_catch(mz_planner* p, const mz_catch_env* env, const int32_t* h_ball_col, const int32_t* h_start_row) {
-    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_catch");
-    const mz_config& c = p->cfg;
-    int rows, cols;
-    mz_external_env x;
-    int rc = catch_geometry(p, env, "mz_arena_reset_catch", rows, cols, x);
+// What the device games' arena resets share: `g` and `x` are the checked geometry, `code` the validated start codes
+template <class G>
+static int game_arena_reset(mz_planner* p, const G& g, const mz_external_env& x, const std::vector<int>& code) {
+    int rc = imgarena_reset(p, &x, G::KIND, G::ARENA, G::STRUCT);
     if (rc) return rc;
-    const int B = c.num_envs;
-    std::vector<int> bc((size_t)B), br((size_t)B);
-    for (int e = 0; e < B; e++) {
-        bc[e] = h_ball_col ? h_ball_col[e] : e % cols;
-        br[e] = h_start_row ? h_start_row[e] : 0;
-        if (bc[e] < 0 || bc[e] >= cols)
-            return fail(MZ_E_INVALID, "mz_arena_reset_catch: h_ball_col[" + std::to_string(e) + "] = " + std::to_string(bc[e]) + " is outside the " + std::to_string(cols) + " columns");
-        if (br[e] < 0 || br[e] > rows - 2)
-            return fail(MZ_E_INVALID, "mz_arena_reset_catch: h_start_row[" + std::to_string(e) + "] = " + std::to_string(br[e]) + " is outside 0 .. rows - 2 = " + std::to_string(rows - 2));
+    rc = game_alloc(p, g);
+    if (rc) return rc;
+    const size_t bytes = code.size() * sizeof(int);
+    int* d_code = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_code), bytes));
+    hipError_t he = hipMemcpy(d_code, code.data(), bytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(k_imgarena_reset, per_env(p), dim3(256), 0, p->stream, imgarena_launch(p));
+        GameLaunch<G> L = game_launch<G>(p);
+        L.start = d_code; L.mask = p->arena.mask; L.cur = p->arena.cur; L.opp = p->arena.opp;
+        hipLaunchKernelGGL(k_game_reset<G>, per_env(p), dim3(256), 0, p->stream, L);
+        game_render<G>(p);
+        he = hipGetLastError();
+        if (he == hipSuccess) he = hipStreamSynchronize(p->stream);
     }
-    rc = imgarena_reset(p, &x, MZ_ENV_CATCH, IMGARENA_CATCH, "mz_catch_env");
-    if (rc) return rc;
-    rc = catch_alloc(p, rows, cols);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(p->catch_env.bc, bc.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->catch_env.br, br.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-    const ImgArenaLaunch R = imgarena_launch(p);
-    hipLaunchKernelGGL(k_imgarena_reset, dim3((B + 255) / 256), dim3(256), 0, p->stream, R);
-    catch_render(p, catch_launch(p));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));
+    (void)hipFree(d_code);
+    HIPCHK(he);
     p->arena_open = true;
     return MZ_OK;
+}
+
+extern "C" int mz_arena_reset_catch(mz_planner* p, const mz_catch_env* env, const int32_t* h_ball_col, const int32_t* h_start_row) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_catch");
+    Catch g{};
+    mz_external_env x;
+    int rc = game_geometry(p, env, "mz_arena_reset_catch", g, x);
+    if (rc) return rc;
+    std::vector<int> code((size_t)g.B);
+    for (int e = 0; e < g.B; e++) {
+        const int bc = h_ball_col ? h_ball_col[e] : e % g.cols, br = h_start_row ? h_start_row[e] : 0;
+        if (bc < 0 || bc >= g.cols)
+            return fail(MZ_E_INVALID, "mz_arena_reset_catch: h_ball_col[" + std::to_string(e) + "] = " + std::to_string(bc) + " is outside the " + std::to_string(g.cols) + " columns");
+        if (br < 0 || br > g.rows - 2)
+            return fail(MZ_E_INVALID, "mz_arena_reset_catch: h_start_row[" + std::to_string(e) + "] = " + std::to_string(br) + " is outside 0 .. rows - 2 = " + std::to_string(g.rows - 2));
+        code[e] = br * g.cols + bc;
+    }
+    return game_arena_reset(p, g, x, code);
 }
 
 extern "C" int mz_arena_reset_external(mz_planner* p, const mz_external_env* env) {
     if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_external");
     int rc = imgarena_reset(p, env, MZ_ENV_EXTERNAL, IMGARENA_EXTERNAL, "mz_external_env");
     if (rc) return rc;
-    ImgArenaLaunch R = imgarena_launch(p);
-    R.c = CatchEnv{};
-    hipLaunchKernelGGL(k_imgarena_reset, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, R);
+    hipLaunchKernelGGL(k_imgarena_reset, dim3((p->cfg.num_envs + 255) / 256), dim3(256), 0, p->stream, imgarena_launch(p));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(p->stream));
     p->arena_open = true;
@@ -2607,41 +2583,18 @@ static int image_game_plies(mz_planner* p, const ImageGame& g, int n_plies) {
 
 extern "C" int mz_arena_reset_breakout(mz_planner* p, const mz_breakout_env* env, const int32_t* h_start_code) {
     if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_breakout");
-    const mz_config& c = p->cfg;
-    mz_breakout_env g;
+    Breakout g{};
     mz_external_env x;
-    int rc = breakout_geometry(p, env, "mz_arena_reset_breakout", g, x);
+    int rc = game_geometry(p, env, "mz_arena_reset_breakout", g, x);
     if (rc) return rc;
-    const int B = c.num_envs;
-    std::vector<int> code((size_t)B);
-    for (int e = 0; e < B; e++) {
+    std::vector<int> code((size_t)g.B);
+    for (int e = 0; e < g.B; e++) {
         code[e] = h_start_code ? h_start_code[e] : e % (2 * g.cols);
         if (code[e] < 0 || code[e] >= 2 * g.cols)
             return fail(MZ_E_INVALID, "mz_arena_reset_breakout: h_start_code[" + std::to_string(e) + "] = " + std::to_string(code[e]) + " is outside 0 .. 2 * cols - 1 = " +
                                           std::to_string(2 * g.cols - 1));
     }
-    rc = imgarena_reset(p, &x, MZ_ENV_BREAKOUT, IMGARENA_BREAKOUT, "mz_breakout_env");
-    if (rc) return rc;
-    rc = breakout_alloc(p, g);
-    if (rc) return rc;
-    int* d_code = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_code), (size_t)B * sizeof(int)));
-    hipError_t he = hipMemcpy(d_code, code.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        const ImgArenaLaunch R = imgarena_launch(p);
-        // (R.c.pc is null: k_imgarena_reset writes the arena state only; mask and player ids come from k_breakout_reset)
-        hipLaunchKernelGGL(k_imgarena_reset, dim3((B + 255) / 256), dim3(256), 0, p->stream, R);
-        BreakoutLaunch G = breakout_launch(p);
-        G.start = d_code; G.mask = p->arena.mask; G.cur = p->arena.cur; G.opp = p->arena.opp;
-        hipLaunchKernelGGL(k_breakout_reset, dim3((B + 255) / 256), dim3(256), 0, p->stream, G);
-        breakout_render(p);
-        he = hipGetLastError();
-        if (he == hipSuccess) he = hipStreamSynchronize(p->stream);
-    }
-    (void)hipFree(d_code);
-    HIPCHK(he);
-    p->arena_open = true;
-    return MZ_OK;
+    return game_arena_reset(p, g, x, code);
 }
 
 extern "C" int mz_arena_external_act(mz_planner* p, const void* h_frames, const uint8_t* h_mask, const int32_t* h_cur, const int32_t* h_opp,

@@ -215,13 +215,25 @@ class EpisodeAssembler:
 
 
 DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari', 'Catch', 'Breakout')
-IMAGE_GAMES = ('Catch', 'Breakout')  # device envs drawn on the network's own frame: the planner keeps the [C, H, W] input shape
+
+
+def _catch_args(env) -> dict:
+    """The grid of a `games.CatchEnv` (or a wrapper of one) as the planner's Catch resets take it; the defaults for a name."""
+    return dict(rows=int(getattr(env, 'rows', 12)), cols=int(getattr(env, 'cols', 12)))
 
 
 def _breakout_args(env) -> dict:
     """The grid of a `games.BreakoutEnv` (or a wrapper of one) as the planner's Breakout resets take it; the defaults for a name."""
     return dict(rows=int(getattr(env, 'rows', 12)), cols=int(getattr(env, 'cols', 12)), brick_rows=int(getattr(env, 'brick_rows', 3)),
                 max_moves=int(getattr(env, 'max_moves', 200)))
+
+
+# Device envs drawn on the network's own frame (the planner keeps the [C, H, W] input shape): name -> (the reset arguments off an env object
+# or the defaults, the planner's self-play reset, its arena reset, the env's own move cap from those arguments)
+IMAGE_GAMES = {
+    'Catch': (_catch_args, 'selfplay_reset_catch', 'arena_reset_catch', lambda args: args['rows'] - 1),
+    'Breakout': (_breakout_args, 'selfplay_reset_breakout', 'arena_reset_breakout', lambda args: args['max_moves']),
+}
 
 MAX_ENV_THREADS = 16
 
@@ -331,10 +343,9 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
     on_device = isinstance(data_queue, PrioritizedReplay)
     if on_device:  # ONE device writer per replay (attach_device_writer raises on a second one): every actor rank its own shard
         p.attach_replay(data_queue, config, obs_shape=getattr(network, 'input_shape', None))
-    if name == 'Catch':
-        p.selfplay_reset_catch(int(getattr(env, 'rows', 12)), int(getattr(env, 'cols', 12)), record_format=record_format)
-    elif name == 'Breakout':
-        p.selfplay_reset_breakout(record_format=record_format, **_breakout_args(env))
+    if name in IMAGE_GAMES:
+        args, selfplay_reset, _, _ = IMAGE_GAMES[name]
+        getattr(p, selfplay_reset)(record_format=record_format, **args(env))
     else:
         p.selfplay_reset(kinds[name])
     asm = EpisodeAssembler(config, num_envs, getattr(network, 'input_shape', None))
@@ -559,7 +570,7 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     if isinstance(env, (list, tuple)) or (callable(env) and not hasattr(env, 'step')):  # what resolve_self_play_envs calls 'host'
         return _play_match_host(config, challenger_network, opponent, device, env, int(num_games), opening_plies, init_state, what)
     name = resolve_arena_env(env)
-    two = name not in ('CartPole-v1',) + IMAGE_GAMES
+    two = name != 'CartPole-v1' and name not in IMAGE_GAMES
     num_games = int(num_games)
     if num_games < 1:
         raise ValueError(f'{what}: num_games must be >= 1, got {num_games}')
@@ -587,7 +598,6 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
     kinds = {'CartPole-v1': pl.ENV_CARTPOLE, 'TicTacToe': pl.ENV_TICTACTOE, 'Gomoku': pl.ENV_GOMOKU}
     idx = device.index if getattr(device, 'index', None) is not None else 0
     seed = int(getattr(config, 'planner_seed', 1))
-    rows = int(getattr(env, 'rows', 12))
     p = pl.Planner(pl.make_mz_config(challenger_network.planner_spec(), config, num_envs=num_games, seed=seed + 104729, keep_shape=name in IMAGE_GAMES), idx,
                    tower_precision=getattr(config, 'tower_precision', 'f32'))
     q = None
@@ -596,14 +606,14 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
         if is_net:
             q = pl.Planner(pl.make_mz_config(opponent.planner_spec(), config, num_envs=num_games, seed=seed + 130003), idx, tower_precision=getattr(config, 'tower_precision', 'f32'))
             q.reload(opponent.state_dict())
-        if name == 'Catch':
-            p.arena_reset_catch(rows, int(getattr(env, 'cols', 12)))
-        elif name == 'Breakout':
-            p.arena_reset_breakout(**_breakout_args(env))
+        # the env's own cap: a Catch ball's fall, Breakout's move cap, CartPole's TimeLimit, a board's point count
+        if name in IMAGE_GAMES:
+            args, _, arena_reset, move_cap = IMAGE_GAMES[name]
+            getattr(p, arena_reset)(**args(env))
+            cap = move_cap(args(env))
         else:
             p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
-        # the env's own cap: CartPole's TimeLimit, a Catch ball's fall, Breakout's move cap, a board's point count
-        cap = (rows - 1 if name == 'Catch' else (_breakout_args(env)['max_moves'] if name == 'Breakout' else 500)) if not two else p.A - 1
+            cap = p.A - 1 if two else 500
         res = p.arena_result()
         played = 0
         while res['live'] > 0 and played < cap:

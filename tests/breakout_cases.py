@@ -127,7 +127,7 @@ class BreakoutModel:
         return 0
 
     def frames(self):
-        """uint8 [B, 1, H, W], painted as k_breakout_render paints: lane i owns bytes 16 i .. 16 i + 15 of the flat array [pad16(B * FE)]; it
+        """uint8 [B, 1, H, W], painted as k_game_render paints: lane i owns bytes 16 i .. 16 i + 15 of the flat array [pad16(B * FE)]; it
         divides once for its first byte and walks the others with counters."""
         H, W = self.rows * self.ch, self.cols * self.cw
         FE, total = H * W, self.B * H * W

@@ -12,6 +12,7 @@ STREAM = 0x70000000  # the ball column's Philox stream (mz_catch.h CATCH_STREAM)
 SHAPES = {
     'c1': (12, 12, 1, 1),     # 12 x 12 frames, cells of one pixel
     'r6c4': (6, 4, 2, 3),     # 12 x 12 frames cut 6 x 4: cell width 3 (no multiple of 4), episodes of 5 moves
+    'r5c5': (5, 5, 2, 3),     # 10 x 15 frames: 150 bytes (no multiple of 16 or of 4), so the renderer's 16-byte runs cross envs
     'wide': (12, 12, 1, 2),   # 12 x 24 frames, non-square cells
     'atari': (12, 12, 8, 8),  # 96 x 96, the Atari nets' frame
 }

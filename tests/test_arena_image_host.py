@@ -80,17 +80,21 @@ def test_pipeline_resolves_catch_and_refuses_opponents_before_any_planner():
 
 
 def test_image_arena_kernels_cross_compile_without_scratch_spills_or_lds(tmp_path):
-    """mz_arena_image.h alone, device side, for gfx950 with the library's flags: the new kernels (both forms of the root builder) are
-    there, and the compiler reports no scratch memory, no register spills and no LDS for them."""
+    """mz_arena_image.h and the two game headers on it (mz_catch.h, mz_breakout.h), device side, for gfx950 with the library's flags: the
+    arena's kernels (both forms of the root builder) and every instance of mz_grid_game.h's four kernel templates for both games are there,
+    and the compiler reports no scratch memory, no register spills and no LDS for them."""
     from muzero_amd import build
 
     hipcc = os.environ.get('HIPCC', 'hipcc')
     if shutil.which(hipcc) is None:
         pytest.fail('hipcc not found: the image arena kernels cannot be compiled')
+    games, templates = ('Catch', 'Breakout'), ('k_game_reset', 'k_game_step', 'k_game_render', 'k_game_arena_step')
     src = tmp_path / 'arena_image_tu.hip'
-    src.write_text('#include "mz_arena_image.h"\n'
+    src.write_text('#include "mz_catch.h"\n#include "mz_breakout.h"\n'
                    'template __global__ void mz::k_imgarena_ingest<4>(const mz::ImgArenaLaunch);\n'
-                   'template __global__ void mz::k_imgarena_ingest<1>(const mz::ImgArenaLaunch);\n')
+                   'template __global__ void mz::k_imgarena_ingest<1>(const mz::ImgArenaLaunch);\n' +
+                   ''.join(f'template __global__ void mz::{t}<mz::{g}>(const mz::GameLaunch<mz::{g}>);\n' for g in games for t in templates[:3]) +
+                   ''.join(f'template __global__ void mz::k_game_arena_step<mz::{g}>(const mz::ImgArenaLaunch, const mz::{g});\n' for g in games))
     flags = [f for f in build.FLAGS if f not in ('-shared', '-fPIC')]
     out = subprocess.run([hipcc] + flags + ['--cuda-device-only', '-c', '-Rpass-analysis=kernel-resource-usage', '-I', build.CSRC, str(src), '-o',
                                             str(tmp_path / 'arena_image_tu.o')], capture_output=True, text=True)
@@ -98,14 +102,18 @@ def test_image_arena_kernels_cross_compile_without_scratch_spills_or_lds(tmp_pat
     found = {}
     for b in re.split(r'remark: Function Name: ', out.stderr)[1:]:
         m = re.match(r'\S*?(k_imgarena_[a-z_]+?)(ILi(\d)EEE\S*|E\S*)\s', b)
-        if m:
-            name = m.group(1) + (f'<{m.group(3)}>' if m.group(3) else '')
+        t = re.match(r'\S*?(k_game_[a-z_]+?)INS_\d+([A-Za-z]+)EEE\S*\s', b)  # a template instance is named with its argument
+        if m or t:
+            name = m.group(1) + (f'<{m.group(3)}>' if m.group(3) else '') if m else f'{t.group(1)}<{t.group(2)}>'
             found[name] = {k: int(v) for k, v in re.findall(r'remark:\s+([A-Za-z ]+?)(?: \[bytes/\w+\])?: (\d+)', b)}
-    assert sorted(found) == ['k_imgarena_catch_step', 'k_imgarena_commit', 'k_imgarena_ingest<1>', 'k_imgarena_ingest<4>', 'k_imgarena_record',
-                             'k_imgarena_reset']
+    assert sorted(found) == sorted(['k_imgarena_commit', 'k_imgarena_ingest<1>', 'k_imgarena_ingest<4>', 'k_imgarena_record', 'k_imgarena_reset'] +
+                                   [f'{t}<{g}>' for g in games for t in templates])
     for name, use in found.items():
         assert use['ScratchSize'] == 0 and use['SGPRs Spill'] == 0 and use['VGPRs Spill'] == 0, (name, use)
         assert use['LDS Size'] == 0 and use['VGPRs'] <= 128, (name, use)
     # mz_arena.h stays a translation unit of its own: it does not pull the image arena in
     with open(os.path.join(build.CSRC, 'mz_arena.h')) as f:
         assert 'mz_arena_image.h' not in f.read()
+    # and the arena header knows no game: the game headers include it, not the other way round
+    with open(os.path.join(build.CSRC, 'mz_arena_image.h')) as f:
+        assert '#include "mz_catch.h"' not in f.read()

@@ -137,7 +137,8 @@ def ply(args):
                 _source_fingerprint=mz_build.source_fingerprint())
 
 
-KERNELS = ('k_imgarena_ingest', 'k_imgarena_catch_step', 'k_imgarena_record', 'k_imgarena_commit', 'k_imgarena_reset', 'k_arena_pre', 'k_catch_render')
+KERNELS = ('k_imgarena_ingest', 'k_game_arena_step<Catch>', 'k_imgarena_record', 'k_imgarena_commit', 'k_imgarena_reset', 'k_game_reset<Catch>', 'k_arena_pre',
+           'k_game_render<Catch>')
 
 
 def trace(args):
@@ -153,13 +154,13 @@ def trace(args):
         name, ns, calls = r['Name'], float(r['TotalDurationNs']), int(r['Calls'])
         total += ns
         for k in KERNELS:
-            if k in name:
+            if all(part in name for part in k.rstrip('>').split('<')):  # (a template instance is named with its argument: both must match)
                 d = out.setdefault(k, dict(calls=0, total_us=0.0))
                 d['calls'] += calls
                 d['total_us'] += ns / 1e3
     for d in out.values():
         d['us_per_call'] = d['total_us'] / d['calls']
-    per_ply = sum(d['total_us'] for k, d in out.items() if k != 'k_imgarena_reset') / plies
+    per_ply = sum(d['total_us'] for k, d in out.items() if k not in ('k_imgarena_reset', 'k_game_reset<Catch>')) / plies
     return dict(what=f'rocprofv3 --kernel-trace --stats over {plies} device Catch arena plies at C4 shape ({B} games): the arena kernels\' own time beside the search',
                 kernels=out, arena_kernels_us_per_ply=per_ply, all_kernels_ms_per_ply=total / 1e6 / plies, plies=plies)
 

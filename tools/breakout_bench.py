@@ -110,8 +110,9 @@ def trace(args):
     for r in rows:
         name, ns, calls = r['Name'], float(r['TotalDurationNs']), int(r['Calls'])
         total += ns
-        for k in ('k_breakout_step', 'k_breakout_render', 'k_breakout_reset', 'k_catch_step', 'k_catch_render', 'k_ext_ingest', 'k_ext_commit', 'k_ext_record'):
-            if k in name:
+        for k in ('k_game_step<Breakout>', 'k_game_render<Breakout>', 'k_game_reset<Breakout>', 'k_game_step<Catch>', 'k_game_render<Catch>', 'k_ext_ingest', 'k_ext_commit',
+                  'k_ext_record'):
+            if all(part in name for part in k.rstrip('>').split('<')):  # (a template instance is named with its argument: both must match)
                 d = out.setdefault(k, dict(calls=0, total_us=0.0))
                 d['calls'] += calls
                 d['total_us'] += ns / 1e3
