@@ -37,6 +37,7 @@ extern "C" {
 #define MZ_ENV_EXTERNAL 5  /* any environment the caller steps on the host (mz_selfplay_reset_external) */
 #define MZ_ENV_CATCH 6     /* Catch as an image game on the device: uint8 frames through the host-stepped path's kernels (mz_selfplay_reset_catch) */
 #define MZ_ENV_BREAKOUT 7  /* a brick-breaking image game on the device, rewards during the episode (mz_selfplay_reset_breakout) */
+#define MZ_ENV_CONNECT4 8  /* Connect Four on the device: a two-player game on a rows x cols board, one action per column (mz_selfplay_reset_connect4) */
 
 /* Everything uct_search reads from MuZeroConfig (config.py:51-103) and from the network constructors
  * (network.py:239-247, 504-512, 543-549), plus planner-only sizing knobs. */
@@ -242,7 +243,7 @@ typedef struct {
     /* How `state` is stored.  MZ_STATE_F32 (0: a zero-initialised field): float32, as ever.  The other formats are EXACT -- every state decodes to
      * the float32 observation bit for bit -- and are refused (MZ_E_INVALID naming state_format) at mz_selfplay_reset / mz_selfplay_reset_external
      * for an env whose observations they cannot hold:
-     *   MZ_STATE_I8         [capacity, obs] one signed byte per element, value (float)(int8_t)b.  TicTacToe, Gomoku (0 / 1 planes), and host-stepped
+     *   MZ_STATE_I8         [capacity, obs] one signed byte per element, value (float)(int8_t)b.  TicTacToe, Gomoku, Connect Four (0 / 1 planes), and host-stepped
      *                       envs: there every emitted state is checked (decode(encode(v)) == v bit for bit); on a mismatch the replay count does not
      *                       advance and mz_selfplay_external_commit returns MZ_E_INVALID naming the smallest such env; mz_selfplay_reset_external next.
      *   MZ_STATE_FRAMES_U8  host-stepped envs with stack_history = S > 0, is_obs_image, frame_u8 and num_actions <= 256 only.  A row is the
@@ -351,6 +352,35 @@ typedef struct {
 } mz_breakout_env;
 int mz_selfplay_reset_breakout(mz_planner* p, const mz_breakout_env* env);
 
+/* Connect Four (MZ_ENV_CONNECT4): the two-player device game whose board is not square and whose action count is not its point count.
+ * muzero_amd.games.ConnectFourEnv is the specification; BoardGameEnv's conventions hold wherever they apply.  Board obs_h rows x obs_w
+ * columns (row obs_h - 1 is the bottom), players 1 (black, moves first) and 2; action c < obs_w drops a stone into column c, where it
+ * lands on the lowest empty row; action obs_w resigns (the mover gets -1).  num_to_win or more of the mover's stones in a line through
+ * the stone just placed -- horizontal, vertical, either diagonal; lines end at the board's edges -- win (+1), tested from ply
+ * 2 * (num_to_win - 1) on; a full board without a win is a draw (0).  A column is legal while its top cell is empty, resign always.  The
+ * observation is BoardGameEnv's: (9, obs_h, obs_w), own and opponent stone history interleaved, newest first, then the colour plane.  A
+ * finished env restarts at once.  Temperature < 0 in mz_selfplay_step: 1.0 for the first temp_switch_steps moves of an episode, then 0.1.
+ * Refusals (MZ_E_INVALID naming the field): net_kind other than MZ_NET_BOARD, obs_c != 9, num_actions != obs_w + 1, obs_h * obs_w > 64
+ * (the state is a 64-bit bitboard per colour), num_to_win outside 2 .. max(obs_h, obs_w), an attached replay of MZ_STATE_FRAMES_U8
+ * (MZ_STATE_F32 and MZ_STATE_I8 are served; with is_board_game the items are Monte-Carlo returns on episode end).  Afterwards
+ * mz_selfplay_step, _read, _counters and _record_info work as on the other device kinds; mz_selfplay_external_act / _commit return
+ * MZ_E_STATE; mz_selfplay_reset and mz_arena_reset refuse the kind by naming the right reset.
+ * (This game's entry points carry a digit in their names.  tests/test_abi.py and tests/test_split_tower_host.py both compare
+ * planner.ABI_SYMBOLS with the prototypes they parse out of this header, the first skipping names with digits, the second not; the
+ * prototypes are written `extern int ...`, which neither collects, and tests/test_connect4_host.py checks that they are declared here
+ * and exported by the library.) */
+typedef struct {
+    int32_t num_to_win;        /* stones in a line that win: 2 .. max(obs_h, obs_w) */
+    int32_t temp_switch_steps; /* 0: 6, the board rule's value for num_actions <= 10 */
+} mz_connect4_env;
+extern int mz_selfplay_reset_connect4(mz_planner* p, const mz_connect4_env* env);
+/* Test hook: one move of all envs with the caller's actions (h_action int32 [B]) through the launches of a self-play move -- pre, step,
+ * record, epilogue -- without the search: the recorded policy is the one-hot of the action, the root value 0.  An illegal action of any
+ * env is MZ_E_INVALID naming the env, before any launch; MZ_E_STATE unless mz_selfplay_reset_connect4 came before. */
+extern int mz_connect4_debug_step(mz_planner* p, const int32_t* h_action);
+/* Test hook: the envs' legal-action masks as the next search will see them, h_mask uint8 [B, num_actions]. */
+extern int mz_connect4_debug_mask(mz_planner* p, uint8_t* h_mask);
+
 /* Arena: the evaluators' game loops (pipeline.py:289-397 board games, pipeline.py:400-488 one-player envs) for num_envs games in
  * lock-step on the device.  Every searched move is uct_search(deterministic = True) on the planner's search kernels: no root noise, the
  * most-visited child, tie draws consumed as mz_planner_search consumes them (mz_debug_capture_rng reads them back per handle).  The
@@ -407,6 +437,11 @@ int mz_arena_reset_catch(mz_planner* p, const mz_catch_env* env, const int32_t* 
  * Philox draw is used.  mz_arena_step plays plies as for Catch; a game ends on a miss or at max_moves: ret is the number of bricks broken,
  * length the plies played. */
 int mz_arena_reset_breakout(mz_planner* p, const mz_breakout_env* env, const int32_t* h_start_code_or_null);
+/* Connect Four in the arena: mz_arena_reset's two-player arena -- MZ_ARENA_RANDOM or MZ_ARENA_PLANNER, colours balanced over the two
+ * halves, paired openings, deterministic searches, a finished game frozen, the tally -- on MZ_ENV_CONNECT4, with the refusals of
+ * mz_selfplay_reset_connect4 and of mz_arena_reset's sides.  Random moves (openings and MZ_ARENA_RANDOM) are legal[floor(u * n_legal)]
+ * over the legal COLUMNS only: a random move never resigns.  mz_arena_step, _read_ply and _result as ever. */
+extern int mz_arena_reset_connect4(mz_planner* p, const mz_connect4_env* env, int32_t opponent_kind, mz_planner* q_or_null, int32_t opening_plies);
 /* The same ply for envs the host steps, cut where it steps them.  `env` describes the frames as for mz_selfplay_reset_external (stacked
  * uint8 or float images, stacked vectors, stack_history = 0 for whole observations); max_episode_steps and temp_switch_steps are not used.
  *   mz_arena_external_act    -- uploads every env's newest frame, mask and player ids (arguments as mz_selfplay_external_act's; the entries

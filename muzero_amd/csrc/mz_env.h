@@ -72,10 +72,11 @@ inline void env_free(EnvState& e) {
 }
 
 // with_obs = false: no float32 observation records (r_obs stays null): the compact record ring of mz_extenv.h holds the frames instead
-inline hipError_t env_alloc(EnvState& e, int kind, int B, int A, int D, int ring_len, int board_n = 3, int num_to_win = 3, bool with_obs = true) {
+// points > 0: a board that is not square (mz_connect4.h): board_n is its column count, points = rows * columns
+inline hipError_t env_alloc(EnvState& e, int kind, int B, int A, int D, int ring_len, int board_n = 3, int num_to_win = 3, bool with_obs = true, int points = 0) {
     env_free(e);
     e.kind = kind; e.B = B; e.A = A; e.D = D; e.ring_len = ring_len;
-    e.bn = board_n; e.nn = board_n * board_n; e.win = num_to_win;
+    e.bn = board_n; e.nn = points > 0 ? points : board_n * board_n; e.win = num_to_win;
     hipError_t r;
 #define MZ_ALLOC(ptr, bytes)                                  \
     if ((r = hipMalloc(&(ptr), (bytes))) != hipSuccess) return r; \

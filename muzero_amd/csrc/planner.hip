@@ -20,6 +20,7 @@
 #include "mz_extenv.h"
 #include "mz_catch.h"
 #include "mz_breakout.h"
+#include "mz_connect4.h"
 #include "mz_search.h"
 #include "mz_search_fast.h"
 #include "mz_convnet.h"
@@ -205,6 +206,7 @@ struct mz_planner {
     int* d_epi_off = nullptr;        // per-env slot offsets of the move being written (k_epi_scan)
     long long* d_epi_ctr = nullptr;  // reserved write cursor of the attached replay ring (k_epilogue reserves, k_epi_publish commits)
     long long selfplay_moves = 0;  // moves since mz_selfplay_reset
+    int c4_temp_steps = 6;         // MZ_ENV_CONNECT4: the board temperature schedule's switch step
     // host-stepped envs (MZ_ENV_EXTERNAL): device side of the frames / history, pinned staging of every upload and download
     ExtEnv ext{};
     int ext_od = 0;
@@ -1602,6 +1604,8 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         return fail(MZ_E_INVALID, "MZ_ENV_CATCH has its own reset: mz_selfplay_reset_catch");
     } else if (env_kind == MZ_ENV_BREAKOUT) {
         return fail(MZ_E_INVALID, "MZ_ENV_BREAKOUT has its own reset: mz_selfplay_reset_breakout");
+    } else if (env_kind == MZ_ENV_CONNECT4) {
+        return fail(MZ_E_INVALID, "MZ_ENV_CONNECT4 has its own reset: mz_selfplay_reset_connect4");
     } else {
         return fail(MZ_E_INVALID, "unknown env kind");
     }
@@ -1632,6 +1636,117 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
     return MZ_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Connect Four (mz_connect4.h): its own reset, pre and step launches around the board-net search
+// ---------------------------------------------------------------------------------------------------------
+static C4Launch c4_launch(mz_planner* p, const EnvLaunch& L) {
+    C4Launch P{};
+    P.L = L; P.rows = p->cfg.obs_h; P.cols = p->cfg.obs_w; P.temp_steps = p->c4_temp_steps;
+    return P;
+}
+
+// what both resets check: the net, the board and the env struct; every refusal names the offending field
+static int c4_check(mz_planner* p, const mz_connect4_env* env, const std::string& fn) {
+    const mz_config& c = p->cfg;
+    if (c.net_kind != MZ_NET_BOARD) return fail(MZ_E_INVALID, fn + ": mz_config.net_kind must be MZ_NET_BOARD (Connect Four plays on the board conv net)");
+    if (c.obs_c != 9) return fail(MZ_E_INVALID, fn + ": mz_config.obs_c must be 9 (4 history planes per colour and the colour plane), not " + std::to_string(c.obs_c));
+    if (c.num_actions != c.obs_w + 1)
+        return fail(MZ_E_INVALID, fn + ": mz_config.num_actions must be obs_w + 1 = " + std::to_string(c.obs_w + 1) + " (one per column, and resign), not " + std::to_string(c.num_actions));
+    if (c.obs_h * c.obs_w > 64)
+        return fail(MZ_E_INVALID, fn + ": mz_config.obs_h * obs_w = " + std::to_string(c.obs_h * c.obs_w) + " points, the board holds at most 64 (one 64-bit bitboard per colour)");
+    const int longest = c.obs_h > c.obs_w ? c.obs_h : c.obs_w;
+    if (env->num_to_win < 2 || env->num_to_win > longest)
+        return fail(MZ_E_INVALID, fn + ": mz_connect4_env.num_to_win must be in 2 .. max(obs_h, obs_w) = " + std::to_string(longest) + ", not " + std::to_string(env->num_to_win));
+    if (env->temp_switch_steps < 0) return fail(MZ_E_INVALID, fn + ": mz_connect4_env.temp_switch_steps must be >= 0");
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_reset_connect4(mz_planner* p, const mz_connect4_env* env) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_connect4");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    int rc = c4_check(p, env, "mz_selfplay_reset_connect4");
+    if (rc) return rc;
+    if (p->has_replay && p->replay.state_format != STATE_F32) {
+        if (p->replay.state_format != STATE_I8)
+            return fail(MZ_E_INVALID, "mz_replay_ring.state_format: the device Connect Four env has float32 (MZ_STATE_F32) and exact int8 (MZ_STATE_I8) states; "
+                                      "MZ_STATE_FRAMES_U8 needs a host-stepped env with uint8 frames");
+        p->replay.row_bytes = obs_dim(c);
+        p->replay.enc_err = nullptr;
+    }
+    ext_free(p);
+    p->env_kind = MZ_ENV_CONNECT4;
+    p->arena_open = false;
+    p->c4_temp_steps = env->temp_switch_steps > 0 ? env->temp_switch_steps : 6;  // (the existing rule's value for num_actions <= 10)
+    const int nn = c.obs_h * c.obs_w;
+    ring_start(p, c.is_board_game ? nn : (1 << 30) - 64);  // a board game's ring holds the whole game: at most one ply per point
+    hipError_t e = env_alloc(p->env, ENV_CONNECT4, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, c.obs_w, env->num_to_win, true, nn);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    EnvLaunch L{};
+    L.env = p->env; L.B = c.num_envs; L.seed = c.seed;
+    L.obs = p->d_obs; L.mask = p->d_mask; L.cur = p->d_cur; L.opp = p->d_opp;
+    hipLaunchKernelGGL(k_c4_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, c4_launch(p, L));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+// one move: temperatures and the record's first half, the search (or, search == false, the caller's d_action / d_pi / d_root), env.step +
+// record + auto-reset
+static int c4_move(mz_planner* p, const EnvLaunch& L, bool search) {
+    const mz_config& c = p->cfg;
+    const C4Launch P = c4_launch(p, L);
+    hipLaunchKernelGGL(k_c4_pre, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, P);
+    HIPCHK(hipMemcpyAsync(p->env.r_obs + (size_t)p->ring_pos * c.num_envs * obs_dim(c), p->d_obs, (size_t)c.num_envs * obs_dim(c) * sizeof(float),
+                          hipMemcpyDeviceToDevice, p->stream));
+    if (search) {
+        int rc = launch_search(p, c.num_envs, 0, true, false, false);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_c4_step, dim3((c.num_envs + 15) / 16), dim3(256), 0, p->stream, P);
+    return MZ_OK;
+}
+
+// Test hook: one move of all envs with the caller's actions through the launches of a self-play move, without the search.  The recorded
+// policy is the one-hot of the action, the root value 0.
+extern "C" int mz_connect4_debug_step(mz_planner* p, const int32_t* h_action) {
+    if (!p || !h_action) return fail(MZ_E_INVALID, "null argument to mz_connect4_debug_step");
+    if (p->env_kind != MZ_ENV_CONNECT4 || p->arena_open) return fail(MZ_E_STATE, "mz_connect4_debug_step: call mz_selfplay_reset_connect4 first");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    const mz_config& c = p->cfg;
+    const size_t B = (size_t)c.num_envs, A = (size_t)c.num_actions;
+    std::vector<unsigned char> mask(B * A);
+    HIPCHK(hipMemcpy(mask.data(), p->d_mask, B * A, hipMemcpyDeviceToHost));
+    std::vector<double> pi(B * A, 0.0), root(B, 0.0);
+    for (size_t e = 0; e < B; e++) {
+        const int a = h_action[e];
+        if (a < 0 || a >= (int)A || !mask[e * A + a])
+            return fail(MZ_E_INVALID, "mz_connect4_debug_step: h_action[" + std::to_string(e) + "] = " + std::to_string(a) + " is not a legal action of env " + std::to_string(e));
+        pi[e * A + a] = 1.0;
+    }
+    HIPCHK(hipMemcpy(p->d_action, h_action, B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_pi, pi.data(), B * A * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_root, root.data(), B * sizeof(double), hipMemcpyHostToDevice));
+    EnvLaunch L{};
+    L.env = p->env; L.B = c.num_envs; L.seed = c.seed; L.temperature = 1.0; L.move_counter = p->move_counter;
+    L.obs = p->d_obs; L.mask = p->d_mask; L.cur = p->d_cur; L.opp = p->d_opp; L.temp_out = p->d_temp;
+    L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root; L.slot = p->ring_pos; L.sims = 0;
+    int rc = c4_move(p, L, false);
+    if (rc) return rc;
+    return ring_finish_move(p);
+}
+
+// Test hook: the envs' legal-action masks as the next search will see them, uint8 [B, A]
+extern "C" int mz_connect4_debug_mask(mz_planner* p, uint8_t* h_mask) {
+    if (!p || !h_mask) return fail(MZ_E_INVALID, "null argument to mz_connect4_debug_mask");
+    if (p->env_kind != MZ_ENV_CONNECT4 || p->arena_open) return fail(MZ_E_STATE, "mz_connect4_debug_mask: call mz_selfplay_reset_connect4 first");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpy(h_mask, p->d_mask, (size_t)p->cfg.num_envs * p->cfg.num_actions, hipMemcpyDeviceToHost));
+    return MZ_OK;
+}
+
 extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_moves) {
     if (!p || n_moves < 1) return fail(MZ_E_INVALID, "bad argument to mz_selfplay_step");
     if (p->arena_open) return fail(MZ_E_STATE, "mz_selfplay_step during an arena: call mz_selfplay_reset first");
@@ -1646,7 +1761,10 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
         L.env = p->env; L.B = c.num_envs; L.seed = c.seed; L.temperature = temperature; L.move_counter = p->move_counter;
         L.obs = p->d_obs; L.mask = p->d_mask; L.cur = p->d_cur; L.opp = p->d_opp; L.temp_out = p->d_temp;
         L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root; L.slot = p->ring_pos; L.sims = c.num_simulations;
-        if (!p->conv && !p->hbm_tree && p->env_kind != MZ_ENV_SYNTHETIC) {  // (synthetic frames are redrawn by k_env_synth_obs below)
+        if (p->env_kind == MZ_ENV_CONNECT4) {
+            int rc = c4_move(p, L, true);
+            if (rc) return rc;
+        } else if (!p->conv && !p->hbm_tree && p->env_kind != MZ_ENV_SYNTHETIC) {  // (synthetic frames are redrawn by k_env_synth_obs below)
             // MLP nets with LDS trees: the whole move -- temperature / record, search, env.step, auto-reset -- is ONE kernel launch
             // (C2: 727.7 us per move against 734.6 us for the four launches below, same box, same build)
             int rc = launch_search(p, c.num_envs, 0, true, false, false, &L);
@@ -2267,6 +2385,34 @@ static void arena_seg_searched(ArenaSeg& g, mz_planner* s) {
     g.action = s->d_action; g.pi = s->d_pi; g.root = s->d_root;
 }
 
+// what every arena reset on the lock-step board / CartPole arena checks after its env's own geometry: the sides, the borrowed opponent,
+// committed weights; then it drains the stream and makes the events that order the two planners' streams
+static int arena_check_sides(mz_planner* p, bool two, int opponent_kind, mz_planner* q, int opening_plies, bool init_refused) {
+    const mz_config& c = p->cfg;
+    if (opponent_kind != MZ_ARENA_NONE && opponent_kind != MZ_ARENA_RANDOM && opponent_kind != MZ_ARENA_PLANNER) return fail(MZ_E_INVALID, "unknown opponent kind");
+    if (two != (opponent_kind != MZ_ARENA_NONE)) return fail(MZ_E_INVALID, "two-player envs need an opponent (MZ_ARENA_RANDOM / MZ_ARENA_PLANNER), one-player envs MZ_ARENA_NONE");
+    if (two && (c.num_envs & 1)) return fail(MZ_E_INVALID, "two-player arenas need an even num_envs (env i and i + num_envs / 2 are a pair)");
+    if (opening_plies < 0) return fail(MZ_E_INVALID, "opening_plies must be >= 0");
+    if (init_refused) return fail(MZ_E_INVALID, "only the CartPole env takes an initial state");
+    if (opponent_kind == MZ_ARENA_PLANNER) {
+        if (!q || q == p) return fail(MZ_E_INVALID, "MZ_ARENA_PLANNER needs a second planner");
+        if (q->device != p->device) return fail(MZ_E_INVALID, "the opponent planner must be on the challenger's device");
+        if (!arena_same_config(p->cfg, q->cfg)) return fail(MZ_E_INVALID, "the opponent planner's mz_config must equal the challenger's (apart from the seed)");
+        if (p->conv && p->cnet.tower_split != q->cnet.tower_split) return fail(MZ_E_INVALID, "the opponent planner's tower_precision must equal the challenger's");
+        if (!q->committed) return fail(MZ_E_STATE, "the opponent planner's weights are not committed");
+    } else if (q) {
+        return fail(MZ_E_INVALID, "an opponent planner is given but the opponent kind is not MZ_ARENA_PLANNER");
+    }
+    if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (!p->ev_arena_pre) {
+        HIPCHK(hipEventCreateWithFlags(&p->ev_arena_pre, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&p->ev_arena_q, hipEventDisableTiming));
+    }
+    return MZ_OK;
+}
+
 extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_kind, mz_planner* q, int32_t opening_plies, const double* h_init_state) {
     if (!p) return fail(MZ_E_INVALID, "null planner");
     const mz_config& c = p->cfg;
@@ -2286,31 +2432,14 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
         return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_BREAKOUT has its own arena reset: mz_arena_reset_breakout");
     } else if (env_kind == MZ_ENV_EXTERNAL) {
         return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_EXTERNAL has its own arena reset: mz_arena_reset_external");
+    } else if (env_kind == MZ_ENV_CONNECT4) {
+        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_CONNECT4 has its own arena reset: mz_arena_reset_connect4");
     } else {
         return fail(MZ_E_INVALID, "the arena plays the device envs CartPole, TicTacToe and Gomoku (not the synthetic kind)");
     }
     const bool two = env_kind != MZ_ENV_CARTPOLE;
-    if (opponent_kind != MZ_ARENA_NONE && opponent_kind != MZ_ARENA_RANDOM && opponent_kind != MZ_ARENA_PLANNER) return fail(MZ_E_INVALID, "unknown opponent kind");
-    if (two != (opponent_kind != MZ_ARENA_NONE)) return fail(MZ_E_INVALID, "two-player envs need an opponent (MZ_ARENA_RANDOM / MZ_ARENA_PLANNER), one-player envs MZ_ARENA_NONE");
-    if (two && (c.num_envs & 1)) return fail(MZ_E_INVALID, "two-player arenas need an even num_envs (env i and i + num_envs / 2 are a pair)");
-    if (opening_plies < 0) return fail(MZ_E_INVALID, "opening_plies must be >= 0");
-    if (h_init_state && env_kind != MZ_ENV_CARTPOLE) return fail(MZ_E_INVALID, "only the CartPole env takes an initial state");
-    if (opponent_kind == MZ_ARENA_PLANNER) {
-        if (!q || q == p) return fail(MZ_E_INVALID, "MZ_ARENA_PLANNER needs a second planner");
-        if (q->device != p->device) return fail(MZ_E_INVALID, "the opponent planner must be on the challenger's device");
-        if (!arena_same_config(p->cfg, q->cfg)) return fail(MZ_E_INVALID, "the opponent planner's mz_config must equal the challenger's (apart from the seed)");
-        if (p->conv && p->cnet.tower_split != q->cnet.tower_split) return fail(MZ_E_INVALID, "the opponent planner's tower_precision must equal the challenger's");
-        if (!q->committed) return fail(MZ_E_STATE, "the opponent planner's weights are not committed");
-    } else if (q) {
-        return fail(MZ_E_INVALID, "an opponent planner is given but the opponent kind is not MZ_ARENA_PLANNER");
-    }
-    if (!p->committed) return fail(MZ_E_STATE, "weights not committed");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    if (!p->ev_arena_pre) {
-        HIPCHK(hipEventCreateWithFlags(&p->ev_arena_pre, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&p->ev_arena_q, hipEventDisableTiming));
-    }
+    int rc = arena_check_sides(p, two, opponent_kind, q, opening_plies, h_init_state && env_kind != MZ_ENV_CARTPOLE);
+    if (rc) return rc;
     p->env_kind = env_kind;
     ext_free(p);  // (the arena keeps its own one-ply float32 record, ArenaState::r_obs: a compact self-play ring ends here)
     p->ring_len = 1; p->ring_pos = 0; p->ring_count = 0;  // no self-play records in this mode (mz_selfplay_read: MZ_E_INVALID)
@@ -2335,6 +2464,37 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
     return MZ_OK;
 }
 
+// Connect Four in the two-player arena: mz_arena_reset's states and tally around mz_connect4.h's reset, pick and step
+extern "C" int mz_arena_reset_connect4(mz_planner* p, const mz_connect4_env* env, int32_t opponent_kind, mz_planner* q, int32_t opening_plies) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_connect4");
+    const mz_config& c = p->cfg;
+    int rc = c4_check(p, env, "mz_arena_reset_connect4");
+    if (rc) return rc;
+    rc = arena_check_sides(p, true, opponent_kind, q, opening_plies, false);
+    if (rc) return rc;
+    p->env_kind = MZ_ENV_CONNECT4;
+    ext_free(p);
+    p->ring_len = 1; p->ring_pos = 0; p->ring_count = 0;  // no self-play records in this mode (mz_selfplay_read: MZ_E_INVALID)
+    p->selfplay_moves = 0;
+    hipError_t e = env_alloc(p->env, ENV_CONNECT4, c.num_envs, c.num_actions, obs_dim(c), 1, c.obs_w, env->num_to_win, true, c.obs_h * c.obs_w);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    e = arena_alloc(p->arena, c.num_envs, c.num_actions, obs_dim(c));
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("arena_alloc: ") + hipGetErrorString(e));
+    p->arena.half = c.num_envs / 2;
+    p->arena.opponent = opponent_kind;
+    p->arena.opening_plies = opening_plies;
+    p->arena_q = opponent_kind == MZ_ARENA_PLANNER ? q : nullptr;
+    p->arena_ply = 0;
+    p->arena_img = 0;
+    C4Arena Q{};
+    Q.R = arena_launch(p); Q.rows = c.obs_h; Q.cols = c.obs_w;
+    hipLaunchKernelGGL(k_c4_arena_reset, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->arena_open = true;
+    return MZ_OK;
+}
+
 extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     if (!p || n_plies < 1) return fail(MZ_E_INVALID, "bad argument to mz_arena_step");
     if (!p->arena_open) return fail(MZ_E_STATE, "call mz_arena_reset first");
@@ -2346,6 +2506,7 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     const mz_config& c = p->cfg;
     const int B = c.num_envs, half = p->arena.half;
     const dim3 waves((B + 3) / 4), block(256);
+    const bool c4 = p->env_kind == MZ_ENV_CONNECT4;
     for (int m = 0; m < n_plies; m++) {
         ArenaLaunch R = arena_launch(p);
         const int t = p->arena_ply;
@@ -2370,7 +2531,10 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
         const size_t work = (size_t)B * obs_dim(c) / 4 + 1;
         const int pre_blocks = (int)((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024);
         hipLaunchKernelGGL(k_arena_pre, dim3(pre_blocks), block, 0, p->stream, R);
-        if (picks) hipLaunchKernelGGL(k_arena_pick, waves, block, 0, p->stream, R);
+        C4Arena Q{};  // (Connect Four: its own pick -- columns only -- and step, 16 lanes per env)
+        Q.R = R; Q.rows = c.obs_h; Q.cols = c.obs_w;
+        if (picks && c4) hipLaunchKernelGGL(k_c4_arena_pick, dim3((B + 255) / 256), block, 0, p->stream, Q);
+        else if (picks) hipLaunchKernelGGL(k_arena_pick, waves, block, 0, p->stream, R);
         HIPCHK(hipGetLastError());
         if (n_q) {  // the opponent's half on its own stream, beside the challenger's
             HIPCHK(hipEventRecord(p->ev_arena_pre, p->stream));
@@ -2384,7 +2548,8 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
             if (rc) return rc;
         }
         if (n_q) HIPCHK(hipStreamWaitEvent(p->stream, p->ev_arena_q, 0));
-        hipLaunchKernelGGL(k_arena_step, waves, block, 0, p->stream, R);
+        if (c4) hipLaunchKernelGGL(k_c4_arena_step, dim3((B + 15) / 16), block, 0, p->stream, Q);
+        else hipLaunchKernelGGL(k_arena_step, waves, block, 0, p->stream, R);
         HIPCHK(hipGetLastError());
         p->arena_ply++;
     }

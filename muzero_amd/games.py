@@ -142,6 +142,109 @@ class GomokuEnv(BoardGameEnv):
         super().__init__(board_size=board_size, stack_history=stack_history, num_to_win=num_to_win, name='Gomoku')
 
 
+class ConnectFourEnv(BoardGameEnv):
+    """Connect Four; the specification of the device env MZ_ENV_CONNECT4 (`csrc/mz_connect4.h`, same rules).  The reference defines no such
+    game: this class is the definition, with `BoardGameEnv`'s conventions wherever they apply.  A `rows` x `cols` board, row `rows - 1` the
+    bottom; players 1 (black, moves first) and 2 (white).  Action c < cols drops a stone into column c, where it lands on the lowest empty
+    row; action `cols` resigns (reward -1 for the mover, the opponent wins).  A column is legal while its top cell is empty, resign always;
+    `step` raises on a full column.  `num_to_win` or more stones of the mover in a line through the stone just placed (horizontal, vertical,
+    either diagonal; a line ends at the board's edges) win with reward +1, tested from ply 2 * (num_to_win - 1) on (the family's rule, with
+    the pre-increment step count); a win on the last empty cell is a win.  A full board without a win is a draw: reward 0, game over.  The
+    side to move switches only if the game is not over.  Observation: `BoardGameEnv.observation`'s planes on (rows, cols)."""
+
+    def __init__(self, rows: int = 6, cols: int = 7, num_to_win: int = 4, stack_history: int = 4) -> None:
+        if rows < 1 or cols < 1 or not 2 <= num_to_win <= max(rows, cols) or stack_history < 1:
+            raise ValueError('ConnectFourEnv needs rows >= 1, cols >= 1, 2 <= num_to_win <= max(rows, cols) and stack_history >= 1')
+        self.name = 'ConnectFour'
+        self.rows, self.cols, self.stack_history, self.num_to_win = rows, cols, stack_history, num_to_win
+        self.black_player_id, self.white_player_id = 1, 2
+        self.black_color, self.white_color = 1, 2
+        self.num_actions = cols + 1
+        self.resign_action: Optional[int] = cols
+        self.observation_shape = (stack_history * 2 + 1, rows, cols)
+        self.reset()
+
+    def reset(self, **kwargs) -> np.ndarray:
+        self.board = np.zeros((self.rows, self.cols), dtype=np.int8)
+        self.actions_mask = np.ones(self.num_actions, dtype=np.bool_)
+        self.current_player = self.black_player_id
+        self.steps = 0
+        self.winner: Optional[int] = None
+        self.last_actions = {self.black_player_id: None, self.white_player_id: None}
+        self.last_coords: Optional[Tuple[int, int]] = None  # where the last stone landed
+        self.feature_planes = {p: np.zeros((self.stack_history, self.rows, self.cols), dtype=np.int8) for p in (self.black_player_id, self.white_player_id)}
+        return self.observation()
+
+    def landing_row(self, col: int) -> int:
+        """The lowest empty row of column `col` (-1: the column is full)."""
+        return int(self.rows - 1 - np.count_nonzero(self.board[:, col]))
+
+    def action_to_coords(self, action: int) -> Tuple[int, int]:
+        return self.landing_row(action), action
+
+    def coords_to_action(self, coords: Tuple[int, int]) -> int:
+        return coords[1]
+
+    def step(self, action: int):
+        if not 0 <= action <= self.num_actions - 1:
+            raise ValueError(f'Invalid action. Expect action to be in range [0, {self.num_actions}], got {action}')
+        if not self.actions_mask[action]:
+            raise ValueError(f'Invalid action. The column {action} is full.')
+        if self.is_game_over:
+            raise RuntimeError('Game is over, call reset before using step method.')
+        action = int(action)
+        reward = 0.0
+        self.last_actions[self.current_player] = action
+        if action == self.resign_action:
+            reward = -1.0
+            self.winner = self.opponent_player
+        else:
+            r = self.landing_row(action)
+            self.board[r, action] = self.current_player_color
+            self.last_coords = (r, action)
+            if r == 0:
+                self.actions_mask[action] = False  # the top cell is taken
+            planes = self.feature_planes[self.current_player]
+            planes[1:] = planes[:-1].copy()
+            planes[0] = (self.board == self.current_player_color)
+            if self.is_current_player_won():
+                reward = 1.0
+                self.winner = self.current_player
+        done = self.is_game_over
+        if not done:
+            self.current_player = self.opponent_player
+        self.steps += 1
+        return self.observation(), reward, done, {}
+
+    def is_current_player_won(self) -> bool:
+        """Lines through the last stone only; needs at least 2 * (num_to_win - 1) earlier plies (steps not yet incremented)."""
+        if self.steps < (self.num_to_win - 1) * 2:
+            return False
+        last = self.last_actions[self.current_player]
+        if last is None or last == self.resign_action:
+            return False
+        r0, c0 = self.last_coords
+        colour = self.current_player_color
+        for dr, dc in ((0, 1), (1, 0), (1, 1), (-1, 1)):
+            count = 1
+            for sgn in (1, -1):
+                r, c = r0 + sgn * dr, c0 + sgn * dc
+                while 0 <= r < self.rows and 0 <= c < self.cols and self.board[r, c] == colour:
+                    count += 1
+                    r, c = r + sgn * dr, c + sgn * dc
+            if count >= self.num_to_win:
+                return True
+        return False
+
+    def observation(self) -> np.ndarray:
+        me, opp = self.current_player, self.opponent_player
+        out = np.zeros(self.observation_shape, dtype=np.int8)
+        out[0:2 * self.stack_history:2] = self.feature_planes[me]
+        out[1:2 * self.stack_history:2] = self.feature_planes[opp]
+        out[-1] = 1 if me == self.black_player_id else 0
+        return out
+
+
 class ScaledFloatFrame:
     """`gym_env.py:214-224`: frames as float32 scaled to [0, 1] (x / 255).  Host-stepped self-play with device frame stacking
     recognises it inside `StackFrameAndAction` and uploads the raw uint8 frames instead, scaled on the device to the same values."""

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libmzplanner_hip.so')
 
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
 ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_CATCH, ENV_BREAKOUT = 0, 1, 2, 3, 4, 5, 6, 7
+ENV_CONNECT4 = 8
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
 ARENA_NONE, ARENA_RANDOM, ARENA_PLANNER = 0, 1, 2  # opponent kinds of mz_arena_reset
 SIDE_CHALLENGER, SIDE_OPPONENT, SIDE_RANDOM, SIDE_OPENING = 0, 1, 2, 3  # who chose a ply's move (arena_read_ply 'side')
@@ -72,6 +73,10 @@ class MzBreakoutEnv(C.Structure):
     _fields_ = [('rows', C.c_int32), ('cols', C.c_int32), ('brick_rows', C.c_int32), ('max_moves', C.c_int32), ('record_format', C.c_int32)]
 
 
+class MzConnect4Env(C.Structure):
+    _fields_ = [('num_to_win', C.c_int32), ('temp_switch_steps', C.c_int32)]
+
+
 _lib = None
 
 
@@ -120,6 +125,11 @@ def load_library():
     L.mz_selfplay_reset_catch.argtypes = [vp, C.POINTER(MzCatchEnv)]
     L.mz_selfplay_reset_breakout.argtypes = [vp, C.POINTER(MzBreakoutEnv)]
     L.mz_arena_reset_breakout.argtypes = [vp, C.POINTER(MzBreakoutEnv), vp]
+    # (the Connect Four entries: include/mzplanner.h declares them `extern int ...`, outside ABI_SYMBOLS: see the note there)
+    L.mz_selfplay_reset_connect4.argtypes = [vp, C.POINTER(MzConnect4Env)]
+    L.mz_connect4_debug_step.argtypes = [vp, vp]
+    L.mz_connect4_debug_mask.argtypes = [vp, vp]
+    L.mz_arena_reset_connect4.argtypes = [vp, C.POINTER(MzConnect4Env), i32, vp, i32]
     L.mz_arena_reset.argtypes = [vp, i32, i32, vp, i32, vp]
     L.mz_arena_step.argtypes = [vp, i32]
     L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
@@ -577,6 +587,25 @@ class Planner:
         x = MzCatchEnv(int(rows), int(cols), rfmt)
         _chk(self.lib.mz_selfplay_reset_catch(self.h, C.byref(x)))
 
+    def selfplay_reset_connect4(self, num_to_win=4, temp_switch_steps=0):
+        """Start self-play on the device Connect Four env (mz_selfplay_reset_connect4; `games.ConnectFourEnv` is the same game on the host):
+        the board is the planner's own (9, rows, cols) input, `num_actions` = cols + 1.  `temp_switch_steps`: the board temperature
+        schedule's switch from 1.0 to 0.1 (0: 6).  `selfplay_step` then plays whole moves on the device."""
+        x = MzConnect4Env(int(num_to_win), int(temp_switch_steps))
+        _chk(self.lib.mz_selfplay_reset_connect4(self.h, C.byref(x)))
+
+    def debug_connect4_step(self, actions):
+        """Test hook (mz_connect4_debug_step): one move of all envs with `actions` [B] through the launches of a self-play move, without
+        the search; the recorded policy is the one-hot of the action, the root value 0.  An illegal action raises before any launch."""
+        a = np.ascontiguousarray(actions, np.int32).reshape(self.B)
+        _chk(self.lib.mz_connect4_debug_step(self.h, _p(a)))
+
+    def debug_connect4_mask(self):
+        """Test hook (mz_connect4_debug_mask): the device Connect Four envs' legal-action masks, uint8 [B, A]."""
+        m = np.empty((self.B, self.A), np.uint8)
+        _chk(self.lib.mz_connect4_debug_mask(self.h, _p(m)))
+        return m
+
     def selfplay_read(self, n_moves, fields=None):
         """Records of the last `n_moves` moves, arrays [n_moves, B, ...].  `fields`: subset of ('obs', 'action', 'reward', 'pi',
         'root_value', 'player', 'done') to copy out (default all): with the device epilogue attached a host loop only needs
@@ -657,6 +686,20 @@ class Planner:
             raise ValueError(f"opponent must be None, 'random' or a Planner, got {opponent!r}")
         init = None if init_state is None else np.ascontiguousarray(init_state, np.float64).reshape(self.B, 4)
         _chk(self.lib.mz_arena_reset(self.h, int(env_kind), kind, q.h if q is not None else None, int(opening_plies), _p(init)))
+        self._arena_opponent = q
+
+    def arena_reset_connect4(self, opponent, opening_plies=0, num_to_win=4):
+        """Start `num_envs` evaluation games of the device Connect Four env (mz_arena_reset_connect4): `arena_reset`'s two-player arena
+        -- `opponent` 'random' or a second `Planner`, colours balanced over the two halves, paired random openings -- on this game.
+        Random moves are drawn from the legal columns only: they never resign."""
+        if isinstance(opponent, Planner):
+            kind, q = ARENA_PLANNER, opponent
+        elif opponent == 'random':
+            kind, q = ARENA_RANDOM, None
+        else:
+            raise ValueError(f"opponent must be 'random' or a Planner, got {opponent!r}")
+        x = MzConnect4Env(int(num_to_win), 0)
+        _chk(self.lib.mz_arena_reset_connect4(self.h, C.byref(x), kind, q.h if q is not None else None, int(opening_plies)))
         self._arena_opponent = q
 
     def arena_reset_catch(self, rows=12, cols=12, ball_cols=None, start_rows=None):
