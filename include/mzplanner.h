@@ -38,6 +38,7 @@ extern "C" {
 #define MZ_ENV_CATCH 6     /* Catch as an image game on the device: uint8 frames through the host-stepped path's kernels (mz_selfplay_reset_catch) */
 #define MZ_ENV_BREAKOUT 7  /* a brick-breaking image game on the device, rewards during the episode (mz_selfplay_reset_breakout) */
 #define MZ_ENV_CONNECT4 8  /* Connect Four on the device: a two-player game on a rows x cols board, one action per column (mz_selfplay_reset_connect4) */
+#define MZ_ENV_OTHELLO 9   /* Othello on the device: placements flip stones, a side without a placement passes, the count decides (mz_selfplay_reset_othello) */
 
 /* Everything uct_search reads from MuZeroConfig (config.py:51-103) and from the network constructors
  * (network.py:239-247, 504-512, 543-549), plus planner-only sizing knobs. */
@@ -243,7 +244,7 @@ typedef struct {
     /* How `state` is stored.  MZ_STATE_F32 (0: a zero-initialised field): float32, as ever.  The other formats are EXACT -- every state decodes to
      * the float32 observation bit for bit -- and are refused (MZ_E_INVALID naming state_format) at mz_selfplay_reset / mz_selfplay_reset_external
      * for an env whose observations they cannot hold:
-     *   MZ_STATE_I8         [capacity, obs] one signed byte per element, value (float)(int8_t)b.  TicTacToe, Gomoku, Connect Four (0 / 1 planes), and host-stepped
+     *   MZ_STATE_I8         [capacity, obs] one signed byte per element, value (float)(int8_t)b.  TicTacToe, Gomoku, Connect Four, Othello (0 / 1 planes), and host-stepped
      *                       envs: there every emitted state is checked (decode(encode(v)) == v bit for bit); on a mismatch the replay count does not
      *                       advance and mz_selfplay_external_commit returns MZ_E_INVALID naming the smallest such env; mz_selfplay_reset_external next.
      *   MZ_STATE_FRAMES_U8  host-stepped envs with stack_history = S > 0, is_obs_image, frame_u8 and num_actions <= 256 only.  A row is the
@@ -381,6 +382,38 @@ extern int mz_connect4_debug_step(mz_planner* p, const int32_t* h_action);
 /* Test hook: the envs' legal-action masks as the next search will see them, h_mask uint8 [B, num_actions]. */
 extern int mz_connect4_debug_mask(mz_planner* p, uint8_t* h_mask);
 
+/* Othello (MZ_ENV_OTHELLO): the device board game in which a move changes more than one point.  muzero_amd.games.OthelloEnv is the
+ * specification; BoardGameEnv's conventions hold wherever they apply.  Board obs_h rows x obs_w columns, each 4 .. 8, point r * obs_w + c,
+ * players 1 (black, moves first) and 2; start: white on (r0, c0) and (r0 + 1, c0 + 1), black on (r0, c0 + 1) and (r0 + 1, c0), r0 =
+ * obs_h / 2 - 1, c0 = obs_w / 2 - 1.  With nn = obs_h * obs_w: action a < nn places a stone on point a, legal iff the point is empty and
+ * the stone flips at least one run (in each of the 8 directions, one or more opposing stones next to the point followed directly by a
+ * stone of the mover; runs end at the board's edges); action nn passes, legal iff the mover has no placement (a real ply: the side to
+ * move alternates on every ply); action nn + 1 resigns (always legal, the mover gets -1).  After a placement, if neither colour can place,
+ * the game is over and the stones are counted after the flips: the mover gets +1 with more, -1 with fewer, 0 with as many (a draw).  A
+ * pass never ends a game.  The observation is BoardGameEnv's (9, obs_h, obs_w) -- own and opponent stone history interleaved, newest
+ * first, then the colour plane -- but BOTH colours' histories advance on every ply, pass included: plane k of a colour holds its stones
+ * as they stood k plies ago (a fresh game: plane 0 the start stones).  A finished env restarts at once.  A game has at most
+ * 2 * (nn - 4) plies; the record ring is sized for that.  Temperature < 0 in mz_selfplay_step: 1.0 for the first temp_switch_steps moves
+ * of an episode, then 0.1.  Refusals (MZ_E_INVALID naming the field): net_kind other than MZ_NET_BOARD, obs_c != 9, obs_h or obs_w
+ * outside 4 .. 8, num_actions != obs_h * obs_w + 2, an attached replay of MZ_STATE_FRAMES_U8 (MZ_STATE_F32 and MZ_STATE_I8 are served; with
+ * is_board_game the items are Monte-Carlo returns on episode end).  Afterwards mz_selfplay_step, _read, _counters and _record_info work
+ * as on the other device kinds; mz_selfplay_external_act / _commit return MZ_E_STATE; mz_selfplay_reset and mz_arena_reset refuse the
+ * kind by naming the right reset. */
+typedef struct {
+    int32_t temp_switch_steps; /* 0: 6 */
+} mz_othello_env;
+int mz_selfplay_reset_othello(mz_planner* p, const mz_othello_env* env);
+/* Test hook: one move of all envs with the caller's actions (h_action int32 [B]) through the launches of a self-play move -- pre, step,
+ * record, epilogue -- without the search: the recorded policy is the one-hot of the action, the root value 0.  An illegal action of any
+ * env is MZ_E_INVALID naming the env, before any launch; MZ_E_STATE unless mz_selfplay_reset_othello came before. */
+int mz_othello_debug_step(mz_planner* p, const int32_t* h_action);
+/* Test hook: the envs' legal-action masks as the next search will see them, h_mask uint8 [B, num_actions]. */
+int mz_othello_debug_mask(mz_planner* p, uint8_t* h_mask);
+/* Test hook: the envs' boards, h_board int8 [B, obs_h * obs_w] (0 empty, 1 black, 2 white): after mz_selfplay_reset_othello the positions
+ * the next move starts from; after mz_arena_reset_othello the live games' positions and the finished games' frozen final boards, flips
+ * included.  MZ_E_STATE unless one of the two resets came before. */
+int mz_othello_debug_board(mz_planner* p, int8_t* h_board);
+
 /* Arena: the evaluators' game loops (pipeline.py:289-397 board games, pipeline.py:400-488 one-player envs) for num_envs games in
  * lock-step on the device.  Every searched move is uct_search(deterministic = True) on the planner's search kernels: no root noise, the
  * most-visited child, tie draws consumed as mz_planner_search consumes them (mz_debug_capture_rng reads them back per handle).  The
@@ -442,6 +475,11 @@ int mz_arena_reset_breakout(mz_planner* p, const mz_breakout_env* env, const int
  * mz_selfplay_reset_connect4 and of mz_arena_reset's sides.  Random moves (openings and MZ_ARENA_RANDOM) are legal[floor(u * n_legal)]
  * over the legal COLUMNS only: a random move never resigns.  mz_arena_step, _read_ply and _result as ever. */
 extern int mz_arena_reset_connect4(mz_planner* p, const mz_connect4_env* env, int32_t opponent_kind, mz_planner* q_or_null, int32_t opening_plies);
+/* Othello in the arena: the same two-player arena on MZ_ENV_OTHELLO, with the refusals of mz_selfplay_reset_othello and of
+ * mz_arena_reset's sides.  Random moves (openings and MZ_ARENA_RANDOM) are legal[floor(u * n_legal)] over the legal placements, or the
+ * pass where there is none: a random move never resigns.  A finished game is frozen with its final board, flips included; the winner is
+ * the colour with more stones (or the side that did not resign), a draw on equal counts.  mz_arena_step, _read_ply and _result as ever. */
+int mz_arena_reset_othello(mz_planner* p, const mz_othello_env* env, int32_t opponent_kind, mz_planner* q_or_null, int32_t opening_plies);
 /* The same ply for envs the host steps, cut where it steps them.  `env` describes the frames as for mz_selfplay_reset_external (stacked
  * uint8 or float images, stacked vectors, stack_history = 0 for whole observations); max_episode_steps and temp_switch_steps are not used.
  *   mz_arena_external_act    -- uploads every env's newest frame, mask and player ids (arguments as mz_selfplay_external_act's; the entries

@@ -245,6 +245,140 @@ class ConnectFourEnv(BoardGameEnv):
         return out
 
 
+class OthelloEnv(BoardGameEnv):
+    """Othello (Reversi); the specification of the device env MZ_ENV_OTHELLO (`csrc/mz_othello.h`, same rules).  The reference defines no
+    such game: this class is the definition, with `BoardGameEnv`'s conventions wherever they apply.  A `rows` x `cols` board (each 4..8),
+    point r * cols + c; players 1 (black, moves first) and 2 (white); start: white on (r0, c0) and (r0 + 1, c0 + 1), black on (r0, c0 + 1)
+    and (r0 + 1, c0) with r0 = rows // 2 - 1, c0 = cols // 2 - 1.  Action a < rows * cols places a stone on point a: legal iff the point
+    is empty and the stone flips at least one run -- in each of the 8 directions, one or more opposing stones next to the point followed
+    directly by a stone of the mover; runs end at the board's edges.  Action rows * cols passes: legal iff the mover has no placement (a
+    real ply: the side to move alternates on every ply).  Action rows * cols + 1 resigns (always legal; -1 for the mover, the opponent
+    wins).  After a placement, if neither colour can place, the game is over and the stones are counted after the flips: more for the
+    mover +1, fewer -1 (the opponent wins), equal 0 (a draw, no winner).  A pass never ends a game.  The side to move switches only if
+    the game is not over, and the mask is rebuilt only then.  Both colours' history planes advance on every ply, pass included: plane k
+    of colour p holds p's stones as they stood k plies ago (a fresh game: plane 0 the start stones, the older planes empty).
+    Observation: `BoardGameEnv.observation`'s planes on (rows, cols)."""
+
+    DIRECTIONS = ((0, 1), (1, 1), (1, 0), (1, -1), (0, -1), (-1, -1), (-1, 0), (-1, 1))
+
+    def __init__(self, rows: int = 8, cols: int = 8, stack_history: int = 4) -> None:
+        if not (4 <= rows <= 8 and 4 <= cols <= 8) or stack_history < 1:
+            raise ValueError('OthelloEnv needs rows and cols in 4..8 and stack_history >= 1')
+        self.name = 'Othello'
+        self.rows, self.cols, self.stack_history = rows, cols, stack_history
+        self.black_player_id, self.white_player_id = 1, 2
+        self.black_color, self.white_color = 1, 2
+        self.num_actions = rows * cols + 2
+        self.pass_action = rows * cols
+        self.resign_action: Optional[int] = rows * cols + 1
+        self.observation_shape = (stack_history * 2 + 1, rows, cols)
+        self.reset()
+
+    def reset(self, **kwargs) -> np.ndarray:
+        self.board = np.zeros((self.rows, self.cols), dtype=np.int8)
+        r0, c0 = self.rows // 2 - 1, self.cols // 2 - 1
+        self.board[r0, c0] = self.board[r0 + 1, c0 + 1] = self.white_color
+        self.board[r0, c0 + 1] = self.board[r0 + 1, c0] = self.black_color
+        self.current_player = self.black_player_id
+        self.steps = 0
+        self.winner: Optional[int] = None
+        self.finished = False  # the game ended by the count (a draw has no winner)
+        self.last_actions = {self.black_player_id: None, self.white_player_id: None}
+        self.feature_planes = {p: np.zeros((self.stack_history, self.rows, self.cols), dtype=np.int8) for p in (self.black_player_id, self.white_player_id)}
+        for p in (self.black_player_id, self.white_player_id):
+            self.feature_planes[p][0] = (self.board == p)
+        self._rebuild_mask()
+        return self.observation()
+
+    @property
+    def is_game_over(self) -> bool:
+        return self.winner is not None or self.finished
+
+    def action_to_coords(self, action: int) -> Tuple[int, int]:
+        return action // self.cols, action % self.cols
+
+    def coords_to_action(self, coords: Tuple[int, int]) -> int:
+        return coords[0] * self.cols + coords[1]
+
+    def flips(self, r0: int, c0: int, colour: int):
+        """The stones a placement of `colour` on the empty point (r0, c0) flips, as a list of coordinates."""
+        out = []
+        for dr, dc in self.DIRECTIONS:
+            run = []
+            r, c = r0 + dr, c0 + dc
+            while 0 <= r < self.rows and 0 <= c < self.cols and self.board[r, c] == 3 - colour:
+                run.append((r, c))
+                r, c = r + dr, c + dc
+            if run and 0 <= r < self.rows and 0 <= c < self.cols and self.board[r, c] == colour:
+                out += run
+        return out
+
+    def legal_placements(self, colour: int) -> np.ndarray:
+        """bool [rows * cols]: the points on which `colour` may place."""
+        out = np.zeros(self.rows * self.cols, dtype=np.bool_)
+        for r in range(self.rows):
+            for c in range(self.cols):
+                if self.board[r, c] == 0 and self.flips(r, c, colour):
+                    out[r * self.cols + c] = True
+        return out
+
+    def _rebuild_mask(self) -> None:
+        nn = self.rows * self.cols
+        self.actions_mask = np.zeros(self.num_actions, dtype=np.bool_)
+        self.actions_mask[:nn] = self.legal_placements(self.current_player_color)
+        self.actions_mask[nn] = not self.actions_mask[:nn].any()
+        self.actions_mask[nn + 1] = True
+
+    def step(self, action: int):
+        if not 0 <= action <= self.num_actions - 1:
+            raise ValueError(f'Invalid action. Expect action to be in range [0, {self.num_actions}], got {action}')
+        if not self.actions_mask[action]:
+            raise ValueError(f'Invalid action. The action {action} is not legal here.')
+        if self.is_game_over:
+            raise RuntimeError('Game is over, call reset before using step method.')
+        action = int(action)
+        reward = 0.0
+        me, opp = self.current_player, self.opponent_player
+        self.last_actions[me] = action
+        if action == self.resign_action:
+            reward = -1.0
+            self.winner = opp
+        else:
+            if action != self.pass_action:
+                r, c = self.action_to_coords(action)
+                for fr, fc in self.flips(r, c, me):
+                    self.board[fr, fc] = me
+                self.board[r, c] = me
+            for p in (me, opp):  # both histories advance on every ply
+                planes = self.feature_planes[p]
+                planes[1:] = planes[:-1].copy()
+                planes[0] = (self.board == p)
+            if action != self.pass_action and not self.legal_placements(me).any() and not self.legal_placements(opp).any():
+                mine, theirs = int(np.count_nonzero(self.board == me)), int(np.count_nonzero(self.board == opp))
+                self.finished = True
+                if mine > theirs:
+                    reward, self.winner = 1.0, me
+                elif mine < theirs:
+                    reward, self.winner = -1.0, opp
+        done = self.is_game_over
+        if not done:
+            self.current_player = opp
+            self._rebuild_mask()
+        self.steps += 1
+        return self.observation(), reward, done, {}
+
+    def is_current_player_won(self) -> bool:
+        return self.winner is not None and self.winner == self.current_player
+
+    def observation(self) -> np.ndarray:
+        me, opp = self.current_player, self.opponent_player
+        out = np.zeros(self.observation_shape, dtype=np.int8)
+        out[0:2 * self.stack_history:2] = self.feature_planes[me]
+        out[1:2 * self.stack_history:2] = self.feature_planes[opp]
+        out[-1] = 1 if me == self.black_player_id else 0
+        return out
+
+
 class ScaledFloatFrame:
     """`gym_env.py:214-224`: frames as float32 scaled to [0, 1] (x / 255).  Host-stepped self-play with device frame stacking
     recognises it inside `StackFrameAndAction` and uploads the raw uint8 frames instead, scaled on the device to the same values."""

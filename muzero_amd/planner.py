@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libmzplanner_hip.so')
 NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
 ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_CATCH, ENV_BREAKOUT = 0, 1, 2, 3, 4, 5, 6, 7
 ENV_CONNECT4 = 8
+ENV_OTHELLO = 9
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
 ARENA_NONE, ARENA_RANDOM, ARENA_PLANNER = 0, 1, 2  # opponent kinds of mz_arena_reset
 SIDE_CHALLENGER, SIDE_OPPONENT, SIDE_RANDOM, SIDE_OPENING = 0, 1, 2, 3  # who chose a ply's move (arena_read_ply 'side')
@@ -27,9 +28,9 @@ ABI_SYMBOLS = [
     'mz_planner_search_scripted', 'mz_selfplay_reset', 'mz_selfplay_step', 'mz_selfplay_read', 'mz_selfplay_counters',
     'mz_selfplay_record_info',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
-    'mz_selfplay_reset_catch', 'mz_selfplay_reset_breakout',
+    'mz_selfplay_reset_catch', 'mz_selfplay_reset_breakout', 'mz_selfplay_reset_othello', 'mz_othello_debug_step', 'mz_othello_debug_mask', 'mz_othello_debug_board',
     'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
-    'mz_arena_reset_catch', 'mz_arena_reset_breakout', 'mz_arena_reset_external', 'mz_arena_external_act', 'mz_arena_external_commit',
+    'mz_arena_reset_catch', 'mz_arena_reset_breakout', 'mz_arena_reset_othello', 'mz_arena_reset_external', 'mz_arena_external_act', 'mz_arena_external_commit',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
 ]
 
@@ -75,6 +76,10 @@ class MzBreakoutEnv(C.Structure):
 
 class MzConnect4Env(C.Structure):
     _fields_ = [('num_to_win', C.c_int32), ('temp_switch_steps', C.c_int32)]
+
+
+class MzOthelloEnv(C.Structure):
+    _fields_ = [('temp_switch_steps', C.c_int32)]
 
 
 _lib = None
@@ -130,6 +135,11 @@ def load_library():
     L.mz_connect4_debug_step.argtypes = [vp, vp]
     L.mz_connect4_debug_mask.argtypes = [vp, vp]
     L.mz_arena_reset_connect4.argtypes = [vp, C.POINTER(MzConnect4Env), i32, vp, i32]
+    L.mz_selfplay_reset_othello.argtypes = [vp, C.POINTER(MzOthelloEnv)]
+    L.mz_othello_debug_step.argtypes = [vp, vp]
+    L.mz_othello_debug_mask.argtypes = [vp, vp]
+    L.mz_othello_debug_board.argtypes = [vp, vp]
+    L.mz_arena_reset_othello.argtypes = [vp, C.POINTER(MzOthelloEnv), i32, vp, i32]
     L.mz_arena_reset.argtypes = [vp, i32, i32, vp, i32, vp]
     L.mz_arena_step.argtypes = [vp, i32]
     L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
@@ -606,6 +616,32 @@ class Planner:
         _chk(self.lib.mz_connect4_debug_mask(self.h, _p(m)))
         return m
 
+    def selfplay_reset_othello(self, temp_switch_steps=0):
+        """Start self-play on the device Othello env (mz_selfplay_reset_othello; `games.OthelloEnv` is the same game on the host): the
+        board is the planner's own (9, rows, cols) input, rows and cols in 4..8, `num_actions` = rows * cols + 2 (placements, pass,
+        resign).  `temp_switch_steps`: the board temperature schedule's switch from 1.0 to 0.1 (0: 6)."""
+        x = MzOthelloEnv(int(temp_switch_steps))
+        _chk(self.lib.mz_selfplay_reset_othello(self.h, C.byref(x)))
+
+    def debug_othello_step(self, actions):
+        """Test hook (mz_othello_debug_step): one move of all envs with `actions` [B] through the launches of a self-play move, without
+        the search; the recorded policy is the one-hot of the action, the root value 0.  An illegal action raises before any launch."""
+        a = np.ascontiguousarray(actions, np.int32).reshape(self.B)
+        _chk(self.lib.mz_othello_debug_step(self.h, _p(a)))
+
+    def debug_othello_mask(self):
+        """Test hook (mz_othello_debug_mask): the device Othello envs' legal-action masks, uint8 [B, A]."""
+        m = np.empty((self.B, self.A), np.uint8)
+        _chk(self.lib.mz_othello_debug_mask(self.h, _p(m)))
+        return m
+
+    def debug_othello_board(self):
+        """Test hook (mz_othello_debug_board): the device Othello envs' boards, int8 [B, rows * cols] (0 empty, 1 black, 2 white); in an
+        arena a finished game's row is its frozen final board."""
+        b = np.empty((self.B, self.obs_dim // 9), np.int8)
+        _chk(self.lib.mz_othello_debug_board(self.h, _p(b)))
+        return b
+
     def selfplay_read(self, n_moves, fields=None):
         """Records of the last `n_moves` moves, arrays [n_moves, B, ...].  `fields`: subset of ('obs', 'action', 'reward', 'pi',
         'root_value', 'player', 'done') to copy out (default all): with the device epilogue attached a host loop only needs
@@ -700,6 +736,20 @@ class Planner:
             raise ValueError(f"opponent must be 'random' or a Planner, got {opponent!r}")
         x = MzConnect4Env(int(num_to_win), 0)
         _chk(self.lib.mz_arena_reset_connect4(self.h, C.byref(x), kind, q.h if q is not None else None, int(opening_plies)))
+        self._arena_opponent = q
+
+    def arena_reset_othello(self, opponent, opening_plies=0):
+        """Start `num_envs` evaluation games of the device Othello env (mz_arena_reset_othello): `arena_reset`'s two-player arena --
+        `opponent` 'random' or a second `Planner`, colours balanced over the two halves, paired random openings -- on this game.  Random
+        moves are drawn from the legal placements, or are the pass where there is none: they never resign."""
+        if isinstance(opponent, Planner):
+            kind, q = ARENA_PLANNER, opponent
+        elif opponent == 'random':
+            kind, q = ARENA_RANDOM, None
+        else:
+            raise ValueError(f"opponent must be 'random' or a Planner, got {opponent!r}")
+        x = MzOthelloEnv(0)
+        _chk(self.lib.mz_arena_reset_othello(self.h, C.byref(x), kind, q.h if q is not None else None, int(opening_plies)))
         self._arena_opponent = q
 
     def arena_reset_catch(self, rows=12, cols=12, ball_cols=None, start_rows=None):
