@@ -39,6 +39,7 @@ extern "C" {
 #define MZ_ENV_BREAKOUT 7  /* a brick-breaking image game on the device, rewards during the episode (mz_selfplay_reset_breakout) */
 #define MZ_ENV_CONNECT4 8  /* Connect Four on the device: a two-player game on a rows x cols board, one action per column (mz_selfplay_reset_connect4) */
 #define MZ_ENV_OTHELLO 9   /* Othello on the device: placements flip stones, a side without a placement passes, the count decides (mz_selfplay_reset_othello) */
+#define MZ_ENV_GO 10       /* Go on the device: captures, simple ko, a pass that is always legal, Tromp-Taylor area count with komi (mz_selfplay_reset_go) */
 
 /* Everything uct_search reads from MuZeroConfig (config.py:51-103) and from the network constructors
  * (network.py:239-247, 504-512, 543-549), plus planner-only sizing knobs. */
@@ -414,6 +415,43 @@ int mz_othello_debug_mask(mz_planner* p, uint8_t* h_mask);
  * included.  MZ_E_STATE unless one of the two resets came before. */
 int mz_othello_debug_board(mz_planner* p, int8_t* h_board);
 
+/* Go (MZ_ENV_GO): the device board game in which a move removes whole connected groups.  muzero_amd.games.GoEnv is the specification;
+ * BoardGameEnv's conventions hold wherever they apply.  Board obs_h rows x obs_w columns, each 3 .. 19, point r * obs_w + c, empty at the
+ * start; players 1 (black, moves first) and 2.  With nn = obs_h * obs_w: action a < nn places a stone on point a and then removes every
+ * opposing group (4-connected stones of one colour) without a liberty (an empty 4-neighbour); legal iff the point is empty, it is not the
+ * ko point, and the mover's group with the new stone has a liberty after the removals (suicide is illegal).  Simple ko: a placement that
+ * captures exactly one stone, by a stone that is a one-stone group with exactly one liberty, forbids the captured point to the opponent
+ * on the next ply only; no superko.  Action nn passes (always legal, a real ply); action nn + 1 resigns (the mover gets -1; legal iff
+ * allow_resign, else its mask entry is 0 throughout).  The game ends by a resignation, by a pass directly after a pass, or with the ply
+ * that makes the step count max_plies, whatever the action; the last two end in a Tromp-Taylor area count (stones plus the empty regions
+ * that touch that colour only): black wins iff 2 * black_area > 2 * white_area + komi2, white iff less, equal is a draw; the final mover
+ * gets +1, -1 or 0.  The observation is BoardGameEnv's (9, obs_h, obs_w); both colours' histories advance on every ply, pass included.
+ * A finished env restarts at once.  The record ring is sized for max_plies plies.  Temperature < 0 in mz_selfplay_step: 1.0 for the
+ * first temp_switch_steps moves of an episode, then 0.1.  Refusals (MZ_E_INVALID naming the field): net_kind other than MZ_NET_BOARD,
+ * obs_c != 9, obs_h or obs_w outside 3 .. 19, a non-square board of more than 64 points (that combination of the board net's kernels is
+ * not held to the oracle search), num_actions != obs_h * obs_w + 2, komi2 outside 0 .. 2 * nn, max_plies outside 0 .. 2 * nn,
+ * allow_resign other than 0 / 1, an attached replay of MZ_STATE_FRAMES_U8 (MZ_STATE_F32 and MZ_STATE_I8 are served; with is_board_game
+ * the items are Monte-Carlo returns on episode end).  Afterwards mz_selfplay_step, _read, _counters and _record_info work as on the other
+ * device kinds; mz_selfplay_external_act / _commit return MZ_E_STATE; mz_selfplay_reset and mz_arena_reset refuse the kind by naming the
+ * right reset. */
+typedef struct {
+    int32_t temp_switch_steps; /* 0: 6 */
+    int32_t komi2;             /* twice the komi, 0 .. 2 * nn */
+    int32_t max_plies;         /* 0: 2 * nn */
+    int32_t allow_resign;      /* 0: the resignation is never legal; 1: always */
+} mz_go_env;
+int mz_selfplay_reset_go(mz_planner* p, const mz_go_env* env);
+/* Test hook: one move of all envs with the caller's actions (h_action int32 [B]) through the launches of a self-play move -- pre, step,
+ * record, epilogue -- without the search: the recorded policy is the one-hot of the action, the root value 0.  An illegal action of any
+ * env is MZ_E_INVALID naming the env, before any launch; MZ_E_STATE unless mz_selfplay_reset_go came before. */
+int mz_go_debug_step(mz_planner* p, const int32_t* h_action);
+/* Test hook: the envs' legal-action masks as the next search will see them, h_mask uint8 [B, num_actions]. */
+int mz_go_debug_mask(mz_planner* p, uint8_t* h_mask);
+/* Test hook: the envs' boards, h_board int8 [B, obs_h * obs_w] (0 empty, 1 black, 2 white): after mz_selfplay_reset_go the positions the
+ * next move starts from; after mz_arena_reset_go the live games' positions and the finished games' frozen final boards, captures
+ * included.  MZ_E_STATE unless one of the two resets came before. */
+int mz_go_debug_board(mz_planner* p, int8_t* h_board);
+
 /* Arena: the evaluators' game loops (pipeline.py:289-397 board games, pipeline.py:400-488 one-player envs) for num_envs games in
  * lock-step on the device.  Every searched move is uct_search(deterministic = True) on the planner's search kernels: no root noise, the
  * most-visited child, tie draws consumed as mz_planner_search consumes them (mz_debug_capture_rng reads them back per handle).  The
@@ -480,6 +518,11 @@ extern int mz_arena_reset_connect4(mz_planner* p, const mz_connect4_env* env, in
  * pass where there is none: a random move never resigns.  A finished game is frozen with its final board, flips included; the winner is
  * the colour with more stones (or the side that did not resign), a draw on equal counts.  mz_arena_step, _read_ply and _result as ever. */
 int mz_arena_reset_othello(mz_planner* p, const mz_othello_env* env, int32_t opponent_kind, mz_planner* q_or_null, int32_t opening_plies);
+/* Go in the arena: the same two-player arena on MZ_ENV_GO, with the refusals of mz_selfplay_reset_go and of mz_arena_reset's sides.
+ * Random moves (openings and MZ_ARENA_RANDOM) are legal[floor(u * n_legal)] over the legal placements and the pass: a random move may
+ * pass and never resigns.  A finished game is frozen with its final board, captures included; the winner is decided by the area count
+ * (or is the side that did not resign).  mz_arena_step, _read_ply and _result as ever. */
+int mz_arena_reset_go(mz_planner* p, const mz_go_env* env, int32_t opponent_kind, mz_planner* q_or_null, int32_t opening_plies);
 /* The same ply for envs the host steps, cut where it steps them.  `env` describes the frames as for mz_selfplay_reset_external (stacked
  * uint8 or float images, stacked vectors, stack_history = 0 for whole observations); max_episode_steps and temp_switch_steps are not used.
  *   mz_arena_external_act    -- uploads every env's newest frame, mask and player ids (arguments as mz_selfplay_external_act's; the entries

@@ -219,3 +219,27 @@ def make_othello_config(num_training_steps=3000, batch_size=128, min_replay_size
     cfg.num_actions, cfg.stack_history, cfg.rows, cfg.cols, cfg.temp_switch_steps = rows * cols + 2, stack_history, rows, cols, switch
     cfg.input_shape = (2 * stack_history + 1, rows, cols)
     return cfg
+
+
+def make_go_config(num_training_steps=3000, batch_size=128, min_replay_size=2000, rows=7, cols=7, komi2=15, max_plies=0, allow_resign=False,
+                   stack_history=4, temp_switch_steps=8, num_simulations=32, use_tensorboard=False, clip_grad=False) -> MuZeroConfig:
+    """Go (`games.GoEnv`, the device env 'Go') for the board conv net `MuZeroBoardGameNet`: the board games' config -- discount 1,
+    Monte-Carlo returns (td_steps 0), values in [-1, 1] -- and their temperature rule, 1.0 for the first `temp_switch_steps` moves of an
+    episode, then 0.1, on a small net.  Not in the reference; the extra attributes (num_actions = rows * cols + 2: placements, pass,
+    resign; stack_history, rows, cols, komi2, max_plies, allow_resign, temp_switch_steps, input_shape) describe the env, and
+    `run_self_play` / `play_match` read the rules off them when given the name 'Go'."""
+    switch = int(temp_switch_steps)
+
+    def go_visit_softmax_temperature_fn(env_steps, training_steps):
+        return 1.0 if env_steps < switch else 0.1
+
+    cfg = MuZeroConfig(
+        discount=1.0, dirichlet_alpha=0.25, num_simulations=num_simulations, batch_size=batch_size, td_steps=0, lr_init=0.002, lr_milestones=[100e3],
+        visit_softmax_temperature_fn=go_visit_softmax_temperature_fn, known_bounds=KnownBounds(-1, 1),
+        num_training_steps=num_training_steps, num_planes=32, num_res_blocks=2, hidden_dim=0, min_replay_size=min_replay_size,
+        checkpoint_interval=100, acc_seq_length=9999, train_delay=0.0, clip_grad=clip_grad, use_tensorboard=use_tensorboard, is_board_game=True,
+    )
+    cfg.num_actions, cfg.stack_history, cfg.rows, cfg.cols, cfg.temp_switch_steps = rows * cols + 2, stack_history, rows, cols, switch
+    cfg.komi2, cfg.max_plies, cfg.allow_resign = int(komi2), int(max_plies), bool(allow_resign)
+    cfg.input_shape = (2 * stack_history + 1, rows, cols)
+    return cfg

@@ -22,6 +22,7 @@
 #include "mz_breakout.h"
 #include "mz_connect4.h"
 #include "mz_othello.h"
+#include "mz_go.h"
 #include "mz_search.h"
 #include "mz_search_fast.h"
 #include "mz_convnet.h"
@@ -209,6 +210,8 @@ struct mz_planner {
     long long selfplay_moves = 0;  // moves since mz_selfplay_reset
     int c4_temp_steps = 6;         // MZ_ENV_CONNECT4: the board temperature schedule's switch step
     int oth_temp_steps = 6;        // MZ_ENV_OTHELLO: likewise
+    GoRules go{};                  // MZ_ENV_GO: the rules of the last reset and the two per-env arrays (ko point, pass flag)
+    int go_cap = 0;                // envs the two arrays hold
     // host-stepped envs (MZ_ENV_EXTERNAL): device side of the frames / history, pinned staging of every upload and download
     ExtEnv ext{};
     int ext_od = 0;
@@ -625,6 +628,8 @@ extern "C" int mz_planner_destroy(mz_planner* p) {
     if (p->d_dbg_noise) { (void)hipFree(p->d_dbg_noise); (void)hipFree(p->d_dbg_utie); (void)hipFree(p->d_dbg_ufinal); }
     if (p->d_epi_ctr) (void)hipFree(p->d_epi_ctr);
     if (p->d_epi_off) (void)hipFree(p->d_epi_off);
+    if (p->go.ko) (void)hipFree(p->go.ko);
+    if (p->go.passf) (void)hipFree(p->go.passf);
     void* cbufs[] = {p->d_pi_scratch, p->d_regions, p->d_pi0, p->d_sim_reward, p->d_sim_value, (void*)p->d_srcptrs, p->d_dstptrs, p->d_rootptrs, p->d_sim_action};
     for (void* b : cbufs)
         if (b) (void)hipFree(b);
@@ -1610,6 +1615,8 @@ extern "C" int mz_selfplay_reset(mz_planner* p, int32_t env_kind, const double* 
         return fail(MZ_E_INVALID, "MZ_ENV_CONNECT4 has its own reset: mz_selfplay_reset_connect4");
     } else if (env_kind == MZ_ENV_OTHELLO) {
         return fail(MZ_E_INVALID, "MZ_ENV_OTHELLO has its own reset: mz_selfplay_reset_othello");
+    } else if (env_kind == MZ_ENV_GO) {
+        return fail(MZ_E_INVALID, "MZ_ENV_GO has its own reset: mz_selfplay_reset_go");
     } else {
         return fail(MZ_E_INVALID, "unknown env kind");
     }
@@ -1871,6 +1878,152 @@ extern "C" int mz_othello_debug_board(mz_planner* p, int8_t* h_board) {
     return MZ_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Go (mz_go.h): its own reset, pre and step launches around the board-net search; one workgroup per env
+// ---------------------------------------------------------------------------------------------------------
+// what both resets check: the net, the board and the env struct; every refusal names the offending field.  Changes nothing: a refused
+// reset leaves a running game's rules as they were (go_apply stores them once every check has passed).
+static int go_check(mz_planner* p, const mz_go_env* env, const std::string& fn) {
+    const mz_config& c = p->cfg;
+    if (c.net_kind != MZ_NET_BOARD) return fail(MZ_E_INVALID, fn + ": mz_config.net_kind must be MZ_NET_BOARD (Go plays on the board conv net)");
+    if (c.obs_c != 9) return fail(MZ_E_INVALID, fn + ": mz_config.obs_c must be 9 (4 history planes per colour and the colour plane), not " + std::to_string(c.obs_c));
+    if (c.obs_h < 3 || c.obs_h > 19) return fail(MZ_E_INVALID, fn + ": mz_config.obs_h must be in 3 .. 19 (rows of the board), not " + std::to_string(c.obs_h));
+    if (c.obs_w < 3 || c.obs_w > 19) return fail(MZ_E_INVALID, fn + ": mz_config.obs_w must be in 3 .. 19 (columns of the board), not " + std::to_string(c.obs_w));
+    const int nn = c.obs_h * c.obs_w;
+    if (c.obs_h != c.obs_w && nn > 64)
+        return fail(MZ_E_INVALID, fn + ": mz_config.obs_h x obs_w = " + std::to_string(c.obs_h) + " x " + std::to_string(c.obs_w) +
+                                      ": a board of more than 64 points must be square (non-square boards above 64 points are not held to the oracle search and are refused)");
+    if (c.num_actions != nn + 2)
+        return fail(MZ_E_INVALID, fn + ": mz_config.num_actions must be obs_h * obs_w + 2 = " + std::to_string(nn + 2) + " (one per point, pass, resign), not " + std::to_string(c.num_actions));
+    if (env->temp_switch_steps < 0) return fail(MZ_E_INVALID, fn + ": mz_go_env.temp_switch_steps must be >= 0");
+    if (env->komi2 < 0 || env->komi2 > 2 * nn) return fail(MZ_E_INVALID, fn + ": mz_go_env.komi2 must be in 0 .. 2 * obs_h * obs_w = " + std::to_string(2 * nn) + ", not " + std::to_string(env->komi2));
+    if (env->max_plies < 0 || env->max_plies > 2 * nn)
+        return fail(MZ_E_INVALID, fn + ": mz_go_env.max_plies must be 0 (2 * obs_h * obs_w) or in 1 .. " + std::to_string(2 * nn) + ", not " + std::to_string(env->max_plies));
+    if (env->allow_resign != 0 && env->allow_resign != 1) return fail(MZ_E_INVALID, fn + ": mz_go_env.allow_resign must be 0 or 1");
+    return MZ_OK;
+}
+
+// the rules of an accepted reset and the two per-env arrays (ko point, pass flag) into p->go
+static int go_apply(mz_planner* p, const mz_go_env* env) {
+    const mz_config& c = p->cfg;
+    const int nn = c.obs_h * c.obs_w;
+    if (p->go_cap < c.num_envs) {
+        if (p->go.ko) (void)hipFree(p->go.ko);
+        if (p->go.passf) (void)hipFree(p->go.passf);
+        p->go.ko = nullptr; p->go.passf = nullptr; p->go_cap = 0;
+        HIPCHK(hipMalloc(&p->go.ko, (size_t)c.num_envs * sizeof(int)));
+        HIPCHK(hipMalloc(&p->go.passf, (size_t)c.num_envs * sizeof(int)));
+        p->go_cap = c.num_envs;
+    }
+    p->go.rows = c.obs_h; p->go.cols = c.obs_w;
+    p->go.komi2 = env->komi2;
+    p->go.max_plies = env->max_plies > 0 ? env->max_plies : 2 * nn;
+    p->go.allow_resign = env->allow_resign;
+    p->go.temp_steps = env->temp_switch_steps > 0 ? env->temp_switch_steps : 6;
+    return MZ_OK;
+}
+
+extern "C" int mz_selfplay_reset_go(mz_planner* p, const mz_go_env* env) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_selfplay_reset_go");
+    HIPCHK(hipSetDevice(p->device));
+    const mz_config& c = p->cfg;
+    if (p->has_replay && p->replay.state_format != STATE_F32 && p->replay.state_format != STATE_I8)
+        return fail(MZ_E_INVALID, "mz_replay_ring.state_format: the device Go env has float32 (MZ_STATE_F32) and exact int8 (MZ_STATE_I8) states; "
+                                  "MZ_STATE_FRAMES_U8 needs a host-stepped env with uint8 frames");
+    int rc = go_check(p, env, "mz_selfplay_reset_go");
+    if (rc) return rc;
+    rc = go_apply(p, env);
+    if (rc) return rc;
+    if (p->has_replay && p->replay.state_format == STATE_I8) {
+        p->replay.row_bytes = obs_dim(c);
+        p->replay.enc_err = nullptr;
+    }
+    ext_free(p);
+    p->env_kind = MZ_ENV_GO;
+    p->arena_open = false;
+    const int nn = c.obs_h * c.obs_w;
+    // a board game's ring holds the whole game: max_plies plies
+    ring_start(p, c.is_board_game ? p->go.max_plies : (1 << 30) - 64);
+    hipError_t e = env_alloc(p->env, ENV_GO, c.num_envs, c.num_actions, obs_dim(c), p->ring_len, c.obs_w, 0, true, nn);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    GoLaunch P{};
+    P.L.env = p->env; P.L.B = c.num_envs; P.L.seed = c.seed;
+    P.L.obs = p->d_obs; P.L.mask = p->d_mask; P.L.cur = p->d_cur; P.L.opp = p->d_opp;
+    P.G = p->go;
+    hipLaunchKernelGGL(k_go_reset, dim3(c.num_envs), dim3(go_block(nn)), 0, p->stream, P);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MZ_OK;
+}
+
+// one move: temperatures and the record's first half, the search (or, search == false, the caller's d_action / d_pi / d_root), env.step +
+// record + auto-reset
+static int go_move(mz_planner* p, const EnvLaunch& L, bool search) {
+    const mz_config& c = p->cfg;
+    GoLaunch P{};
+    P.L = L; P.G = p->go;
+    hipLaunchKernelGGL(k_go_pre, dim3((c.num_envs + 255) / 256), dim3(256), 0, p->stream, P);
+    HIPCHK(hipMemcpyAsync(p->env.r_obs + (size_t)p->ring_pos * c.num_envs * obs_dim(c), p->d_obs, (size_t)c.num_envs * obs_dim(c) * sizeof(float),
+                          hipMemcpyDeviceToDevice, p->stream));
+    if (search) {
+        int rc = launch_search(p, c.num_envs, 0, true, false, false);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_go_step, dim3(c.num_envs), dim3(go_block(c.obs_h * c.obs_w)), 0, p->stream, P);
+    return MZ_OK;
+}
+
+// Test hook: one move of all envs with the caller's actions through the launches of a self-play move, without the search.  The recorded
+// policy is the one-hot of the action, the root value 0.
+extern "C" int mz_go_debug_step(mz_planner* p, const int32_t* h_action) {
+    if (!p || !h_action) return fail(MZ_E_INVALID, "null argument to mz_go_debug_step");
+    if (p->env_kind != MZ_ENV_GO || p->arena_open) return fail(MZ_E_STATE, "mz_go_debug_step: call mz_selfplay_reset_go first");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    const mz_config& c = p->cfg;
+    const size_t B = (size_t)c.num_envs, A = (size_t)c.num_actions;
+    std::vector<unsigned char> mask(B * A);
+    HIPCHK(hipMemcpy(mask.data(), p->d_mask, B * A, hipMemcpyDeviceToHost));
+    std::vector<double> pi(B * A, 0.0), root(B, 0.0);
+    for (size_t e = 0; e < B; e++) {
+        const int a = h_action[e];
+        if (a < 0 || a >= (int)A || !mask[e * A + a])
+            return fail(MZ_E_INVALID, "mz_go_debug_step: h_action[" + std::to_string(e) + "] = " + std::to_string(a) + " is not a legal action of env " + std::to_string(e));
+        pi[e * A + a] = 1.0;
+    }
+    HIPCHK(hipMemcpy(p->d_action, h_action, B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_pi, pi.data(), B * A * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_root, root.data(), B * sizeof(double), hipMemcpyHostToDevice));
+    EnvLaunch L{};
+    L.env = p->env; L.B = c.num_envs; L.seed = c.seed; L.temperature = 1.0; L.move_counter = p->move_counter;
+    L.obs = p->d_obs; L.mask = p->d_mask; L.cur = p->d_cur; L.opp = p->d_opp; L.temp_out = p->d_temp;
+    L.action = p->d_action; L.pi = p->d_pi; L.root = p->d_root; L.slot = p->ring_pos; L.sims = 0;
+    int rc = go_move(p, L, false);
+    if (rc) return rc;
+    return ring_finish_move(p);
+}
+
+// Test hook: the envs' legal-action masks as the next search will see them, uint8 [B, A]
+extern "C" int mz_go_debug_mask(mz_planner* p, uint8_t* h_mask) {
+    if (!p || !h_mask) return fail(MZ_E_INVALID, "null argument to mz_go_debug_mask");
+    if (p->env_kind != MZ_ENV_GO || p->arena_open) return fail(MZ_E_STATE, "mz_go_debug_mask: call mz_selfplay_reset_go first");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpy(h_mask, p->d_mask, (size_t)p->cfg.num_envs * p->cfg.num_actions, hipMemcpyDeviceToHost));
+    return MZ_OK;
+}
+
+// Test hook: the envs' boards, int8 [B, nn] (0 empty, 1 black, 2 white) -- in self-play the positions the next move starts from, in an
+// arena the live games' positions and the finished games' frozen final boards
+extern "C" int mz_go_debug_board(mz_planner* p, int8_t* h_board) {
+    if (!p || !h_board) return fail(MZ_E_INVALID, "null argument to mz_go_debug_board");
+    if (p->env_kind != MZ_ENV_GO) return fail(MZ_E_STATE, "mz_go_debug_board: call mz_selfplay_reset_go or mz_arena_reset_go first");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpy(h_board, p->env.board, (size_t)p->cfg.num_envs * p->env.nn, hipMemcpyDeviceToHost));
+    return MZ_OK;
+}
+
 extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_moves) {
     if (!p || n_moves < 1) return fail(MZ_E_INVALID, "bad argument to mz_selfplay_step");
     if (p->arena_open) return fail(MZ_E_STATE, "mz_selfplay_step during an arena: call mz_selfplay_reset first");
@@ -1890,6 +2043,9 @@ extern "C" int mz_selfplay_step(mz_planner* p, double temperature, int32_t n_mov
             if (rc) return rc;
         } else if (p->env_kind == MZ_ENV_OTHELLO) {
             int rc = oth_move(p, L, true);
+            if (rc) return rc;
+        } else if (p->env_kind == MZ_ENV_GO) {
+            int rc = go_move(p, L, true);
             if (rc) return rc;
         } else if (!p->conv && !p->hbm_tree && p->env_kind != MZ_ENV_SYNTHETIC) {  // (synthetic frames are redrawn by k_env_synth_obs below)
             // MLP nets with LDS trees: the whole move -- temperature / record, search, env.step, auto-reset -- is ONE kernel launch
@@ -2563,6 +2719,8 @@ extern "C" int mz_arena_reset(mz_planner* p, int32_t env_kind, int32_t opponent_
         return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_CONNECT4 has its own arena reset: mz_arena_reset_connect4");
     } else if (env_kind == MZ_ENV_OTHELLO) {
         return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_OTHELLO has its own arena reset: mz_arena_reset_othello");
+    } else if (env_kind == MZ_ENV_GO) {
+        return fail(MZ_E_INVALID, "mz_arena_reset: MZ_ENV_GO has its own arena reset: mz_arena_reset_go");
     } else {
         return fail(MZ_E_INVALID, "the arena plays the device envs CartPole, TicTacToe and Gomoku (not the synthetic kind)");
     }
@@ -2655,6 +2813,40 @@ extern "C" int mz_arena_reset_othello(mz_planner* p, const mz_othello_env* env, 
     return MZ_OK;
 }
 
+// Go in the two-player arena: mz_arena_reset's states and tally around mz_go.h's reset, pick and step
+extern "C" int mz_arena_reset_go(mz_planner* p, const mz_go_env* env, int32_t opponent_kind, mz_planner* q, int32_t opening_plies) {
+    if (!p || !env) return fail(MZ_E_INVALID, "null argument to mz_arena_reset_go");
+    const mz_config& c = p->cfg;
+    HIPCHK(hipSetDevice(p->device));
+    int rc = go_check(p, env, "mz_arena_reset_go");
+    if (rc) return rc;
+    rc = arena_check_sides(p, true, opponent_kind, q, opening_plies, false);
+    if (rc) return rc;
+    rc = go_apply(p, env);
+    if (rc) return rc;
+    p->env_kind = MZ_ENV_GO;
+    ext_free(p);
+    p->ring_len = 1; p->ring_pos = 0; p->ring_count = 0;  // no self-play records in this mode (mz_selfplay_read: MZ_E_INVALID)
+    p->selfplay_moves = 0;
+    hipError_t e = env_alloc(p->env, ENV_GO, c.num_envs, c.num_actions, obs_dim(c), 1, c.obs_w, 0, true, c.obs_h * c.obs_w);
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("env_alloc: ") + hipGetErrorString(e));
+    e = arena_alloc(p->arena, c.num_envs, c.num_actions, obs_dim(c));
+    if (e != hipSuccess) return fail(MZ_E_HIP, std::string("arena_alloc: ") + hipGetErrorString(e));
+    p->arena.half = c.num_envs / 2;
+    p->arena.opponent = opponent_kind;
+    p->arena.opening_plies = opening_plies;
+    p->arena_q = opponent_kind == MZ_ARENA_PLANNER ? q : nullptr;
+    p->arena_ply = 0;
+    p->arena_img = 0;
+    GoArena Q{};
+    Q.R = arena_launch(p); Q.G = p->go;
+    hipLaunchKernelGGL(k_go_arena_reset, dim3(c.num_envs), dim3(go_block(c.obs_h * c.obs_w)), 0, p->stream, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->arena_open = true;
+    return MZ_OK;
+}
+
 extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     if (!p || n_plies < 1) return fail(MZ_E_INVALID, "bad argument to mz_arena_step");
     if (!p->arena_open) return fail(MZ_E_STATE, "call mz_arena_reset first");
@@ -2666,7 +2858,7 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
     const mz_config& c = p->cfg;
     const int B = c.num_envs, half = p->arena.half;
     const dim3 waves((B + 3) / 4), block(256);
-    const bool c4 = p->env_kind == MZ_ENV_CONNECT4, oth = p->env_kind == MZ_ENV_OTHELLO;
+    const bool c4 = p->env_kind == MZ_ENV_CONNECT4, oth = p->env_kind == MZ_ENV_OTHELLO, go = p->env_kind == MZ_ENV_GO;
     for (int m = 0; m < n_plies; m++) {
         ArenaLaunch R = arena_launch(p);
         const int t = p->arena_ply;
@@ -2695,8 +2887,11 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
         Q.R = R; Q.rows = c.obs_h; Q.cols = c.obs_w;
         OthArena O{};  // (Othello likewise: placements or the pass, never resign)
         O.R = R; O.rows = c.obs_h; O.cols = c.obs_w;
+        GoArena G{};  // (Go: placements and the pass, never resign; one workgroup per env)
+        G.R = R; G.G = p->go;
         if (picks && c4) hipLaunchKernelGGL(k_c4_arena_pick, dim3((B + 255) / 256), block, 0, p->stream, Q);
         else if (picks && oth) hipLaunchKernelGGL(k_oth_arena_pick, dim3((B + 255) / 256), block, 0, p->stream, O);
+        else if (picks && go) hipLaunchKernelGGL(k_go_arena_pick, dim3((B + 255) / 256), block, 0, p->stream, G);
         else if (picks) hipLaunchKernelGGL(k_arena_pick, waves, block, 0, p->stream, R);
         HIPCHK(hipGetLastError());
         if (n_q) {  // the opponent's half on its own stream, beside the challenger's
@@ -2713,6 +2908,7 @@ extern "C" int mz_arena_step(mz_planner* p, int32_t n_plies) {
         if (n_q) HIPCHK(hipStreamWaitEvent(p->stream, p->ev_arena_q, 0));
         if (c4) hipLaunchKernelGGL(k_c4_arena_step, dim3((B + 15) / 16), block, 0, p->stream, Q);
         else if (oth) hipLaunchKernelGGL(k_oth_arena_step, dim3((B + 15) / 16), block, 0, p->stream, O);
+        else if (go) hipLaunchKernelGGL(k_go_arena_step, dim3(B), dim3(go_block(c.obs_h * c.obs_w)), 0, p->stream, G);
         else hipLaunchKernelGGL(k_arena_step, waves, block, 0, p->stream, R);
         HIPCHK(hipGetLastError());
         p->arena_ply++;

@@ -379,6 +379,206 @@ class OthelloEnv(BoardGameEnv):
         return out
 
 
+class GoEnv(BoardGameEnv):
+    """Go; the specification of the device env MZ_ENV_GO (`csrc/mz_go.h`, same rules).  The reference defines no such game: this class is
+    the definition, with `BoardGameEnv`'s conventions wherever they apply.  A `rows` x `cols` board (each 3..19), point r * cols + c, empty
+    at the start; players 1 (black, moves first) and 2 (white); nn = rows * cols, nn + 2 actions.  A group is a 4-connected set of stones
+    of one colour, a liberty an empty 4-neighbour of one of its stones.
+    Placement (action a < nn): the stone goes on the empty point a, then every opposing group without a liberty is removed.  Legal iff the
+    point is empty, it is not the ko point, and the mover's group containing the new stone has a liberty after those removals (suicide is
+    illegal, a "suicide" that captures is legal).
+    Simple ko: if a placement captures exactly one stone and the new stone is a one-stone group with exactly one liberty (the captured
+    point), that point is forbidden to the opponent on the next ply only; any ply, a pass included, clears it.  No superko.
+    Pass (action nn): always legal, a real ply.  Resign (action nn + 1): -1 for the mover, the opponent wins; legal iff `allow_resign`
+    (off: the mask entry is 0 for the whole game).
+    End: a resignation; a pass directly after a pass; or the ply that makes steps == max_plies, whatever the action (`max_plies` 0 means
+    2 * nn, else 1 <= max_plies <= 2 * nn).  The last two end in a Tromp-Taylor area count: a colour's area is its stones plus every empty
+    region whose neighbouring stones are all of that colour (a region touching both colours, or neither, counts for nobody).  Black wins
+    iff 2 * black_area > 2 * white_area + komi2 (`komi2`: twice the komi, an integer in 0 .. 2 * nn), white iff it is less, equal is a draw
+    without a winner; the final mover gets +1, -1 or 0.
+    Both colours' history planes advance on every ply, pass included (plane k of colour p: p's stones as they stood k plies ago).  The side
+    to move switches, and the mask is rebuilt, only if the game goes on.  Observation: `BoardGameEnv.observation`'s planes on (rows,
+    cols); ko and the pass flag are not planes, the history carries them."""
+
+    def __init__(self, rows: int = 9, cols: int = 9, komi2: int = 15, max_plies: int = 0, allow_resign: bool = True, stack_history: int = 4) -> None:
+        if not (3 <= rows <= 19 and 3 <= cols <= 19) or stack_history < 1:
+            raise ValueError('GoEnv needs rows and cols in 3..19 and stack_history >= 1')
+        nn = rows * cols
+        if not 0 <= komi2 <= 2 * nn:
+            raise ValueError(f'GoEnv needs 0 <= komi2 <= 2 * rows * cols, got {komi2}')
+        if not 0 <= max_plies <= 2 * nn:
+            raise ValueError(f'GoEnv needs max_plies = 0 (2 * rows * cols) or 1 <= max_plies <= 2 * rows * cols, got {max_plies}')
+        self.name = 'Go'
+        self.rows, self.cols, self.stack_history = rows, cols, stack_history
+        self.komi2, self.max_plies, self.allow_resign = int(komi2), int(max_plies) if max_plies else 2 * nn, bool(allow_resign)
+        self.black_player_id, self.white_player_id = 1, 2
+        self.black_color, self.white_color = 1, 2
+        self.num_actions = nn + 2
+        self.pass_action = nn
+        self.resign_action: Optional[int] = nn + 1
+        self.observation_shape = (stack_history * 2 + 1, rows, cols)
+        self.reset()
+
+    def reset(self, **kwargs) -> np.ndarray:
+        self.board = np.zeros((self.rows, self.cols), dtype=np.int8)
+        self.current_player = self.black_player_id
+        self.steps = 0
+        self.winner: Optional[int] = None
+        self.finished = False  # the game ended by the count (a draw has no winner)
+        self.ko_point: Optional[int] = None  # forbidden to the side to move on this ply
+        self.last_was_pass = False
+        self.last_actions = {self.black_player_id: None, self.white_player_id: None}
+        self.feature_planes = {p: np.zeros((self.stack_history, self.rows, self.cols), dtype=np.int8) for p in (self.black_player_id, self.white_player_id)}
+        self._rebuild_mask()
+        return self.observation()
+
+    @property
+    def is_game_over(self) -> bool:
+        return self.winner is not None or self.finished
+
+    def action_to_coords(self, action: int) -> Tuple[int, int]:
+        return action // self.cols, action % self.cols
+
+    def coords_to_action(self, coords: Tuple[int, int]) -> int:
+        return coords[0] * self.cols + coords[1]
+
+    def neighbours(self, r: int, c: int):
+        return [(r + dr, c + dc) for dr, dc in ((-1, 0), (1, 0), (0, -1), (0, 1)) if 0 <= r + dr < self.rows and 0 <= c + dc < self.cols]
+
+    @staticmethod
+    def group_of(board: np.ndarray, r0: int, c0: int):
+        """(stones, liberties) of the group of the stone on (r0, c0) of `board`, as sets of coordinates."""
+        rows, cols = board.shape
+        colour = board[r0, c0]
+        stones, libs, todo = {(r0, c0)}, set(), [(r0, c0)]
+        while todo:
+            r, c = todo.pop()
+            for q in ((r - 1, c), (r + 1, c), (r, c - 1), (r, c + 1)):
+                if not (0 <= q[0] < rows and 0 <= q[1] < cols):
+                    continue
+                if board[q] == 0:
+                    libs.add(q)
+                elif board[q] == colour and q not in stones:
+                    stones.add(q)
+                    todo.append(q)
+        return stones, libs
+
+    @classmethod
+    def all_groups_have_liberty(cls, board: np.ndarray) -> bool:
+        """Whether `board` (any shape) is a legal Go position: every group has a liberty."""
+        return all(cls.group_of(board, r, c)[1] for r, c in zip(*np.nonzero(board)))
+
+    def try_place(self, board: np.ndarray, r: int, c: int, colour: int):
+        """A placement of `colour` on the empty point (r, c) of `board`, ko aside: (board after, captured points, ko point it creates or
+        None), or None if it is suicide."""
+        b = board.copy()
+        b[r, c] = colour
+        captured = []
+        for q in self.neighbours(r, c):
+            if b[q] == 3 - colour:
+                stones, libs = self.group_of(b, *q)
+                if not libs:
+                    for s in stones:
+                        b[s] = 0
+                    captured += sorted(stones)
+        stones, libs = self.group_of(b, r, c)
+        if not libs:
+            return None
+        ko = self.coords_to_action(captured[0]) if len(captured) == 1 and len(stones) == 1 and len(libs) == 1 else None
+        return b, captured, ko
+
+    def legal_placements(self, colour: int) -> np.ndarray:
+        """bool [rows * cols]: the points on which `colour` may place now (the ko point excluded)."""
+        out = np.zeros(self.rows * self.cols, dtype=np.bool_)
+        for r in range(self.rows):
+            for c in range(self.cols):
+                a = r * self.cols + c
+                if self.board[r, c] != 0 or a == self.ko_point:
+                    continue
+                # a stone next to an empty point has a liberty whatever it captures; otherwise play it out
+                out[a] = any(self.board[q] == 0 for q in self.neighbours(r, c)) or self.try_place(self.board, r, c, colour) is not None
+        return out
+
+    def _rebuild_mask(self) -> None:
+        nn = self.rows * self.cols
+        self.actions_mask = np.zeros(self.num_actions, dtype=np.bool_)
+        self.actions_mask[:nn] = self.legal_placements(self.current_player_color)
+        self.actions_mask[nn] = True
+        self.actions_mask[nn + 1] = self.allow_resign
+
+    def areas(self) -> Tuple[int, int]:
+        """Tromp-Taylor areas (black, white): stones plus the empty regions that touch stones of that colour only."""
+        area = [0, int(np.count_nonzero(self.board == 1)), int(np.count_nonzero(self.board == 2))]
+        seen = np.zeros((self.rows, self.cols), dtype=np.bool_)
+        for r0 in range(self.rows):
+            for c0 in range(self.cols):
+                if self.board[r0, c0] != 0 or seen[r0, c0]:
+                    continue
+                seen[r0, c0] = True
+                region, touches, todo = 0, set(), [(r0, c0)]
+                while todo:
+                    r, c = todo.pop()
+                    region += 1
+                    for q in self.neighbours(r, c):
+                        if self.board[q] != 0:
+                            touches.add(int(self.board[q]))
+                        elif not seen[q]:
+                            seen[q] = True
+                            todo.append(q)
+                if len(touches) == 1:
+                    area[touches.pop()] += region
+        return area[1], area[2]
+
+    def step(self, action: int):
+        if not 0 <= action <= self.num_actions - 1:
+            raise ValueError(f'Invalid action. Expect action to be in range [0, {self.num_actions}], got {action}')
+        if not self.actions_mask[action]:
+            raise ValueError(f'Invalid action. The action {action} is not legal here.')
+        if self.is_game_over:
+            raise RuntimeError('Game is over, call reset before using step method.')
+        action = int(action)
+        reward = 0.0
+        me, opp = self.current_player, self.opponent_player
+        self.last_actions[me] = action
+        if action == self.resign_action:
+            reward = -1.0
+            self.winner = opp
+        else:
+            passed = action == self.pass_action
+            self.ko_point = None  # any ply clears it
+            if not passed:
+                self.board, _, self.ko_point = self.try_place(self.board, *self.action_to_coords(action), me)
+            for p in (me, opp):  # both histories advance on every ply
+                planes = self.feature_planes[p]
+                planes[1:] = planes[:-1].copy()
+                planes[0] = (self.board == p)
+            if (passed and self.last_was_pass) or self.steps + 1 == self.max_plies:
+                black, white = self.areas()
+                self.finished = True
+                diff = 2 * black - 2 * white - self.komi2  # > 0: black wins
+                if diff != 0:
+                    self.winner = self.black_player_id if diff > 0 else self.white_player_id
+                    reward = 1.0 if self.winner == me else -1.0
+            self.last_was_pass = passed
+        done = self.is_game_over
+        if not done:
+            self.current_player = opp
+            self._rebuild_mask()
+        self.steps += 1
+        return self.observation(), reward, done, {}
+
+    def is_current_player_won(self) -> bool:
+        return self.winner is not None and self.winner == self.current_player
+
+    def observation(self) -> np.ndarray:
+        me, opp = self.current_player, self.opponent_player
+        out = np.zeros(self.observation_shape, dtype=np.int8)
+        out[0:2 * self.stack_history:2] = self.feature_planes[me]
+        out[1:2 * self.stack_history:2] = self.feature_planes[opp]
+        out[-1] = 1 if me == self.black_player_id else 0
+        return out
+
+
 class ScaledFloatFrame:
     """`gym_env.py:214-224`: frames as float32 scaled to [0, 1] (x / 255).  Host-stepped self-play with device frame stacking
     recognises it inside `StackFrameAndAction` and uploads the raw uint8 frames instead, scaled on the device to the same values."""

@@ -214,7 +214,7 @@ class EpisodeAssembler:
         del self.open[b][:n]
 
 
-DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari', 'Catch', 'Breakout', 'ConnectFour', 'Othello')
+DEVICE_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Synthetic-Atari', 'Catch', 'Breakout', 'ConnectFour', 'Othello', 'Go')
 
 
 def _catch_args(env) -> dict:
@@ -239,6 +239,16 @@ IMAGE_GAMES = {
 def _connect4_num_to_win(env, config) -> int:
     """Stones in a line that win Connect Four: off a `games.ConnectFourEnv` object, else off the config (`make_connect4_config`), else 4."""
     return int(getattr(env, 'num_to_win', None) or getattr(config, 'num_to_win', None) or 4)
+
+
+def _go_args(env, config) -> dict:
+    """Go's rules as the planner's Go resets take them: off a `games.GoEnv` object, else off the config (`make_go_config`), else the
+    defaults (komi2 15, max_plies 0 = 2 * rows * cols, resignation allowed)."""
+    def pick(name, default):
+        v = getattr(env, name, None)
+        v = getattr(config, name, None) if v is None else v
+        return default if v is None else v
+    return dict(komi2=int(pick('komi2', 15)), max_plies=int(pick('max_plies', 0)), allow_resign=bool(pick('allow_resign', True)))
 
 
 MAX_ENV_THREADS = 16
@@ -312,7 +322,8 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
                   record_format: str = 'f32') -> int:
     """Self-play until `stop_event` is set (pipeline.py:41-167).  `env` names a device environment ('CartPole-v1',
     'TicTacToe', 'Gomoku', 'ConnectFour' (`games.ConnectFourEnv` on the device, on the board net's own (9, rows, cols) input), 'Othello'
-    (`games.OthelloEnv` likewise, rows * cols + 2 actions),
+    (`games.OthelloEnv` likewise, rows * cols + 2 actions), 'Go' (`games.GoEnv` likewise; komi2, max_plies and allow_resign off the env
+    object, else off the config, else 15 / 2 * rows * cols / True),
     'Synthetic-Atari': random frames standing in for the absent emulator, or 'Catch': `games.CatchEnv` on the
     device, its grid read off `env` when that is a CatchEnv object, else 12 x 12 on the network's frame, or 'Breakout': `games.BreakoutEnv`
     likewise, with its brick rows and move cap); `config.num_envs` of them advance in lock-step on GPU `device`.  `data_queue` is either a queue -- items put on it are the reference's
@@ -358,6 +369,8 @@ def run_self_play(config, rank, network, device, env, data_queue, train_steps_co
         p.selfplay_reset_connect4(_connect4_num_to_win(env, config), board_temperature_switch(config, train_steps_counter.value) if config.is_board_game else 0)
     elif name == 'Othello':
         p.selfplay_reset_othello(board_temperature_switch(config, train_steps_counter.value) if config.is_board_game else 0)
+    elif name == 'Go':
+        p.selfplay_reset_go(temp_switch_steps=board_temperature_switch(config, train_steps_counter.value) if config.is_board_game else 0, **_go_args(env, config))
     else:
         p.selfplay_reset(kinds[name])
     asm = EpisodeAssembler(config, num_envs, getattr(network, 'input_shape', None))
@@ -486,7 +499,7 @@ def _run_self_play_host(config, rank, network, device, envs, data_queue, train_s
 # ------------------------------------------------------------------------------------------------------------------
 # evaluation matches on the device arena (Planner.arena_*)
 # ------------------------------------------------------------------------------------------------------------------
-ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Catch', 'Breakout', 'ConnectFour', 'Othello')
+ARENA_ENVS = ('CartPole-v1', 'TicTacToe', 'Gomoku', 'Catch', 'Breakout', 'ConnectFour', 'Othello', 'Go')
 _UNFINISHED, _WIN_CHALLENGER, _WIN_OPPONENT, _DRAW = 0, 1, 2, 3  # planner.ARENA_* (kept here so this module imports without the library)
 
 
@@ -566,7 +579,7 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
                init_state=None) -> MatchResult:
     """`num_games` evaluation games in lock-step on the GPU (Planner.arena_*), every searched move a deterministic search
     (pipeline.py:374, 468).  `opponent`: a network (two-player envs), 'random' (two-player envs), or None (one-player envs).  `env`: a
-    device-env name ('TicTacToe', 'Gomoku', 'ConnectFour', 'Othello', 'CartPole-v1', 'Catch', 'Breakout') or an env object with a device twin.  Two-player envs: `num_games` must be
+    device-env name ('TicTacToe', 'Gomoku', 'ConnectFour', 'Othello', 'Go', 'CartPole-v1', 'Catch', 'Breakout') or an env object with a device twin.  Two-player envs: `num_games` must be
     even -- the challenger plays black in the first half and white in the second, game i and game i + num_games / 2 share their
     `opening_plies` random opening plies (default: 2 against a network, 0 otherwise; deterministic play from one opening would repeat one
     game).  `init_state`: CartPole start states [num_games, 4].  `tag` names the match in error messages.
@@ -629,6 +642,10 @@ def play_match(config, challenger_network, opponent, device, env, num_games: int
         elif name == 'Othello':
             p.arena_reset_othello(q if is_net else opponent, int(opening_plies))
             cap = 2 * (p.obs_dim // 9 - 4)  # at most nn - 4 placements, each after at most one pass
+        elif name == 'Go':
+            go = _go_args(env, config)
+            p.arena_reset_go(q if is_net else opponent, int(opening_plies), **go)
+            cap = go['max_plies'] or 2 * (p.obs_dim // 9)  # the ply that ends the game by the count
         else:
             p.arena_reset(kinds[name], q if is_net else opponent, int(opening_plies), init_state)
             cap = p.A - 1 if two else 500

@@ -15,6 +15,7 @@ NET_MLP, NET_BOARD, NET_ATARI = 0, 1, 2
 ENV_NONE, ENV_CARTPOLE, ENV_TICTACTOE, ENV_GOMOKU, ENV_SYNTHETIC, ENV_EXTERNAL, ENV_CATCH, ENV_BREAKOUT = 0, 1, 2, 3, 4, 5, 6, 7
 ENV_CONNECT4 = 8
 ENV_OTHELLO = 9
+ENV_GO = 10
 _NET_KINDS = {'mlp': NET_MLP, 'board': NET_BOARD, 'atari': NET_ATARI}
 ARENA_NONE, ARENA_RANDOM, ARENA_PLANNER = 0, 1, 2  # opponent kinds of mz_arena_reset
 SIDE_CHALLENGER, SIDE_OPPONENT, SIDE_RANDOM, SIDE_OPENING = 0, 1, 2, 3  # who chose a ply's move (arena_read_ply 'side')
@@ -29,6 +30,7 @@ ABI_SYMBOLS = [
     'mz_selfplay_record_info',
     'mz_selfplay_attach_replay', 'mz_selfplay_reset_external', 'mz_selfplay_external_act', 'mz_selfplay_external_commit',
     'mz_selfplay_reset_catch', 'mz_selfplay_reset_breakout', 'mz_selfplay_reset_othello', 'mz_othello_debug_step', 'mz_othello_debug_mask', 'mz_othello_debug_board',
+    'mz_selfplay_reset_go', 'mz_go_debug_step', 'mz_go_debug_mask', 'mz_go_debug_board', 'mz_arena_reset_go',
     'mz_arena_reset', 'mz_arena_step', 'mz_arena_read_ply', 'mz_arena_result',
     'mz_arena_reset_catch', 'mz_arena_reset_breakout', 'mz_arena_reset_othello', 'mz_arena_reset_external', 'mz_arena_external_act', 'mz_arena_external_commit',
     'mz_profile_begin', 'mz_profile_end', 'mz_planner_synchronize',
@@ -80,6 +82,10 @@ class MzConnect4Env(C.Structure):
 
 class MzOthelloEnv(C.Structure):
     _fields_ = [('temp_switch_steps', C.c_int32)]
+
+
+class MzGoEnv(C.Structure):
+    _fields_ = [('temp_switch_steps', C.c_int32), ('komi2', C.c_int32), ('max_plies', C.c_int32), ('allow_resign', C.c_int32)]
 
 
 _lib = None
@@ -140,6 +146,11 @@ def load_library():
     L.mz_othello_debug_mask.argtypes = [vp, vp]
     L.mz_othello_debug_board.argtypes = [vp, vp]
     L.mz_arena_reset_othello.argtypes = [vp, C.POINTER(MzOthelloEnv), i32, vp, i32]
+    L.mz_selfplay_reset_go.argtypes = [vp, C.POINTER(MzGoEnv)]
+    L.mz_go_debug_step.argtypes = [vp, vp]
+    L.mz_go_debug_mask.argtypes = [vp, vp]
+    L.mz_go_debug_board.argtypes = [vp, vp]
+    L.mz_arena_reset_go.argtypes = [vp, C.POINTER(MzGoEnv), i32, vp, i32]
     L.mz_arena_reset.argtypes = [vp, i32, i32, vp, i32, vp]
     L.mz_arena_step.argtypes = [vp, i32]
     L.mz_arena_read_ply.argtypes = [vp] + [vp] * 9
@@ -642,6 +653,34 @@ class Planner:
         _chk(self.lib.mz_othello_debug_board(self.h, _p(b)))
         return b
 
+    def selfplay_reset_go(self, komi2=15, max_plies=0, allow_resign=True, temp_switch_steps=0):
+        """Start self-play on the device Go env (mz_selfplay_reset_go; `games.GoEnv` is the same game on the host): the board is the
+        planner's own (9, rows, cols) input, rows and cols in 3..19 (square above 64 points), `num_actions` = rows * cols + 2
+        (placements, pass, resign).  `komi2`: twice the komi; `max_plies`: the ply that ends the game by the count (0: 2 * rows * cols);
+        `allow_resign` False: the resignation is never legal; `temp_switch_steps`: the board temperature schedule's switch from 1.0 to
+        0.1 (0: 6)."""
+        x = MzGoEnv(int(temp_switch_steps), int(komi2), int(max_plies), int(bool(allow_resign)))
+        _chk(self.lib.mz_selfplay_reset_go(self.h, C.byref(x)))
+
+    def debug_go_step(self, actions):
+        """Test hook (mz_go_debug_step): one move of all envs with `actions` [B] through the launches of a self-play move, without the
+        search; the recorded policy is the one-hot of the action, the root value 0.  An illegal action raises before any launch."""
+        a = np.ascontiguousarray(actions, np.int32).reshape(self.B)
+        _chk(self.lib.mz_go_debug_step(self.h, _p(a)))
+
+    def debug_go_mask(self):
+        """Test hook (mz_go_debug_mask): the device Go envs' legal-action masks, uint8 [B, A]."""
+        m = np.empty((self.B, self.A), np.uint8)
+        _chk(self.lib.mz_go_debug_mask(self.h, _p(m)))
+        return m
+
+    def debug_go_board(self):
+        """Test hook (mz_go_debug_board): the device Go envs' boards, int8 [B, rows * cols] (0 empty, 1 black, 2 white); in an arena a
+        finished game's row is its frozen final board, captures included."""
+        b = np.empty((self.B, self.obs_dim // 9), np.int8)
+        _chk(self.lib.mz_go_debug_board(self.h, _p(b)))
+        return b
+
     def selfplay_read(self, n_moves, fields=None):
         """Records of the last `n_moves` moves, arrays [n_moves, B, ...].  `fields`: subset of ('obs', 'action', 'reward', 'pi',
         'root_value', 'player', 'done') to copy out (default all): with the device epilogue attached a host loop only needs
@@ -750,6 +789,20 @@ class Planner:
             raise ValueError(f"opponent must be 'random' or a Planner, got {opponent!r}")
         x = MzOthelloEnv(0)
         _chk(self.lib.mz_arena_reset_othello(self.h, C.byref(x), kind, q.h if q is not None else None, int(opening_plies)))
+        self._arena_opponent = q
+
+    def arena_reset_go(self, opponent, opening_plies=0, komi2=15, max_plies=0, allow_resign=True):
+        """Start `num_envs` evaluation games of the device Go env (mz_arena_reset_go): `arena_reset`'s two-player arena -- `opponent`
+        'random' or a second `Planner`, colours balanced over the two halves, paired random openings -- on this game, with
+        `selfplay_reset_go`'s rules.  Random moves are drawn from the legal placements and the pass: they never resign."""
+        if isinstance(opponent, Planner):
+            kind, q = ARENA_PLANNER, opponent
+        elif opponent == 'random':
+            kind, q = ARENA_RANDOM, None
+        else:
+            raise ValueError(f"opponent must be 'random' or a Planner, got {opponent!r}")
+        x = MzGoEnv(0, int(komi2), int(max_plies), int(bool(allow_resign)))
+        _chk(self.lib.mz_arena_reset_go(self.h, C.byref(x), kind, q.h if q is not None else None, int(opening_plies)))
         self._arena_opponent = q
 
     def arena_reset_catch(self, rows=12, cols=12, ball_cols=None, start_rows=None):
